@@ -18,6 +18,12 @@ weights: random init (no network in this environment).
 stock`` runs the reference stack on the same model and data (ATen/MIOpen
 BatchNorm+ReLU+add, autocast bf16 over f32 params, torch.optim.AdamW,
 torch DDP over RCCL) — the comparator recorded in BASELINE.md.
+
+A plain run sets up, warms up, times the K steps and prints the JSON line.
+``--dump-outputs DIR`` also writes the last timed step's loss, logits and a seeded
+sample of the updated parameters as float32 ``DIR/<name>.npy`` (same arguments ->
+same inputs, so two builds compare output for output); ``--full`` adds the
+reports the headline figure does not need (the conv routing table, route by route).
 """
 from __future__ import annotations
 
@@ -65,7 +71,35 @@ def _parser() -> argparse.ArgumentParser:
                     help="replay the whole native step (fwd, bwd, all-reduce, clip, AdamW) as one hipGraph "
                          "(utils.GraphedStep; auto = on for a single rank).  Off by default: the eager ResNet-50 "
                          "step is GPU-bound (22.5 ms eager vs 22.9 ms replayed, profiles/r02_lmdb)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32): loss, logits, and a fixed seeded sample of the updated parameters.  Same "
+                         "arguments -> same inputs, so two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also report what the headline figure does not need (stderr): the conv routing table "
+                         "route by route")
     return ap
+
+
+_DUMP_PARAM_SAMPLE = 1 << 22  # parameters sampled into params.npy (16 MiB of float32)
+
+
+def _dump_outputs(path: str, loss, logits, model) -> None:
+    """``--dump-outputs``: the last timed step's results as float32 ``.npy`` files.  ``loss`` and
+    ``logits`` are what the step's caller holds; ``params.npy`` is a seeded sample (sorted flat
+    indices, the same for every run) of the parameters the step's optimizer update left behind."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(path, "logits.npy"), logits.detach().float().cpu().numpy())
+    flat = torch.cat([p.detach().float().reshape(-1) for p in model.parameters()])
+    n = flat.numel()
+    if n > _DUMP_PARAM_SAMPLE:
+        idx = np.sort(np.random.RandomState(0).choice(n, _DUMP_PARAM_SAMPLE, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    np.save(os.path.join(path, "params.npy"), flat.cpu().numpy())
 
 
 def main() -> int:
@@ -144,6 +178,7 @@ def _rank_main(opts: dict) -> int:
     x = torch.randn(B, 3, S, S, device=dev).contiguous(memory_format=torch.channels_last)
     y = torch.randint(0, 1000, (B,), device=dev)
     n_iter = a.warmup + a.steps + 10
+    last_logits = [None]  # the newest step's logits (a reference only; --dump-outputs writes them)
 
     if a.mode == "native":
         from torchbooster_amd.ops.optim import FusedAdamW
@@ -167,6 +202,7 @@ def _rank_main(opts: dict) -> int:
 
         def train():
             logits = model(x)
+            last_logits[0] = logits.detach()
             loss, acc = cross_entropy_accuracy(logits, y, 0.1)
             utils.step(loss, opt, None, clip=1.0)
             return loss
@@ -191,6 +227,7 @@ def _rank_main(opts: dict) -> int:
         def step():
             with torch.autocast("cuda", dtype=torch.bfloat16):
                 logits = model(x)
+                last_logits[0] = logits.detach()
                 loss = F.cross_entropy(logits, y, label_smoothing=0.1)
             utils.step(loss, opt, sched, clip=1.0)
             return loss
@@ -297,10 +334,13 @@ def _rank_main(opts: dict) -> int:
             tab = autotune_table()
             nat = sum(v == "native" for v in tab.values())
             print(f"[bench] conv routing: {nat}/{len(tab)} (direction, shape) pairs native", file=sys.stderr)
-            for k, v in sorted(tab.items(), key=str):
-                print(f"[bench]   {v:7s} {k}", file=sys.stderr)
-            if a.mode == "native" and ddp is not None:
+            if a.full:  # the whole table, route by route
+                for k, v in sorted(tab.items(), key=str):
+                    print(f"[bench]   {v:7s} {k}", file=sys.stderr)
+            if ddp is not None:
                 print(f"[bench] ddp buckets (MiB): {[round(x, 2) for x in ddp.bucket_sizes_mb()]}", file=sys.stderr)
+        if a.dump_outputs:
+            _dump_outputs(a.dump_outputs, loss, last_logits[0], model)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if "RANK" in os.environ:  # torchrun / env:// rank: ours to tear down (dist.job tears its own down)
         dist.destroy()
