@@ -24,6 +24,18 @@
 // come from a zero page (keys are masked to -inf, queries are not stored).
 // Workgroups are remapped so that the blocks of one (batch, head) run on the
 // same XCD and share its L2 for K/V (or Q/dO).
+//
+// Masks (AttnArgs::causal, AttnArgs::klen; self-attention): query i of batch b sees keys
+// j < min(klen[b], causal ? i + 1 : N), klen[b] clamped into [1, N] in the kernel.  Every kernel is
+// a template on MASK: the <false> instantiations are the dense kernels, the <true> ones are launched
+// only when a mask is requested.  The masked kernels SKIP tiles no query of the workgroup (or wave)
+// sees, run the dense tile body on tiles wholly inside every limit of the wave, and the masked body
+// (the per-lane limit in place of N in the EDGE compares) only on tiles a limit cuts through: the
+// causal diagonal and the length edge.  Tiles run in increasing key order and tile 0 always holds
+// key 0, which every query sees, so the running max is finite before any tile in which a query sees
+// nothing (there p = exp2(-inf) = 0 and alpha = 1).  In the 128-row kernels the tile loop bounds are
+// workgroup-uniform: a wave past its own limit skips the compute of a tile, never its staging or
+// its barrier.
 #include <type_traits>
 
 #include "common.h"
@@ -35,6 +47,11 @@ namespace {
 
 constexpr int kBlk = 128;           // queries (fwd, dQ) or keys (dK/dV) per workgroup: 4 waves x 32
 constexpr float kLog2e = 1.4426950408889634f;
+
+// keys visible in batch b before the causal limit: klen[b] clamped into [1, N] (N without lengths)
+__device__ __forceinline__ int key_len(const AttnArgs& a, int b) {
+  return a.klen ? min(max(a.klen[b], 1), a.N) : a.N;
+}
 
 // XCD-aware block order: consecutive logical ids (the blocks of one (b, h)) on one XCD
 __device__ __forceinline__ void block_coords(int nblk, int H, int& x, int& h, int& b) {
@@ -78,10 +95,13 @@ __device__ __forceinline__ void fwd_store(const AttnArgs& a, int b, int h, int q
 // EDGE: the tile holds keys past N (the last tile when N % 64 != 0): only there are the key mask
 // and the sub-tile skips compiled in.  exp2: the bare v_exp_f32 (__builtin_amdgcn_exp2f; exp2f adds a
 // range reduction for denormal results -- an ldexp, two selects and an add per score).
-template <bool EDGE>
+// LIM (masked kernels, with EDGE): N is the largest key limit of the wave's queries (sub-tile skips)
+// and lim[qt] the lane's own query's limit, which replaces N in the key mask.
+template <bool EDGE, bool LIM = false>
 __device__ __forceinline__ void fwd_tile(const uint4* Kt, const uint4* Vt, int t, int N, int nqt, float c,
                                          const bf16x8_t (&qf)[2][2], f32x4_t (&acc)[4][2], float (&m)[2],
-                                         float (&l)[2], int fr, int fg) {
+                                         float (&l)[2], int fr, int fg, const int (&lim)[2]) {
+  static_assert(EDGE || !LIM, "the masked body is an edge body");
   // valid keys in this tile: 16-key sub-tiles (and 32-key PV steps) past N are skipped
   // (N = 197 -> the last tile holds 5 keys: 13 sub-tiles of 16 computed instead of 16)
   const int nvk = EDGE ? N - t * kTile : kTile;
@@ -112,7 +132,7 @@ __device__ __forceinline__ void fwd_tile(const uint4* Kt, const uint4* Vt, int t
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         if constexpr (EDGE) {
-          if (key0 + 16 * mt + i >= N) s[mt][qt][i] = -INFINITY;
+          if (key0 + 16 * mt + i >= (LIM ? lim[qt] : N)) s[mt][qt][i] = -INFINITY;
         }
         mx = fmaxf(mx, s[mt][qt][i]);
       }
@@ -150,6 +170,23 @@ __device__ __forceinline__ void fwd_tile(const uint4* Kt, const uint4* Vt, int t
   }
 }
 
+// The key limits of a wave's 32 queries q0 .. q0 + 31 (masked forward and dQ kernels)
+struct QLim {
+  int lim[2];  // the lane's own queries' limits (q0 + 16 qt + fr)
+  int lo, hi;  // smallest / largest limit in the wave (wave-uniform)
+};
+
+__device__ __forceinline__ QLim q_limits(const AttnArgs& a, int len, int q0, int fr) {
+  QLim r;
+  const int wq0 = __builtin_amdgcn_readfirstlane(q0);
+  r.lo = a.causal ? min(len, wq0 + 1) : len;
+  r.hi = a.causal ? min(len, wq0 + 32) : len;
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) r.lim[qt] = a.causal ? min(len, q0 + 16 * qt + fr + 1) : len;
+  return r;
+}
+
+template <bool MASK>
 __global__ __launch_bounds__(256, 2) void attn_fwd_k(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) uint4 lds[2 * 2 * kTileU4];  // [buf][K | V] = 32 KiB
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -183,7 +220,18 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_k(AttnArgs a) {
     for (int qt = 0; qt < 2; ++qt) acc[dt][qt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   float m[2] = {-INFINITY, -INFINITY}, l[2] = {0.f, 0.f};
 
-  const int nt = (N + kTile - 1) / kTile;
+  // nt: tiles the workgroup visits (workgroup-uniform: every wave stages and meets the barrier of
+  // each); nfull: the leading tiles the wave runs with the unmasked body
+  int nt = (N + kTile - 1) / kTile, nfull = N / kTile;
+  QLim ql{};
+  if constexpr (MASK) {
+    const int len = key_len(a, b);
+    ql = q_limits(a, len, q0, fr);
+    // the largest limit of the workgroup's queries: key tiles past it are never staged
+    const int lim_wg = a.causal ? min(len, min(N, xb * kBlk + kBlk)) : len;
+    nt = (lim_wg + kTile - 1) / kTile;
+    nfull = min(nt, ql.lo / kTile);
+  }
   stage_tile(lds, kp, a.sk[2], 0, N, wave, lane);
   stage_tile(lds + kTileU4, vp, a.sv[2], 0, N, wave, lane);
   auto next = [&](int t) {
@@ -197,18 +245,25 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_k(AttnArgs a) {
   };
   // full tiles unmasked, the edge tile peeled, the query sub-tile count a constant (as the head
   // kernel); a wave with no query only helps stage tiles
-  const int nfull = N / kTile;
   auto run = [&](auto nq) {
     constexpr int NQ = decltype(nq)::value;
     for (int t = 0; t < nfull; ++t) {
       next(t);
       const uint4* Kt = lds + (t & 1) * 2 * kTileU4;
-      if (wave_live) fwd_tile<false>(Kt, Kt + kTileU4, t, N, NQ, c, qf, acc, m, l, fr, fg);
+      if (wave_live) fwd_tile<false>(Kt, Kt + kTileU4, t, N, NQ, c, qf, acc, m, l, fr, fg, ql.lim);
     }
-    if (nfull < nt) {
+    if constexpr (MASK) {
+      // tiles a limit of the wave cuts through; past the wave's largest limit only stage and sync
+      for (int t = nfull; t < nt; ++t) {
+        next(t);
+        const uint4* Kt = lds + (t & 1) * 2 * kTileU4;
+        if (wave_live && t * kTile < ql.hi)
+          fwd_tile<true, true>(Kt, Kt + kTileU4, t, ql.hi, NQ, c, qf, acc, m, l, fr, fg, ql.lim);
+      }
+    } else if (nfull < nt) {
       next(nfull);
       const uint4* Kt = lds + (nfull & 1) * 2 * kTileU4;
-      if (wave_live) fwd_tile<true>(Kt, Kt + kTileU4, nfull, N, NQ, c, qf, acc, m, l, fr, fg);
+      if (wave_live) fwd_tile<true>(Kt, Kt + kTileU4, nfull, N, NQ, c, qf, acc, m, l, fr, fg, ql.lim);
     }
   };
   if (nqt == 2) run(std::integral_constant<int, 2>{});
@@ -222,7 +277,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_k(AttnArgs a) {
 // The two 128-query workgroups of attn_fwd_k each staged K / V and paid a vmcnt(0) + barrier per
 // 64-key tile (64.5 us per ViT-B layer at 11 % MFMA busy, profiles/r05_vit/pmc_table_before_tnfill.txt).
 constexpr int kHeadWaves = 8, kHeadTiles = 4;
-__global__ __launch_bounds__(512, 2) void attn_fwd_head_k(AttnArgs a) {
+// (The masked instantiation takes 130 VGPRs, two over what two workgroups per CU allow: it asks for one.)
+template <bool MASK>
+__global__ __launch_bounds__(512, MASK ? 1 : 2) void attn_fwd_head_k(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) uint4 lds[2 * kHeadTiles * kTileU4];  // [K tiles | V tiles]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fg = lane >> 4;
@@ -231,7 +288,12 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_head_k(AttnArgs a) {
   const uint16_t* qp = head(a.q, a.sq, b, h);
   const uint16_t* kp = head(a.k, a.sk, b, h);
   const uint16_t* vp = head(a.v, a.sv, b, h);
-  const int nt = (N + kTile - 1) / kTile;  // <= kHeadTiles (host check)
+  int nt = (N + kTile - 1) / kTile;  // <= kHeadTiles (host check)
+  int len = N;
+  if constexpr (MASK) {
+    len = key_len(a, b);  // the last query's limit under either mask: later key tiles are not staged
+    nt = (len + kTile - 1) / kTile;
+  }
   {
     const bool kv = wave >= 4;
     uint4* base = lds + (kv ? kHeadTiles * kTileU4 : 0);
@@ -264,12 +326,24 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_head_k(AttnArgs a) {
   // cost 168 VGPRs, one workgroup per CU)
   // (the query sub-tile count stays a runtime value here: as a constant, two loop copies took 130
   // VGPRs -- 128 forced -- and measured 92 vs 89 us per call, r5_43)
-  const int nfull = N / kTile;
+  int nfull = N / kTile;
+  QLim ql{};
+  if constexpr (MASK) {
+    ql = q_limits(a, len, q0, fr);
+    nfull = ql.lo / kTile;
+    nt = (ql.hi + kTile - 1) / kTile;  // the wave's own last tile
+  }
   for (int t = 0; t < nfull; ++t)
-    fwd_tile<false>(lds + t * kTileU4, lds + (kHeadTiles + t) * kTileU4, t, N, nqt, c, qf, acc, m, l, fr, fg);
-  if (nfull < nt)
+    fwd_tile<false>(lds + t * kTileU4, lds + (kHeadTiles + t) * kTileU4, t, N, nqt, c, qf, acc, m, l, fr, fg,
+                    ql.lim);
+  if constexpr (MASK) {
+    for (int t = nfull; t < nt; ++t)
+      fwd_tile<true, true>(lds + t * kTileU4, lds + (kHeadTiles + t) * kTileU4, t, ql.hi, nqt, c, qf, acc, m, l, fr,
+                           fg, ql.lim);
+  } else if (nfull < nt) {
     fwd_tile<true>(lds + nfull * kTileU4, lds + (kHeadTiles + nfull) * kTileU4, nfull, N, nqt, c, qf, acc, m, l, fr,
-                   fg);
+                   fg, ql.lim);
+  }
   fwd_store(a, b, h, q0, acc, m, l, fr, fg);
 }
 
@@ -309,9 +383,12 @@ __device__ __forceinline__ void dq_rows(const AttnArgs& a, int b, int h, int q0,
 }
 
 // One 64-key tile of the dQ pass: Sᵀ = K·Qᵀ, dPᵀ = V·dOᵀ, dSᵀ = Pᵀ∘(dPᵀ-δ), dQᵀ += Kᵀ·dSᵀ
-template <bool EDGE>
+// (LIM: as fwd_tile)
+template <bool EDGE, bool LIM = false>
 __device__ __forceinline__ void dq_tile(const uint4* Kt, const uint4* Vt, int t, int N, int nqt, float c,
-                                        const DqRows& r, f32x4_t (&acc)[4][2], int fr, int fg) {
+                                        const DqRows& r, f32x4_t (&acc)[4][2], int fr, int fg,
+                                        const int (&lim)[2]) {
+  static_assert(EDGE || !LIM, "the masked body is an edge body");
   const int nvk = EDGE ? N - t * kTile : kTile;  // valid keys in the tile
   f32x4_t s[4][2], dp[4][2];
 #pragma unroll
@@ -343,7 +420,8 @@ __device__ __forceinline__ void dq_tile(const uint4* Kt, const uint4* Vt, int t,
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float p =
-            !EDGE || key0 + 16 * mt + i < N ? __builtin_amdgcn_exp2f(s[mt][qt][i] * c - r.lse2[qt]) : 0.f;
+            !EDGE || key0 + 16 * mt + i < (LIM ? lim[qt] : N) ? __builtin_amdgcn_exp2f(s[mt][qt][i] * c - r.lse2[qt])
+                                                              : 0.f;
         s[mt][qt][i] = p * (dp[mt][qt][i] - r.delta[qt]);  // dS (in units of the scaled scores)
       }
 #pragma unroll
@@ -378,7 +456,10 @@ __device__ __forceinline__ void dq_store(const AttnArgs& a, int b, int h, int q0
 // 3 waves per SIMD (154 VGPRs): three 4-wave workgroups per CU.  (A whole-head dQ -- one 8-wave
 // workgroup per (batch, head), K / V staged once, as attn_fwd_head_k -- measured 174 vs 165 us per
 // ViT-B call and was removed, profiles/r05_vit.)
-__global__ __launch_bounds__(256, 3) void attn_bwd_dq_k(AttnArgs a) {
+// (The masked instantiation takes 176 VGPRs -- 32 B of scratch when held to 168 -- so it has bounds
+// of its own: two waves per SIMD.)
+template <bool MASK>
+__global__ __launch_bounds__(256, MASK ? 2 : 3) void attn_bwd_dq_k(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) uint4 lds[2 * 2 * kTileU4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fg = lane >> 4;
@@ -399,7 +480,15 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_k(AttnArgs a) {
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) acc[dt][qt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-  const int nt = (N + kTile - 1) / kTile;
+  int nt = (N + kTile - 1) / kTile, nfull = N / kTile;  // (both as the forward)
+  QLim ql{};
+  if constexpr (MASK) {
+    const int len = key_len(a, b);
+    ql = q_limits(a, len, q0, fr);
+    const int lim_wg = a.causal ? min(len, min(N, xb * kBlk + kBlk)) : len;
+    nt = (lim_wg + kTile - 1) / kTile;
+    nfull = min(nt, ql.lo / kTile);
+  }
   stage_tile(lds, kp, a.sk[2], 0, N, wave, lane);
   stage_tile(lds + kTileU4, vp, a.sv[2], 0, N, wave, lane);
   // tile t landed (every wave is done with the other buffer) -> stage tile t + 1 into it
@@ -413,7 +502,6 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_k(AttnArgs a) {
     }
   };
   // full tiles unmasked, the edge tile peeled (one body per loop keeps the VGPR count down)
-  const int nfull = N / kTile;
   // the query sub-tile count as a constant: the waves of one workgroup may run different copies of
   // the loop, which pass the same barriers in the same order
   auto run = [&](auto nq) {
@@ -421,12 +509,19 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_k(AttnArgs a) {
     for (int t = 0; t < nfull; ++t) {
       next(t);
       const uint4* Kt = lds + (t & 1) * 2 * kTileU4;
-      if (wave_live) dq_tile<false>(Kt, Kt + kTileU4, t, N, NQ, c, r, acc, fr, fg);
+      if (wave_live) dq_tile<false>(Kt, Kt + kTileU4, t, N, NQ, c, r, acc, fr, fg, ql.lim);
     }
-    if (nfull < nt) {
+    if constexpr (MASK) {
+      for (int t = nfull; t < nt; ++t) {  // (as the forward)
+        next(t);
+        const uint4* Kt = lds + (t & 1) * 2 * kTileU4;
+        if (wave_live && t * kTile < ql.hi)
+          dq_tile<true, true>(Kt, Kt + kTileU4, t, ql.hi, NQ, c, r, acc, fr, fg, ql.lim);
+      }
+    } else if (nfull < nt) {
       next(nfull);
       const uint4* Kt = lds + (nfull & 1) * 2 * kTileU4;
-      if (wave_live) dq_tile<true>(Kt, Kt + kTileU4, nfull, N, NQ, c, r, acc, fr, fg);
+      if (wave_live) dq_tile<true>(Kt, Kt + kTileU4, nfull, N, NQ, c, r, acc, fr, fg, ql.lim);
     }
   };
   if (nqt == 2) run(std::integral_constant<int, 2>{});
@@ -457,10 +552,12 @@ __device__ __forceinline__ void kv_rows(const AttnArgs& a, int b, int h, int k0,
 
 // One 64-query tile: S = Q·Kᵀ, dP = dO·Vᵀ (key on the lane), dVᵀ += dOᵀ·P, dKᵀ += Qᵀ·dS.
 // lse_t / del_t: the tile's 64 log2-domain log-sum-exps (+inf past N) and deltas in LDS.
-template <bool EDGE>
+// LIM (masked kernels): qmin[kt] is the first query that sees the lane's key (the key itself when
+// causal, 0 otherwise, INT_MAX for a key at or past the length): P = 0 for the queries before it.
+template <bool EDGE, bool LIM = false>
 __device__ __forceinline__ void dkdv_tile(const uint4* Qt, const uint4* Dt, const float* lse_t, const float* del_t,
                                           int t, int N, int nkt, float c, const KvRows& r, f32x4_t (&dv)[4][2],
-                                          f32x4_t (&dk)[4][2], int fr, int fg) {
+                                          f32x4_t (&dk)[4][2], int fr, int fg, const int (&qmin)[2]) {
   const int nvq = EDGE ? N - t * kTile : kTile;  // valid queries in the tile
   f32x4_t s[4][2], dp[4][2];
 #pragma unroll
@@ -494,7 +591,10 @@ __device__ __forceinline__ void dkdv_tile(const uint4* Qt, const uint4* Dt, cons
     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float p = __builtin_amdgcn_exp2f(s[mt][kt][i] * c - lv[i]);
+        float p = __builtin_amdgcn_exp2f(s[mt][kt][i] * c - lv[i]);
+        if constexpr (LIM) {
+          if (t * kTile + 16 * mt + 4 * fg + i < qmin[kt]) p = 0.f;
+        }
         s[mt][kt][i] = p;
         dp[mt][kt][i] = p * (dp[mt][kt][i] - dl[i]);
       }
@@ -540,6 +640,33 @@ __device__ __forceinline__ void dkdv_store(const AttnArgs& a, int b, int h, int 
   }
 }
 
+// The query limits of a wave's 32 keys k0 .. k0 + 31 and its query tile ranges (masked dK/dV
+// kernels).  Of the tiles [t0, t_end) the wave visits, [t0, tm) take the masked body -- every tile
+// when the length cuts through the wave's keys, else the causal diagonal -- and [tm, t_end) the
+// unmasked ones.
+struct KLim {
+  int qmin[2];  // the first query that sees the lane's own keys (k0 + 16 kt + fr); INT_MAX: none
+  int k0;       // wave-uniform copy of the wave's first key
+  bool work;    // some key of the wave is inside the length
+  int tm;
+};
+
+__device__ __forceinline__ KLim k_limits(const AttnArgs& a, int len, int k0, int fr, int t0, int t_end) {
+  KLim r;
+  r.k0 = __builtin_amdgcn_readfirstlane(k0);
+  r.work = r.k0 < len;
+#pragma unroll
+  for (int kt = 0; kt < 2; ++kt) {
+    const int ki = k0 + 16 * kt + fr;
+    r.qmin[kt] = ki < len ? (a.causal ? ki : 0) : INT_MAX;
+  }
+  // causal: the first tile whose every query sees every key of the wave starts at or after k0 + 31
+  const int tm = r.k0 + 32 > len ? t_end : a.causal ? (r.k0 + 31 + kTile - 1) / kTile : t0;
+  r.tm = min(max(tm, t0), t_end);
+  return r;
+}
+
+template <bool MASK>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_k(AttnArgs a) {
   // [buf][Q | dO] tiles, then [buf][lse2 | delta] x 64 floats
   __shared__ __attribute__((aligned(16))) uint4 lds[2 * 2 * kTileU4 + 2 * 2 * kTile / 4];
@@ -581,25 +708,67 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_k(AttnArgs a) {
   };
 
   const int nt = (N + kTile - 1) / kTile;
-  issue(0, 0);
-  auto next = [&](int t) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (t + 1 < nt) issue(t + 1, (t & 1) ^ 1);
-  };
-  // full tiles unmasked, the edge tile peeled
   const int nfull = N / kTile;
-  for (int t = 0; t < nfull; ++t) {
-    next(t);
-    const uint4* Qt = lds + (t & 1) * 2 * kTileU4;
-    const float* lse_t = rowc + (t & 1) * 2 * kTile;
-    if (wave_live) dkdv_tile<false>(Qt, Qt + kTileU4, lse_t, lse_t + kTile, t, N, nkt, c, r, dv, dk, fr, fg);
-  }
-  if (nfull < nt) {
-    next(nfull);
-    const uint4* Qt = lds + (nfull & 1) * 2 * kTileU4;
-    const float* lse_t = rowc + (nfull & 1) * 2 * kTile;
-    if (wave_live) dkdv_tile<true>(Qt, Qt + kTileU4, lse_t, lse_t + kTile, nfull, N, nkt, c, r, dv, dk, fr, fg);
+  if constexpr (MASK) {
+    // Query tiles [t0, t_end), workgroup-uniform: causal starts at the first tile that can see the
+    // workgroup's first key (t0 <= nfull as xb * kBlk < N); a key block wholly past the length runs
+    // no tile, stages nothing and stores its zero accumulators.
+    const int len = key_len(a, b);
+    const int t0 = a.causal ? xb * (kBlk / kTile) : 0;
+    const int t_end = xb * kBlk < len ? nt : t0;
+    const KLim kl = k_limits(a, len, k0, fr, t0, t_end);
+    const bool work = wave_live && kl.work;
+    if (t0 < t_end) issue(t0, t0 & 1);
+    auto next = [&](int t) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (t + 1 < t_end) issue(t + 1, (t & 1) ^ 1);
+    };
+    // every wave passes next(t) for t = t0 .. t_end - 1 exactly once, in order, whichever loop it is in
+    for (int t = t0; t < kl.tm; ++t) {
+      next(t);
+      const uint4* Qt = lds + (t & 1) * 2 * kTileU4;
+      const float* lse_t = rowc + (t & 1) * 2 * kTile;
+      // (causal: a tile whose last query is before the wave's first key only stages and syncs)
+      if (work && (!a.causal || (t + 1) * kTile > kl.k0))
+        dkdv_tile<true, true>(Qt, Qt + kTileU4, lse_t, lse_t + kTile, t, N, nkt, c, r, dv, dk, fr, fg, kl.qmin);
+    }
+    const int nf = min(nfull, t_end);
+    for (int t = kl.tm; t < nf; ++t) {
+      next(t);
+      const uint4* Qt = lds + (t & 1) * 2 * kTileU4;
+      const float* lse_t = rowc + (t & 1) * 2 * kTile;
+      if (work) dkdv_tile<false>(Qt, Qt + kTileU4, lse_t, lse_t + kTile, t, N, nkt, c, r, dv, dk, fr, fg, kl.qmin);
+    }
+    if (nfull < t_end && kl.tm <= nfull) {  // the edge tile, unless the masked loop took it
+      next(nfull);
+      const uint4* Qt = lds + (nfull & 1) * 2 * kTileU4;
+      const float* lse_t = rowc + (nfull & 1) * 2 * kTile;
+      if (work)
+        dkdv_tile<true>(Qt, Qt + kTileU4, lse_t, lse_t + kTile, nfull, N, nkt, c, r, dv, dk, fr, fg, kl.qmin);
+    }
+  } else {
+    const int none[2] = {0, 0};
+    issue(0, 0);
+    auto next = [&](int t) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (t + 1 < nt) issue(t + 1, (t & 1) ^ 1);
+    };
+    // full tiles unmasked, the edge tile peeled
+    for (int t = 0; t < nfull; ++t) {
+      next(t);
+      const uint4* Qt = lds + (t & 1) * 2 * kTileU4;
+      const float* lse_t = rowc + (t & 1) * 2 * kTile;
+      if (wave_live) dkdv_tile<false>(Qt, Qt + kTileU4, lse_t, lse_t + kTile, t, N, nkt, c, r, dv, dk, fr, fg, none);
+    }
+    if (nfull < nt) {
+      next(nfull);
+      const uint4* Qt = lds + (nfull & 1) * 2 * kTileU4;
+      const float* lse_t = rowc + (nfull & 1) * 2 * kTile;
+      if (wave_live)
+        dkdv_tile<true>(Qt, Qt + kTileU4, lse_t, lse_t + kTile, nfull, N, nkt, c, r, dv, dk, fr, fg, none);
+    }
   }
   dkdv_store(a, b, h, k0, dk, dv, fr, fg);
 }
@@ -607,6 +776,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_k(AttnArgs a) {
 // Whole-head dK/dV (N <= 256): one 8-wave workgroup per (batch, head) stages the head's Q and dO
 // whole (waves 0-3 Q, 4-7 dO) and its log-sum-exps / deltas (kHeadTiles x 64 each) behind one wait
 // and one barrier; each wave then runs its 32 keys over every query tile from LDS
+// (Masked: every query tile is staged -- the first keys are seen by every query, and queries past the
+// length are computed like any other -- and the tile ranges are the wave's own.)
+template <bool MASK>
 __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_head_k(AttnArgs a) {
   constexpr int kRows = kHeadTiles * kTile;
   __shared__ __attribute__((aligned(16))) uint4 lds[2 * kHeadTiles * kTileU4 + 2 * kRows / 4];
@@ -651,12 +823,29 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_head_k(AttnArgs a) {
   const int nfull = N / kTile;
   auto run = [&](auto nk) {  // the key sub-tile count as a constant (as the head forward)
     constexpr int NK = decltype(nk)::value;
-    for (int t = 0; t < nfull; ++t)
-      dkdv_tile<false>(lds + t * kTileU4, lds + (kHeadTiles + t) * kTileU4, rowc + t * kTile,
-                       rowc + kRows + t * kTile, t, N, NK, c, r, dv, dk, fr, fg);
-    if (nfull < nt)
-      dkdv_tile<true>(lds + nfull * kTileU4, lds + (kHeadTiles + nfull) * kTileU4, rowc + nfull * kTile,
-                      rowc + kRows + nfull * kTile, nfull, N, NK, c, r, dv, dk, fr, fg);
+    if constexpr (MASK) {
+      // the first tile with a query that sees a key of the wave
+      const int t0 = a.causal ? __builtin_amdgcn_readfirstlane(k0) / kTile : 0;
+      const KLim kl = k_limits(a, key_len(a, b), k0, fr, t0, nt);
+      if (!kl.work) return;  // every key of the wave is past the length: zeros are stored
+      for (int t = t0; t < kl.tm; ++t)
+        dkdv_tile<true, true>(lds + t * kTileU4, lds + (kHeadTiles + t) * kTileU4, rowc + t * kTile,
+                              rowc + kRows + t * kTile, t, N, NK, c, r, dv, dk, fr, fg, kl.qmin);
+      for (int t = kl.tm; t < nfull; ++t)
+        dkdv_tile<false>(lds + t * kTileU4, lds + (kHeadTiles + t) * kTileU4, rowc + t * kTile,
+                         rowc + kRows + t * kTile, t, N, NK, c, r, dv, dk, fr, fg, kl.qmin);
+      if (nfull < nt && kl.tm <= nfull)
+        dkdv_tile<true>(lds + nfull * kTileU4, lds + (kHeadTiles + nfull) * kTileU4, rowc + nfull * kTile,
+                        rowc + kRows + nfull * kTile, nfull, N, NK, c, r, dv, dk, fr, fg, kl.qmin);
+    } else {
+      const int none[2] = {0, 0};
+      for (int t = 0; t < nfull; ++t)
+        dkdv_tile<false>(lds + t * kTileU4, lds + (kHeadTiles + t) * kTileU4, rowc + t * kTile,
+                         rowc + kRows + t * kTile, t, N, NK, c, r, dv, dk, fr, fg, none);
+      if (nfull < nt)
+        dkdv_tile<true>(lds + nfull * kTileU4, lds + (kHeadTiles + nfull) * kTileU4, rowc + nfull * kTile,
+                        rowc + kRows + nfull * kTile, nfull, N, NK, c, r, dv, dk, fr, fg, none);
+    }
   };
   if (nkt == 2) run(std::integral_constant<int, 2>{});
   else run(std::integral_constant<int, 1>{});
@@ -681,24 +870,30 @@ int attn_set_head_mask(int mask) {
   return old;
 }
 
+// the masked instantiations run only when a mask is requested (same grids, same kernel choice)
 void attn_fwd(const AttnArgs& a, hipStream_t st) {
+  const bool mask = a.causal || a.klen;
   if ((g_attn_head & 1) && a.N <= kHeadTiles * kTile) {
-    hipLaunchKernelGGL(attn_fwd_head_k, dim3(a.H * a.B), dim3(kHeadWaves * 64), 0, st, a);
+    hipLaunchKernelGGL(mask ? attn_fwd_head_k<true> : attn_fwd_head_k<false>, dim3(a.H * a.B),
+                       dim3(kHeadWaves * 64), 0, st, a);
     return;
   }
   const int nblk = (a.N + kBlk - 1) / kBlk;
-  hipLaunchKernelGGL(attn_fwd_k, dim3(nblk * a.H * a.B), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(mask ? attn_fwd_k<true> : attn_fwd_k<false>, dim3(nblk * a.H * a.B), dim3(256), 0, st, a);
 }
 
 void attn_bwd(const AttnArgs& a, hipStream_t st) {
+  const bool mask = a.causal || a.klen;
   const bool fits = a.N <= kHeadTiles * kTile;
   const int nblk = (a.N + kBlk - 1) / kBlk;
   // dQ pass first: it also writes delta = rowsum(dO * O), which the dK/dV pass reads
-  hipLaunchKernelGGL(attn_bwd_dq_k, dim3(nblk * a.H * a.B), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(mask ? attn_bwd_dq_k<true> : attn_bwd_dq_k<false>, dim3(nblk * a.H * a.B), dim3(256), 0, st, a);
   if ((g_attn_head & 4) && fits)
-    hipLaunchKernelGGL(attn_bwd_dkdv_head_k, dim3(a.H * a.B), dim3(kHeadWaves * 64), 0, st, a);
+    hipLaunchKernelGGL(mask ? attn_bwd_dkdv_head_k<true> : attn_bwd_dkdv_head_k<false>, dim3(a.H * a.B),
+                       dim3(kHeadWaves * 64), 0, st, a);
   else
-    hipLaunchKernelGGL(attn_bwd_dkdv_k, dim3(nblk * a.H * a.B), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(mask ? attn_bwd_dkdv_k<true> : attn_bwd_dkdv_k<false>, dim3(nblk * a.H * a.B), dim3(256), 0,
+                       st, a);
 }
 
 }  // namespace tbamd

@@ -2039,8 +2039,26 @@ static void attn_view(const Tensor& t, const char* name, int64_t B, int64_t H, i
   *p = reinterpret_cast<const uint16_t*>(t.data_ptr());
 }
 
+// The masks (self-attention; both optional): causal, and key_lengths = [B] int32 on q's device,
+// contiguous -- keys j >= key_lengths[b] are hidden from every query of batch b.  The kernels read
+// the lengths from device memory (no host sync, graph-capture safe) and clamp each into [1, N].
+static void attn_masks(tbamd::AttnArgs& a, const Tensor& q, int64_t B, bool causal,
+                       const c10::optional<Tensor>& key_lengths) {
+  a.causal = causal ? 1 : 0;
+  a.klen = nullptr;
+  if (!key_lengths.has_value() || !key_lengths->defined()) return;
+  const Tensor& kl = *key_lengths;
+  check_cuda(kl, "key_lengths");
+  TORCH_CHECK(kl.scalar_type() == at::kInt, "attention: key_lengths must be int32");
+  TORCH_CHECK(kl.device() == q.device(), "attention: key_lengths must be on the device of q");
+  TORCH_CHECK(kl.dim() == 1 && kl.size(0) == B, "attention: key_lengths must have shape [B]");
+  TORCH_CHECK(kl.is_contiguous(), "attention: key_lengths must be contiguous");
+  a.klen = kl.data_ptr<int>();
+}
+
 // -> (o [B, N, H, 64] contiguous, lse [B, H, N] f32)
-std::vector<Tensor> attn_forward(const Tensor& q, const Tensor& k, const Tensor& v, double scale) {
+std::vector<Tensor> attn_forward(const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool causal,
+                                 const c10::optional<Tensor>& key_lengths) {
   const at::DeviceGuard guard(q.device());
   const int64_t B = q.size(0), H = q.size(1), N = q.size(2);
   TORCH_CHECK(N >= 1 && B * H * ((N + 127) / 128) < (int64_t)INT32_MAX, "attention: bad size");
@@ -2056,13 +2074,15 @@ std::vector<Tensor> attn_forward(const Tensor& q, const Tensor& k, const Tensor&
   a.o = const_cast<uint16_t*>(op);
   a.lse = lse.data_ptr<float>();
   a.B = (int)B, a.H = (int)H, a.N = (int)N, a.scale = (float)scale;
+  attn_masks(a, q, B, causal, key_lengths);
   tbamd::attn_fwd(a, cur_stream());
   return {o, lse};
 }
 
 // writes dq, dk, dv (views, e.g. slices of one packed dqkv buffer)
 void attn_backward(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o, const Tensor& dout,
-                   const Tensor& lse, double scale, const Tensor& dq, const Tensor& dk, const Tensor& dv) {
+                   const Tensor& lse, double scale, const Tensor& dq, const Tensor& dk, const Tensor& dv, bool causal,
+                   const c10::optional<Tensor>& key_lengths) {
   const at::DeviceGuard guard(q.device());
   const int64_t B = q.size(0), H = q.size(1), N = q.size(2);
   tbamd::AttnArgs a{};
@@ -2084,6 +2104,7 @@ void attn_backward(const Tensor& q, const Tensor& k, const Tensor& v, const Tens
   a.lse = lse.data_ptr<float>();
   a.delta = delta.data_ptr<float>();
   a.B = (int)B, a.H = (int)H, a.N = (int)N, a.scale = (float)scale;
+  attn_masks(a, q, B, causal, key_lengths);
   tbamd::attn_bwd(a, cur_stream());
 }
 
@@ -2507,8 +2528,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_stem_wgrad", &conv2d_stem_wgrad);
   m.def("scale_mt", &scale_mt);
   m.def("u8_crop_flip_normalize", &u8_crop_flip_normalize);
-  m.def("attn_forward", &attn_forward);
-  m.def("attn_backward", &attn_backward);
+  m.def("attn_forward", &attn_forward, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
+        py::arg("causal") = false, py::arg("key_lengths") = py::none());
+  m.def("attn_backward", &attn_backward, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("dout"),
+        py::arg("lse"), py::arg("scale"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("causal") = false,
+        py::arg("key_lengths") = py::none());
   m.def("attn_set_head_mask", [](int64_t m) { return (int64_t)tbamd::attn_set_head_mask((int)m); });
   m.def("gram_forward", &gram_forward);
   m.def("gram_sym", &gram_sym);

@@ -239,7 +239,8 @@ void conv_wgrad(const void* dy, const void* x, void* dw, float* workspace, int N
 // ---- fused attention (head dim 64, bf16) ----
 // Strides are in elements over (batch, head, token); the head-dim stride is 1.
 // Forward writes o and lse ([B][H][N] f32, natural log); backward reads q, k, v,
-// o, dout, lse and writes dq, dk, dv and delta ([B][H][N] f32 scratch).
+// o, dout, lse and writes dq, dk, dv and delta ([B][H][N] f32 scratch).  Every element of dq, dk,
+// dv is written (rows of dk / dv for keys a mask hides from every query are zeros).
 struct AttnArgs {
   const uint16_t* q;
   const uint16_t* k;
@@ -256,6 +257,12 @@ struct AttnArgs {
   uint16_t* dv;
   int64_t sdq[3], sdk[3], sdv[3];
   float* delta;
+  // masks (self-attention; both optional, combinable): query i of batch b sees keys
+  // j < min(klen[b], causal ? i + 1 : N).  klen: [B] int32 in device memory, read by the kernels
+  // (no host sync; a graph replay follows in-place changes) and clamped there into [1, N], so a bad
+  // value never moves an address and no row is fully masked.  nullptr: every key.
+  int causal;
+  const int* klen;
 };
 int attn_supported(int D);
 // whole-head kernel mask (1 forward, 4 dK/dV); mask < 0 only reads it.  Returns the previous mask.

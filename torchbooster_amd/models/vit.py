@@ -29,15 +29,20 @@ __all__ = ["ViT", "vit_b_16", "vit_s_16", "vit_tiny", "Attention", "Block"]
 
 
 class Attention(nn.Module):
-    def __init__(self, dim: int, heads: int) -> None:
+    """``causal``: query i attends to keys j <= i; ``key_lengths`` (int32 [B], clamped into [1, N]):
+    the keys of batch b at or past its length are hidden (ops/attention.py)."""
+
+    def __init__(self, dim: int, heads: int, causal: bool = False) -> None:
         super().__init__()
         self.heads = heads
         self.hd = dim // heads
+        self.causal = causal
         self.qkv = Linear(dim, 3 * dim)
         self.proj = Linear(dim, dim)
 
-    def forward(self, x: Tensor) -> Tensor:
-        return self.proj(attention_packed(self.qkv(x), self.heads, 1.0 / math.sqrt(self.hd)))
+    def forward(self, x: Tensor, key_lengths: Optional[Tensor] = None) -> Tensor:
+        return self.proj(attention_packed(self.qkv(x), self.heads, 1.0 / math.sqrt(self.hd), causal=self.causal,
+                                          key_lengths=key_lengths))
 
 
 class MLP(nn.Module):
@@ -54,21 +59,22 @@ class MLP(nn.Module):
 
 
 class Block(nn.Module):
-    def __init__(self, dim: int, heads: int, mlp_ratio: float = 4.0) -> None:
+    def __init__(self, dim: int, heads: int, mlp_ratio: float = 4.0, causal: bool = False) -> None:
         super().__init__()
         self.ln1 = LayerNorm(dim, eps=1e-6)
-        self.attn = Attention(dim, heads)
+        self.attn = Attention(dim, heads, causal)
         self.ln2 = LayerNorm(dim, eps=1e-6)
         self.mlp = MLP(dim, int(dim * mlp_ratio))
 
-    def forward(self, x: Tensor, pending: Optional[Tensor] = None):
+    def forward(self, x: Tensor, pending: Optional[Tensor] = None, key_lengths: Optional[Tensor] = None):
         """``x``: residual stream; ``pending``: a sub-block output not yet added
-        to it.  Returns (stream, pending) so adds fuse into the next LayerNorm."""
+        to it.  Returns (stream, pending) so adds fuse into the next LayerNorm.
+        ``key_lengths``: per-batch key lengths for the attention (None: every key)."""
         if pending is None:
             h = self.ln1(x)
         else:
             h, x = self.ln1(x, pending)
-        a = self.attn(h)
+        a = self.attn(h, key_lengths)
         h, x = self.ln2(x, a)
         return x, self.mlp(h)
 
