@@ -2108,6 +2108,110 @@ void attn_backward(const Tensor& q, const Tensor& k, const Tensor& v, const Tens
   tbamd::attn_bwd(a, cur_stream());
 }
 
+// ---- KV-cache decoding (csrc/attention_decode.hip).  Cache: [B, H, cap, 64] bf16 views (checked as
+// attn_view checks q/k/v); lengths / positions: [B] int32 on the same device, read by the kernels.
+static const int* decode_lengths(const Tensor& t, const char* name, const Tensor& like, int64_t B) {
+  check_cuda(t, name);
+  TORCH_CHECK(t.scalar_type() == at::kInt, "attention decode: ", name, " must be int32");
+  TORCH_CHECK(t.device() == like.device(), "attention decode: ", name, " must be on the device of the cache");
+  TORCH_CHECK(t.dim() == 1 && t.size(0) == B, "attention decode: ", name, " must have shape [B]");
+  TORCH_CHECK(t.is_contiguous(), "attention decode: ", name, " must be contiguous");
+  return t.data_ptr<int>();
+}
+
+// packed [B, T, 3*H*64] bf16: unit last stride, batch / token strides multiples of 8, 16-B aligned
+static const uint16_t* packed_qkv(const Tensor& t, int64_t B, int64_t H, const Tensor& like, int64_t* s) {
+  check_cuda(t, "qkv");
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16 && t.dim() == 3, "attention decode: qkv must be bf16 [B, T, 3*H*64]");
+  TORCH_CHECK(t.size(0) == B && t.size(2) == 3 * H * 64 && t.stride(2) == 1,
+              "attention decode: qkv shape/stride mismatch (head dim 64, unit stride)");
+  TORCH_CHECK(t.device() == like.device(), "attention decode: qkv must be on the device of the cache");
+  for (int i = 0; i < 2; ++i) {
+    TORCH_CHECK(t.stride(i) % 8 == 0 || t.size(i) == 1, "attention decode: qkv strides must be multiples of 8");
+    s[i] = t.stride(i);
+  }
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, "attention decode: qkv not 16-B aligned");
+  return reinterpret_cast<const uint16_t*>(t.data_ptr());
+}
+
+void attn_kv_append(const Tensor& qkv, int64_t heads, const Tensor& k_cache, const Tensor& v_cache,
+                    const Tensor& positions) {
+  const at::DeviceGuard guard(k_cache.device());
+  TORCH_CHECK(k_cache.dim() == 4 && heads >= 1 && k_cache.size(1) == heads,
+              "attention decode: cache must be [B, H, cap, 64]");
+  const int64_t B = k_cache.size(0), H = heads, cap = k_cache.size(2);
+  TORCH_CHECK(qkv.dim() == 3, "attention decode: qkv must be bf16 [B, T, 3*H*64]");
+  const int64_t T = qkv.size(1);
+  TORCH_CHECK(B >= 1 && cap >= 1 && T >= 0 && B * T * H < (int64_t)1 << 34 && cap < (int64_t)INT32_MAX,
+              "attention decode: bad size");
+  tbamd::AttnAppendArgs a{};
+  a.qkv = packed_qkv(qkv, B, H, k_cache, a.sqkv);
+  const uint16_t* p;
+  attn_view(k_cache, "k_cache", B, H, cap, &p, a.sk);
+  a.kc = const_cast<uint16_t*>(p);
+  attn_view(v_cache, "v_cache", B, H, cap, &p, a.sv);
+  a.vc = const_cast<uint16_t*>(p);
+  TORCH_CHECK(v_cache.device() == k_cache.device(), "attention decode: caches on different devices");
+  a.pos = decode_lengths(positions, "positions", k_cache, B);
+  a.B = (int)B, a.T = (int)T, a.H = (int)H, a.cap = (int)cap;
+  tbamd::attn_kv_append(a, cur_stream());
+}
+
+// q: [B, H, 64] (any batch / head strides) or the packed [B, 1, 3*H*64] whose q part is read in
+// place -> o [B, H*64].  len = clamp(lengths[b] + add, 1, cap).  workspace (optional, tests): f32,
+// at least attn_decode_workspace floats; by default it comes from the caching allocator.
+Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const Tensor& v_cache, const Tensor& lengths,
+                   int64_t add, double scale, const c10::optional<Tensor>& workspace) {
+  const at::DeviceGuard guard(k_cache.device());
+  TORCH_CHECK(k_cache.dim() == 4 && heads >= 1 && k_cache.size(1) == heads,
+              "attention decode: cache must be [B, H, cap, 64]");
+  const int64_t B = k_cache.size(0), H = heads, cap = k_cache.size(2);
+  TORCH_CHECK(B >= 1 && cap >= 1 && cap < (int64_t)INT32_MAX / 2 && add >= -cap && add <= cap,
+              "attention decode: bad size");
+  TORCH_CHECK(B * H * (int64_t)tbamd::attn_decode_chunks((int)cap) < (int64_t)INT32_MAX / 64,
+              "attention decode: bad size");
+  tbamd::AttnDecodeArgs a{};
+  if (q.dim() == 3 && q.size(1) == 1 && q.size(2) == 3 * H * 64) {
+    int64_t s[2];
+    a.q = packed_qkv(q, B, H, k_cache, s);
+    a.sq[0] = s[0], a.sq[1] = 64;
+  } else {
+    check_cuda(q, "q");
+    TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.dim() == 3 && q.size(0) == B && q.size(1) == H &&
+                    q.size(2) == 64 && q.stride(2) == 1,
+                "attention decode: q must be bf16 [B, H, 64] with a unit head-dim stride (or packed [B, 1, 3*H*64])");
+    TORCH_CHECK(q.device() == k_cache.device(), "attention decode: q must be on the device of the cache");
+    for (int i = 0; i < 2; ++i) {
+      TORCH_CHECK(q.stride(i) % 8 == 0 || q.size(i) == 1, "attention decode: q strides must be multiples of 8");
+      a.sq[i] = q.stride(i);
+    }
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0, "attention decode: q not 16-B aligned");
+    a.q = reinterpret_cast<const uint16_t*>(q.data_ptr());
+  }
+  attn_view(k_cache, "k_cache", B, H, cap, &a.k, a.sk);
+  attn_view(v_cache, "v_cache", B, H, cap, &a.v, a.sv);
+  TORCH_CHECK(v_cache.device() == k_cache.device(), "attention decode: caches on different devices");
+  a.klen = decode_lengths(lengths, "lengths", k_cache, B);
+  const int64_t need = tbamd::attn_decode_workspace((int)B, (int)H, (int)cap);
+  Tensor ws;
+  if (workspace.has_value() && workspace->defined()) {
+    ws = *workspace;
+    check_cuda(ws, "workspace");
+    TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() && ws.numel() >= need &&
+                    ws.device() == k_cache.device() && reinterpret_cast<uintptr_t>(ws.data_ptr()) % 16 == 0,
+                "attention decode: workspace must be contiguous, 16-B aligned f32 with at least ", need, " elements");
+  } else {
+    ws = at::empty({need}, k_cache.options().dtype(at::kFloat));
+  }
+  Tensor o = at::empty({B, H * 64}, k_cache.options());
+  a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
+  a.so[0] = H * 64, a.so[1] = 64;
+  a.ws = ws.data_ptr<float>();
+  a.B = (int)B, a.H = (int)H, a.cap = (int)cap, a.add = (int)add, a.scale = (float)scale;
+  tbamd::attn_decode(a, cur_stream());
+  return o;
+}
+
 // ------------------------------------------------------------ Gram matrix
 // f: [B, C, H, W] bf16 channels_last (NHWC memory) -> [B, C, C] f32 = F_b^T F_b * scale
 // x: bf16 [N, C, H, W] channels_last -> col [N*P*Q, KP] (KP = RSC rounded up to 8)
@@ -2534,6 +2638,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lse"), py::arg("scale"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("causal") = false,
         py::arg("key_lengths") = py::none());
   m.def("attn_set_head_mask", [](int64_t m) { return (int64_t)tbamd::attn_set_head_mask((int)m); });
+  m.def("attn_kv_append", &attn_kv_append, py::arg("qkv"), py::arg("heads"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("positions"));
+  m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("heads"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("lengths"), py::arg("add"), py::arg("scale"), py::arg("workspace") = py::none());
+  m.def("attn_decode_workspace", [](int64_t B, int64_t H, int64_t cap) {
+    return tbamd::attn_decode_workspace((int)B, (int)H, (int)cap);
+  });
+  m.def("attn_decode_set_chunk", [](int64_t n) {
+    TORCH_CHECK(n < 0 || (n >= 8 && n % 8 == 0 && n <= (1 << 20)), "attn_decode_set_chunk: a multiple of 8, >= 8");
+    return (int64_t)tbamd::attn_decode_set_chunk((int)n);
+  });
   m.def("gram_forward", &gram_forward);
   m.def("gram_sym", &gram_sym);
   m.def("im2col", &im2col);

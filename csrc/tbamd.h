@@ -270,6 +270,41 @@ int attn_set_head_mask(int mask);
 void attn_fwd(const AttnArgs& a, hipStream_t st);
 void attn_bwd(const AttnArgs& a, hipStream_t st);
 
+// ---- KV-cache incremental decoding (csrc/attention_decode.hip; head dim 64, bf16) ----
+// Cache, per layer: kc / vc [B][H][cap][64], strides in elements over (batch, head, row), head-dim
+// stride 1.  Append: the k and v rows of a packed qkv [B][T][3*H*64] (strides over batch, token) go
+// to cache rows pos[b] + t; a row outside [0, cap) is dropped.  pos: [B] int32, device memory.
+struct AttnAppendArgs {
+  const uint16_t* qkv;
+  uint16_t* kc;
+  uint16_t* vc;
+  const int* pos;
+  int B, T, H, cap;
+  int64_t sqkv[2], sk[3], sv[3];
+};
+void attn_kv_append(const AttnAppendArgs& a, hipStream_t st);
+// o[b][h][:] = softmax(q[b][h][:] . K[b][h][:len]^T * scale) . V[b][h][:len],
+// len = clamp(klen[b] + add, 1, cap); klen: [B] int32 in device memory, read by the kernels.  Rows at
+// or past len are never loaded.  q, o: strides over (batch, head).  ws: attn_decode_workspace(B, H,
+// cap) floats of per-chunk partials; chunk / nchunks / nparts are filled in by attn_decode.
+struct AttnDecodeArgs {
+  const uint16_t* q;
+  const uint16_t* k;
+  const uint16_t* v;
+  uint16_t* o;
+  const int* klen;
+  float* ws;
+  int B, H, cap, add;
+  float scale;
+  int64_t sq[2], sk[3], sv[3], so[2];
+  int chunk, nchunks, nparts;
+};
+// keys per workgroup (a multiple of 8, >= 8); n < 0 only reads it.  Returns the previous value.
+int attn_decode_set_chunk(int n);
+int attn_decode_chunks(int cap);
+int64_t attn_decode_workspace(int B, int H, int cap);  // floats
+void attn_decode(const AttnDecodeArgs& a, hipStream_t st);
+
 // ---- Gram matrix (NHWC bf16 features, C % 64 == 0) ----
 void gram_sym(const float* dg, void* sym, int B, int C, float scale, hipStream_t st);
 void im2col_nhwc(const void* x, void* col, int N, int H, int W, int C, int R, int S, int P, int Q, int stride,

@@ -11,10 +11,17 @@ LayerNorm and an untied, bias-free vocabulary projection.
 int32 ``[B]`` tensor of the valid tokens per sequence of a right-padded batch (clamped into ``[1, N]``
 by the attention, ops/attention.py).  Logits are returned for every position, padded ones included:
 the caller masks their loss.
+
+Generation (forward only, ``torch.no_grad()``): :class:`KVCache` holds the keys and values of every
+layer, ``prefill`` runs the prompt once and fills it, ``decode_step`` runs ONE new token per sequence
+against it (the split-KV decode kernels of csrc/attention_decode.hip) and ``generate`` ties the two to
+greedy / temperature / top-k sampling.  Nothing in a decode step reads a device value on the host --
+positions and lengths live in device memory -- so a step can be captured into a graph and replayed
+(``generate(graph=True)``).
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import List, Optional, Tuple
 
 import torch
 from torch import Tensor, nn
@@ -23,7 +30,47 @@ from torchbooster_amd.models.vit import Block
 from torchbooster_amd.ops.linear import Linear
 from torchbooster_amd.ops.norm import LayerNorm
 
-__all__ = ["TransformerLM", "gpt_tiny", "gpt2_small"]
+__all__ = ["TransformerLM", "KVCache", "gpt_tiny", "gpt2_small"]
+
+
+class KVCache:
+    """Per-layer keys and values of a :class:`TransformerLM` for ``batch`` sequences of up to ``capacity``
+    tokens (default and upper limit: the model's ``max_len``).
+
+    ``layers[i]`` is the ``(k, v)`` pair of block ``i``, each ``[B, H, capacity, hd]`` and uninitialised
+    (``torch.empty``): rows at or past a sequence's position never enter arithmetic (ops/attention.py).
+    ``positions`` (int32 ``[B]``) is the row each sequence writes next = the number of tokens it holds."""
+
+    def __init__(self, model: "TransformerLM", batch: int, capacity: Optional[int] = None, dtype=None,
+                 device=None) -> None:
+        capacity = model.max_len if capacity is None else int(capacity)
+        if not 1 <= capacity <= model.max_len:
+            raise ValueError(f"capacity {capacity} must be in [1, max_len = {model.max_len}]")
+        w = model.tok.weight
+        dtype = w.dtype if dtype is None else dtype
+        device = w.device if device is None else device
+        attn = model.blocks[0].attn
+        self.capacity = capacity
+        self.layers: List[Tuple[Tensor, Tensor]] = [
+            (torch.empty(batch, attn.heads, capacity, attn.hd, dtype=dtype, device=device),
+             torch.empty(batch, attn.heads, capacity, attn.hd, dtype=dtype, device=device))
+            for _ in model.blocks]
+        self.positions = torch.zeros(batch, dtype=torch.int32, device=device)
+
+    def reset(self) -> None:
+        self.positions.zero_()
+
+
+def _sample(logits: Tensor, temperature: float, top_k: Optional[int], generator) -> Tensor:
+    """[B, vocab] logits -> [B] token ids: argmax at temperature 0, else a draw from
+    softmax(logits / temperature) restricted to the top_k logits."""
+    if temperature == 0:
+        return logits.argmax(dim=-1)
+    z = logits.float() / temperature
+    if top_k is not None:
+        kth = z.topk(min(int(top_k), z.shape[-1]), dim=-1).values[:, -1:]
+        z = z.masked_fill(z < kth, float("-inf"))
+    return torch.multinomial(torch.softmax(z, dim=-1), 1, generator=generator)[:, 0]
 
 
 class TransformerLM(nn.Module):
@@ -54,6 +101,112 @@ class TransformerLM(nn.Module):
             x, pending = blk(x, pending, lengths)
         h, _ = self.norm(x, pending)
         return self.head(h)
+
+    # ---------------------------------------------------------------- generation (forward only)
+    def prefill(self, tokens: Tensor, lengths: Optional[Tensor] = None,
+                cache: Optional[KVCache] = None) -> Tuple[Tensor, KVCache]:
+        """Run the prompt ``[B, N]`` once (causal, ``key_lengths=lengths``) and fill ``cache`` (a fresh
+        full-size one by default) from row 0.  Returns the logits ``[B, vocab]`` of each sequence's last
+        valid token -- position ``lengths[b] - 1``, or ``N - 1`` -- and the cache, whose ``positions`` are
+        now the (clamped) lengths: the pad rows of a ragged batch are overwritten as each sequence grows."""
+        B, N = tokens.shape
+        if N > self.max_len:
+            raise ValueError(f"sequence length {N} exceeds max_len {self.max_len}")
+        with torch.no_grad():
+            if cache is None:
+                cache = KVCache(self, B)
+            if N > cache.capacity:
+                raise ValueError(f"prompt length {N} exceeds the cache capacity {cache.capacity}")
+            cache.positions.zero_()
+            x = self.tok(tokens) + self.pos[:, :N].to(self.tok.weight.dtype)
+            pending = None
+            for blk, kv in zip(self.blocks, cache.layers):
+                x, pending = blk(x, pending, lengths, cache=kv, positions=cache.positions)
+            if lengths is None:
+                cache.positions.fill_(N)
+                x, pending = x[:, N - 1:], pending[:, N - 1:]
+            else:
+                cache.positions.copy_(lengths.clamp(1, N))
+                last = (cache.positions.to(torch.int64) - 1)[:, None, None].expand(B, 1, x.shape[-1])
+                x, pending = x.gather(1, last), pending.gather(1, last)
+            h, _ = self.norm(x.contiguous(), pending.contiguous())
+            return self.head(h[:, 0]), cache
+
+    def decode_step(self, token: Tensor, cache: KVCache) -> Tensor:
+        """One new token per sequence, ``token`` ``[B]``, at ``cache.positions`` -> logits ``[B, vocab]``;
+        ``cache.positions`` advance by one in place.  No device value is read on the host."""
+        with torch.no_grad():
+            at = cache.positions.to(torch.int64).clamp(0, self.max_len - 1)
+            x = (self.tok(token) + self.pos[0].index_select(0, at).to(self.tok.weight.dtype))[:, None]
+            pending = None
+            for blk, kv in zip(self.blocks, cache.layers):
+                x, pending = blk(x, pending, cache=kv, positions=cache.positions)
+            h, _ = self.norm(x, pending)
+            logits = self.head(h[:, 0])
+            cache.positions.add_(1)
+            return logits
+
+    def generate(self, tokens: Tensor, max_new_tokens: int, lengths: Optional[Tensor] = None, *,
+                 temperature: float = 0.0, top_k: Optional[int] = None, eos: Optional[int] = None,
+                 generator=None, graph: bool = False) -> Tuple[Tensor, Tensor]:
+        """Continue the prompts ``tokens`` ``[B, N]`` (``lengths``: valid tokens of each, right-padded) by
+        ``max_new_tokens`` tokens -> ``(out [B, max_new_tokens], out_lengths [B])``.
+
+        ``temperature == 0`` is greedy; otherwise tokens are drawn from ``softmax(logits / temperature)``
+        restricted to the ``top_k`` logits with ``torch.multinomial(generator=generator)``.  With ``eos``, a
+        sequence that has produced it emits ``eos`` from then on and ``out_lengths`` counts its tokens up
+        to and including the first ``eos`` (the mask lives on the device: no per-step sync, no early exit).
+        ``graph=True`` (CUDA): after the prefill and one eager decode step, ONE decode step plus the
+        sampling is captured into a graph and replayed for the remaining tokens; greedy results equal
+        ``graph=False`` bit for bit."""
+        B, N = tokens.shape
+        max_new_tokens = int(max_new_tokens)
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be at least 1")
+        if N + max_new_tokens > self.max_len:
+            raise ValueError(f"prompt {N} + max_new_tokens {max_new_tokens} exceeds max_len {self.max_len}")
+        if graph and not tokens.is_cuda:
+            raise ValueError("graph=True needs CUDA tensors")
+        with torch.no_grad():
+            dev = tokens.device
+            cache = KVCache(self, B, capacity=N + max_new_tokens)
+            logits, _ = self.prefill(tokens, lengths, cache)
+            out = torch.zeros(B, max_new_tokens, dtype=torch.int64, device=dev)
+            out_lengths = torch.zeros(B, dtype=torch.int64, device=dev)
+            finished = torch.zeros(B, dtype=torch.bool, device=dev)
+            slot = torch.zeros(B, 1, dtype=torch.int64, device=dev)  # the column of `out` written next
+            cur = torch.zeros(B, dtype=torch.int64, device=dev)  # the token fed to the next decode step
+
+            def emit(logits: Tensor) -> None:
+                tok = _sample(logits, temperature, top_k, generator)
+                if eos is not None:
+                    tok = torch.where(finished, torch.full_like(tok, eos), tok)
+                out.scatter_(1, slot, tok[:, None])
+                out_lengths.add_((~finished).to(torch.int64))
+                if eos is not None:
+                    finished.logical_or_(tok == eos)
+                slot.add_(1)
+                cur.copy_(tok)
+
+            def step() -> None:
+                emit(self.decode_step(cur, cache))
+
+            emit(logits)
+            eager = max_new_tokens - 1
+            if graph and eager > 1:
+                step()  # warm-up: first-use work of the decode path happens outside the capture
+                eager = 0
+                g = torch.cuda.CUDAGraph()
+                if generator is not None and temperature != 0:
+                    g.register_generator_state(generator)
+                torch.cuda.synchronize()
+                with torch.cuda.graph(g):
+                    step()
+                for _ in range(max_new_tokens - 2):
+                    g.replay()
+            for _ in range(eager):
+                step()
+            return out, out_lengths
 
 
 def gpt_tiny(vocab: int = 256, max_len: int = 128) -> TransformerLM:

@@ -19,7 +19,7 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor, nn
 
-from torchbooster_amd.ops.attention import attention_packed
+from torchbooster_amd.ops.attention import attention_decode_packed, attention_packed, kv_cache_append
 from torchbooster_amd.ops.conv import Conv2d
 
 from torchbooster_amd.ops.norm import LayerNorm
@@ -30,7 +30,13 @@ __all__ = ["ViT", "vit_b_16", "vit_s_16", "vit_tiny", "Attention", "Block"]
 
 class Attention(nn.Module):
     """``causal``: query i attends to keys j <= i; ``key_lengths`` (int32 [B], clamped into [1, N]):
-    the keys of batch b at or past its length are hidden (ops/attention.py)."""
+    the keys of batch b at or past its length are hidden (ops/attention.py).
+
+    Incremental decoding (causal only, forward only): with ``cache=(k_cache, v_cache)``, each
+    ``[B, H, cap, hd]``, and ``positions`` (int32 [B], the row each sequence writes next), an ``x`` of
+    ``[B, 1, dim]`` is one decode step -- its k / v are appended at ``positions`` and the query attends to
+    the cache rows ``j <= positions[b]`` -- and an ``x`` of ``[B, N > 1, dim]`` is a prefill: the masked
+    self-attention as without a cache, plus one append of the same k / v at ``positions``."""
 
     def __init__(self, dim: int, heads: int, causal: bool = False) -> None:
         super().__init__()
@@ -40,9 +46,22 @@ class Attention(nn.Module):
         self.qkv = Linear(dim, 3 * dim)
         self.proj = Linear(dim, dim)
 
-    def forward(self, x: Tensor, key_lengths: Optional[Tensor] = None) -> Tensor:
-        return self.proj(attention_packed(self.qkv(x), self.heads, 1.0 / math.sqrt(self.hd), causal=self.causal,
-                                          key_lengths=key_lengths))
+    def forward(self, x: Tensor, key_lengths: Optional[Tensor] = None, *, cache=None,
+                positions: Optional[Tensor] = None) -> Tensor:
+        scale = 1.0 / math.sqrt(self.hd)
+        if cache is None:
+            return self.proj(attention_packed(self.qkv(x), self.heads, scale, causal=self.causal,
+                                              key_lengths=key_lengths))
+        if not self.causal:
+            raise ValueError("a KV cache needs causal attention")
+        if positions is None:
+            raise ValueError("a KV cache needs positions")
+        k_cache, v_cache = cache
+        qkv = self.qkv(x)
+        if x.shape[1] == 1:
+            return self.proj(attention_decode_packed(qkv, self.heads, k_cache, v_cache, positions, scale))
+        kv_cache_append(k_cache, v_cache, qkv, self.heads, positions)
+        return self.proj(attention_packed(qkv, self.heads, scale, causal=True, key_lengths=key_lengths))
 
 
 class MLP(nn.Module):
@@ -66,15 +85,17 @@ class Block(nn.Module):
         self.ln2 = LayerNorm(dim, eps=1e-6)
         self.mlp = MLP(dim, int(dim * mlp_ratio))
 
-    def forward(self, x: Tensor, pending: Optional[Tensor] = None, key_lengths: Optional[Tensor] = None):
+    def forward(self, x: Tensor, pending: Optional[Tensor] = None, key_lengths: Optional[Tensor] = None, *,
+                cache=None, positions: Optional[Tensor] = None):
         """``x``: residual stream; ``pending``: a sub-block output not yet added
         to it.  Returns (stream, pending) so adds fuse into the next LayerNorm.
-        ``key_lengths``: per-batch key lengths for the attention (None: every key)."""
+        ``key_lengths``: per-batch key lengths for the attention (None: every key).
+        ``cache`` / ``positions``: this layer's KV cache, passed to :class:`Attention`."""
         if pending is None:
             h = self.ln1(x)
         else:
             h, x = self.ln1(x, pending)
-        a = self.attn(h, key_lengths)
+        a = self.attn(h, key_lengths, cache=cache, positions=positions)
         h, x = self.ln2(x, a)
         return x, self.mlp(h)
 

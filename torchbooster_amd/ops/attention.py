@@ -29,6 +29,26 @@ Masks (self-attention, both optional and combinable, the same on every path):
 With both, query ``i`` of batch ``b`` sees keys ``j < min(key_lengths[b], i + 1)``.  The native
 kernels skip the key tiles no query of a workgroup sees instead of masking them; gradients of
 hidden keys are zeros.
+
+KV-cache decoding (forward only; csrc/attention_decode.hip).  A cache is, per layer, a ``k_cache`` and
+a ``v_cache`` of ``[B, H, cap, D]`` (``torch.empty`` is fine: see the guarantee below).
+
+* :func:`kv_cache_append` copies the k and v rows of a packed ``qkv`` ``[B, T, 3*H*D]`` into the
+  caches: token ``t`` of batch ``b`` goes to row ``positions[b] + t``; a row outside ``[0, cap)`` is
+  DROPPED (the rest of that batch is still written).  ``T = 1`` is a decode step, ``T = N`` a prefill.
+* :func:`attention_decode` attends one query per (batch, head), ``q`` ``[B, H, D]``, to the first
+  ``len = clamp(lengths[b], 1, cap)`` cache rows -- 0 behaves as 1, anything above ``cap`` as ``cap``.
+* :func:`attention_decode_packed` takes the ``[B, 1, 3*H*D]`` projection of one new token, appends
+  its k/v at ``positions[b]`` and attends to keys ``j <= positions[b]``, returning ``[B, 1, H*D]``.
+
+``lengths`` / ``positions`` are int32 ``[B]`` tensors on the inputs' device, read on the device like
+``key_lengths``: no host sync on any path, safe inside a graph capture, a replay follows in-place
+changes.  Cache rows at or past the length NEVER enter arithmetic -- the native kernels do not load
+them, the PyTorch path selects them away before the multiply -- so junk there (NaN / Inf bit patterns
+of an uninitialised cache, the pad rows of a ragged prefill) cannot reach the output.  The native path
+(CUDA, bf16, D = 64) splits the keys over workgroups (``attn_decode_set_chunk`` keys each, grid fixed
+from ``cap``) and merges the partials in a second launch in fixed order: deterministic, no atomics.
+These functions do not build an autograd graph and raise if an input requires grad in grad mode.
 """
 from __future__ import annotations
 
@@ -42,7 +62,8 @@ from torch.autograd.function import once_differentiable
 
 from torchbooster_amd.ops._ext import native, use_native
 
-__all__ = ["attention", "attention_packed", "attention_ref", "native_supported"]
+__all__ = ["attention", "attention_packed", "attention_ref", "native_supported", "kv_cache_append",
+           "attention_decode", "attention_decode_packed"]
 
 
 def _visible(N: int, device, causal: bool, key_lengths: Optional[Tensor]) -> Optional[Tensor]:
@@ -171,3 +192,107 @@ def attention_packed(qkv: Tensor, heads: int, scale: Optional[float] = None, *, 
     t = qkv.view(B, N, 3, heads, D).permute(2, 0, 3, 1, 4)
     o = _sdpa(t[0], t[1], t[2], scale, causal, key_lengths)
     return o.transpose(1, 2).reshape(B, N, heads * D)
+
+
+# ---------------------------------------------------------------- KV-cache decoding (forward only)
+def _forward_only(*tensors: Tensor) -> None:
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError("KV-cache decoding is forward-only: call it under torch.no_grad() or detach the inputs")
+
+
+def _check_cache(k_cache: Tensor, v_cache: Tensor, B: int, H: int, D: int, pos: Tensor, name: str) -> None:
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or tuple(k_cache.shape[:2]) != (B, H) \
+            or k_cache.shape[3] != D or k_cache.shape[2] < 1:
+        raise RuntimeError(f"k_cache / v_cache must be [B, H, cap, D] = [{B}, {H}, cap, {D}]")
+    if pos.dtype != torch.int32 or pos.shape != (B,) or pos.device != k_cache.device:
+        raise RuntimeError(f"{name} must be an int32 tensor of shape [B] on the device of the cache")
+
+
+def _decode_native(x: Tensor, k_cache: Tensor, v_cache: Tensor) -> bool:
+    return (native_supported(k_cache) and v_cache.dtype == torch.bfloat16 and v_cache.is_cuda and x.is_cuda
+            and x.dtype == torch.bfloat16 and _rows_ok(k_cache) and _rows_ok(v_cache))
+
+
+def _append_ref(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, positions: Tensor) -> None:
+    """The PyTorch path of :func:`kv_cache_append`: seen from the cache, row j of batch b takes token
+    j - positions[b] if that is one of the T tokens and keeps its bits otherwise (no host sync, no
+    duplicate scatter indices, out-of-range rows simply have no cache row that asks for them)."""
+    B, T, E3 = qkv.shape
+    D = E3 // (3 * heads)
+    cap = k_cache.shape[2]
+    t = torch.arange(cap, device=qkv.device)[None, :] - positions.to(torch.int64)[:, None]  # [B, cap]
+    take = ((t >= 0) & (t < T))[:, None, :, None]
+    idx = t.clamp(0, max(T - 1, 0))[:, :, None, None].expand(B, cap, heads, D)
+    kv = qkv.reshape(B, T, 3, heads, D)
+    for cache, i in ((k_cache, 1), (v_cache, 2)):
+        rows = kv[:, :, i].gather(1, idx).permute(0, 2, 1, 3).to(cache.dtype)  # [B, H, cap, D]
+        cache.copy_(torch.where(take, rows, cache))
+
+
+def _decode_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tensor, scale: float) -> Tensor:
+    """The PyTorch path of :func:`attention_decode` (softmax in fp32, or fp64 for fp64 inputs).  Hidden
+    rows are selected away before either product: a masked score is -inf whatever k held, and v is
+    zeroed there because 0 * NaN is NaN."""
+    cap = k_cache.shape[2]
+    n = lengths.to(torch.int64).clamp(1, cap)  # the kernels' clamp
+    vis = (torch.arange(cap, device=q.device)[None, :] < n[:, None])[:, None, :]  # [B, 1, cap]
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    s = torch.einsum("bhd,bhjd->bhj", q.to(ct), k_cache.to(ct)) * scale
+    p = torch.softmax(s.masked_fill(~vis, float("-inf")), dim=-1)
+    v = torch.where(vis[..., None], v_cache, torch.zeros((), dtype=v_cache.dtype, device=q.device)).to(ct)
+    return torch.einsum("bhj,bhjd->bhd", p, v).to(q.dtype)
+
+
+def kv_cache_append(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, positions: Tensor) -> None:
+    """Write the k / v rows of the packed ``qkv`` ``[B, T, 3*H*D]`` into ``k_cache`` / ``v_cache``
+    ``[B, H, cap, D]`` at rows ``positions[b] + t`` (int32 ``[B]``); rows outside ``[0, cap)`` are dropped."""
+    _forward_only(qkv, k_cache, v_cache)
+    if qkv.dim() != 3 or qkv.shape[2] % (3 * heads):
+        raise RuntimeError("qkv must be [B, T, 3*H*D]")
+    B, T, E3 = qkv.shape
+    with torch.no_grad():
+        if _decode_native(qkv, k_cache, v_cache):
+            qkv = qkv if _rows_ok(qkv) else qkv.contiguous()
+            native().attn_kv_append(qkv, heads, k_cache, v_cache, positions)
+            return
+        _check_cache(k_cache, v_cache, B, heads, E3 // (3 * heads), positions, "positions")
+        _append_ref(k_cache, v_cache, qkv, heads, positions)
+
+
+def attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tensor,
+                     scale: Optional[float] = None) -> Tensor:
+    """One query per (batch, head): ``q`` ``[B, H, D]`` against the first ``clamp(lengths[b], 1, cap)``
+    rows of ``k_cache`` / ``v_cache`` ``[B, H, cap, D]`` -> ``[B, H, D]``."""
+    _forward_only(q, k_cache, v_cache)
+    if q.dim() != 3:
+        raise RuntimeError("q must be [B, H, D]")
+    B, H, D = q.shape
+    scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
+    with torch.no_grad():
+        if _decode_native(q, k_cache, v_cache):
+            q = q if _rows_ok(q) else q.contiguous()
+            return native().attn_decode(q, H, k_cache, v_cache, lengths, 0, scale).view(B, H, D)
+        _check_cache(k_cache, v_cache, B, H, D, lengths, "lengths")
+        return _decode_ref(q, k_cache, v_cache, lengths, scale)
+
+
+def attention_decode_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
+                            scale: Optional[float] = None) -> Tensor:
+    """One decode step on the packed ``[B, 1, 3*H*D]`` projection of the new token: append its k / v at
+    row ``positions[b]``, then attend to keys ``j <= positions[b]`` -> ``[B, 1, H*D]``."""
+    _forward_only(qkv, k_cache, v_cache)
+    if qkv.dim() != 3 or qkv.shape[1] != 1 or qkv.shape[2] % (3 * heads):
+        raise RuntimeError("qkv must be [B, 1, 3*H*D]")
+    B, _, E3 = qkv.shape
+    D = E3 // (3 * heads)
+    scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
+    with torch.no_grad():
+        if _decode_native(qkv, k_cache, v_cache):
+            qkv = qkv if _rows_ok(qkv) else qkv.contiguous()
+            C = native()
+            C.attn_kv_append(qkv, heads, k_cache, v_cache, positions)
+            return C.attn_decode(qkv, heads, k_cache, v_cache, positions, 1, scale).view(B, 1, heads * D)
+        _check_cache(k_cache, v_cache, B, heads, D, positions, "positions")
+        _append_ref(k_cache, v_cache, qkv, heads, positions)
+        q = qkv.reshape(B, 3, heads, D)[:, 0]
+        return _decode_ref(q, k_cache, v_cache, positions.to(torch.int64) + 1, scale).reshape(B, 1, heads * D)
