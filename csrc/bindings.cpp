@@ -404,6 +404,63 @@ Tensor ce_backward(const Tensor& logits_, const Tensor& labels_, const Tensor& r
   return dl;
 }
 
+// ------------------------------------- fused vocabulary projection + cross entropy
+static void check_lm_operands(const Tensor& x, const Tensor& w, const Tensor& labels, const char* op) {
+  check_cuda(x, "x");
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16,
+              op, ": x [M, D] and weight [V, D] must be bf16");
+  TORCH_CHECK(x.stride(1) == 1 && x.stride(0) % 8 == 0 && w.is_contiguous() && x.size(1) == w.size(1) &&
+                  x.size(1) % 8 == 0,
+              op, ": D must be a multiple of 8, x row-major, weight contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+              op, ": operands must be 16-B aligned");
+  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.is_contiguous() &&
+                  labels.numel() == x.size(0),
+              op, ": labels must be a contiguous int64 [M] tensor on the device");
+  TORCH_CHECK(x.size(0) < (1ll << 31) && w.size(0) < (1ll << 31), op, ": dims too large");
+}
+
+int64_t lm_loss_tile_q() { return tbamd::lm_loss_tile_q(); }
+
+// -> {stats3 = (mean loss over valid rows, 0, n_valid), lse [M]}; no [M, V] tensor exists
+std::vector<Tensor> lm_loss_forward(const Tensor& x, const Tensor& w, const Tensor& labels, int64_t ignore_index) {
+  check_lm_operands(x, w, labels, "lm_loss_forward");
+  const at::DeviceGuard guard(x.device());
+  const int64_t M = x.size(0), V = w.size(0), K = x.size(1);
+  TORCH_CHECK(V > 0, "lm_loss_forward: empty vocabulary");
+  const int64_t nt = (V + tbamd::lm_loss_tile_q() - 1) / tbamd::lm_loss_tile_q();
+  auto fopt = x.options().dtype(at::kFloat);
+  Tensor part = at::empty({nt, M, 2}, fopt);
+  Tensor rows = at::empty({4, M}, fopt);  // xy, row loss, lse, row ok
+  Tensor stats = at::empty({3}, fopt);
+  tbamd::lm_loss_partials(x.data_ptr(), x.stride(0), w.data_ptr(), labels.data_ptr<int64_t>(), part.data_ptr<float>(),
+                          rows[0].data_ptr<float>(), (int)M, (int)V, (int)K, cur_stream());
+  tbamd::lm_loss_merge(part.data_ptr<float>(), rows[0].data_ptr<float>(), labels.data_ptr<int64_t>(), (int)M, (int)nt,
+                       (int)V, ignore_index, rows[1].data_ptr<float>(), rows[2].data_ptr<float>(),
+                       rows[3].data_ptr<float>(), stats.data_ptr<float>(), cur_stream());
+  return {stats, rows[2]};
+}
+
+// buf [M, ld] (bf16, contiguous, ld = v1 - v0 rounded up to 8) = d loss / d logits[:, v0:v1], pad columns zero
+void lm_loss_dlogits(const Tensor& x, const Tensor& w, const Tensor& labels, const Tensor& lse, const Tensor& stats,
+                     const Tensor& gout, int64_t v0, int64_t v1, int64_t ignore_index, const Tensor& buf) {
+  check_lm_operands(x, w, labels, "lm_loss_dlogits");
+  const at::DeviceGuard guard(x.device());
+  const int64_t M = x.size(0), V = w.size(0), K = x.size(1);
+  TORCH_CHECK(0 <= v0 && v0 < v1 && v1 <= V, "lm_loss_dlogits: bad column range");
+  const int64_t ld = (v1 - v0 + 7) / 8 * 8;
+  TORCH_CHECK(buf.is_cuda() && buf.scalar_type() == at::kBFloat16 && buf.dim() == 2 && buf.is_contiguous() &&
+                  buf.size(0) == M && buf.size(1) == ld && reinterpret_cast<uintptr_t>(buf.data_ptr()) % 16 == 0,
+              "lm_loss_dlogits: buf must be a contiguous bf16 [M, round8(v1 - v0)] tensor");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() && lse.numel() == M &&
+                  stats.scalar_type() == at::kFloat && stats.is_contiguous() && stats.numel() == 3 &&
+                  gout.scalar_type() == at::kFloat && gout.numel() == 1 && gout.is_cuda(),
+              "lm_loss_dlogits: lse [M], stats [3], gout [1] must be f32 device tensors");
+  tbamd::lm_loss_dlogits(x.data_ptr(), x.stride(0), w.data_ptr(), labels.data_ptr<int64_t>(), lse.data_ptr<float>(),
+                         stats.data_ptr<float>(), gout.data_ptr<float>(), buf.data_ptr(), ld, (int)M, (int)V, (int)K,
+                         (int)v0, (int)v1, ignore_index, cur_stream());
+}
+
 // ------------------------------------------- small fused losses / resampling
 static Tensor aux_part(const Tensor& like) {
   return at::empty({tbamd::aux_partials()}, like.options().dtype(at::kFloat));
@@ -2612,6 +2669,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("need_dres"), py::arg("dgamma_out") = py::none(), py::arg("dbeta_out") = py::none());
   m.def("ce_forward", &ce_forward);
   m.def("ce_backward", &ce_backward);
+  m.def("lm_loss_tile_q", &lm_loss_tile_q);
+  m.def("lm_loss_forward", &lm_loss_forward);
+  m.def("lm_loss_dlogits", &lm_loss_dlogits);
   m.def("adamw_mt", &adamw_mt, py::arg("chunks"), py::arg("nchunks"), py::arg("table"), py::arg("pdt"),
         py::arg("gdt"), py::arg("master"), py::arg("ema"), py::arg("amsgrad"), py::arg("lr"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2_sqrt"), py::arg("ema_decay"),

@@ -30,6 +30,13 @@
 // are remapped so one XCD runs contiguous tile ids (q fastest: the Q tiles of
 // one X panel share that XCD's L2).
 //
+// Language-model head (ops/loss.py linear_cross_entropy): two more epilogues of the same kernel
+// turn the logits tile S = X W^T into what the cross entropy needs without storing it.  kEpiLse
+// reduces each row of the tile to (max, sum exp) over its valid columns and picks the label's
+// logit; kEpiDlogits recomputes the tile over a vocabulary slice and writes the bf16 logits
+// gradient.  Both take any Q (vocabulary size), odd or below 8, and run one fixed tile with the
+// whole k per tile, so the recomputed logits equal the forward's bit for bit.
+//
 // Tails: P and Q arbitrary (out-of-range rows read a zero page, their outputs
 // are not stored), K % 8 == 0 (chunks past K read zeros).
 #include "common.h"
@@ -60,7 +67,10 @@ __device__ __forceinline__ int swz_t(int row) { return (((row >> 1) & 1) | (((ro
 
 // epilogue codes
 enum : int { kEpiNone = 0, kEpiBias = 1, kEpiBiasGelu = 2, kEpiBiasRes = 3, kEpiRes = 4, kEpiF32 = 5,
-             kEpiBiasRelu = 6, kEpiRelu = 7 };
+             kEpiBiasRelu = 6, kEpiRelu = 7,
+             // language-model head (ops/loss.py linear_cross_entropy): the logits tile is reduced /
+             // turned into its gradient in registers and never stored
+             kEpiLse = 8, kEpiDlogits = 9 };
 
 struct GemmArgs {
   const uint16_t* X;    // [P][K] (row stride ldx)
@@ -72,7 +82,23 @@ struct GemmArgs {
   float* part;          // split-K f32 partials [S][P][Q] (kEpiF32)
   int P, Q, K;
   int64_t ldx, ldy;
+  // kEpiLse / kEpiDlogits (Q = the valid columns of this launch, W already advanced to column v0)
+  const int64_t* labels;  // [P]
+  float2* lse_part;       // kEpiLse: (max, sum exp) per column tile and row, [ntq][P]
+  float* xy;              // kEpiLse: logit of the label column, [P]
+  const float* lse;       // kEpiDlogits: [P]
+  const float* stats;     // kEpiDlogits: [2] = number of valid rows
+  const float* gout;      // kEpiDlogits: [1]
+  int64_t ignore_index, v0, vocab;
 };
+
+// online log-sum-exp fold of (m1, s1) into (m, s); (-inf, 0) is the neutral element
+__device__ __forceinline__ void lse_fold(float& m, float& s, float m1, float s1) {
+  const float nm = fmaxf(m, m1);
+  if (nm == -INFINITY) return;
+  s = s * __expf(m - nm) + s1 * __expf(m1 - nm);
+  m = nm;
+}
 
 __device__ __forceinline__ float gelu_exact(float z) { return gelu_f(z); }
 
@@ -312,6 +338,79 @@ __global__ __launch_bounds__(kGemmThreads, 2) void gemm_k(GemmArgs a) {
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+  }
+
+  if constexpr (EPI == kEpiLse) {
+    // per row: max and sum exp over this tile's valid columns (q < Q: the columns past the
+    // vocabulary are excluded, not zero logits), from the unrounded f32 accumulators.  Lane ->
+    // 4 lane groups of the row (xor 16, 32) -> the WQ waves through LDS (the staging buffers are idle).
+    static_assert(BP <= kGemmThreads, "one thread per tile row folds the waves");
+    float2* red = reinterpret_cast<float2*>(lds);  // [WQ][BP]
+#pragma unroll
+    for (int j = 0; j < TP; ++j) {
+      const int pl = wp * PW + 16 * j + fr, p = p0 + pl;
+      // the label is only compared with column indices (never an address): -1 matches none
+      const int64_t y = p < a.P ? a.labels[p] : -1;
+      float m = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < TQ; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (q0 + wq * QW + 16 * i + 4 * fg + e < a.Q) m = fmaxf(m, acc[i][j][e]);
+      m = fmaxf(m, __shfl_xor(m, 16, 64));
+      m = fmaxf(m, __shfl_xor(m, 32, 64));
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < TQ; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int q = q0 + wq * QW + 16 * i + 4 * fg + e;
+          if (q < a.Q) {
+            s += __expf(acc[i][j][e] - m);
+            if ((int64_t)q == y && TB_BOUNDS_OK(p < a.P, kBndGemmDst)) a.xy[p] = acc[i][j][e];  // one writer per row
+          }
+        }
+      s += __shfl_xor(s, 16, 64);
+      s += __shfl_xor(s, 32, 64);
+      if (fg == 0) red[wq * BP + pl] = make_float2(m, s);
+    }
+    __syncthreads();
+    if (tid < BP && p0 + tid < a.P) {
+      float m = -INFINITY, s = 0.f;
+#pragma unroll
+      for (int w = 0; w < WQ; ++w) lse_fold(m, s, red[w * BP + tid].x, red[w * BP + tid].y);
+      if (TB_BOUNDS_OK(tq < ntq, kBndGemmDst)) a.lse_part[(int64_t)tq * a.P + p0 + tid] = make_float2(m, s);
+    }
+    return;
+  }
+
+  if constexpr (EPI == kEpiDlogits) {
+    // Y[p][q] = (exp(S - lse[p]) - [v0 + q == label]) * gout / n_valid in bf16; zeros for ignored
+    // rows and for the pad columns Q <= q < ldy (ldy = Q rounded up to 8)
+    const float g = a.gout[0] / a.stats[2];
+#pragma unroll
+    for (int j = 0; j < TP; ++j) {
+      const int p = p0 + wp * PW + 16 * j + fr;
+      if (p >= a.P) continue;
+      const int64_t y = a.labels[p];
+      const bool valid = y != a.ignore_index && y >= 0 && y < a.vocab;
+      const float lse = valid ? a.lse[p] : 0.f;
+      const int64_t yl = y - a.v0;  // the label's column in this slice (compared only)
+#pragma unroll
+      for (int i = 0; i < TQ; ++i) {
+        const int q = q0 + wq * QW + 16 * i + 4 * fg;
+        if (q >= a.ldy) continue;
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          v[e] = (valid && q + e < a.Q) ? (__expf(acc[i][j][e] - lse) - ((int64_t)(q + e) == yl ? 1.f : 0.f)) * g : 0.f;
+        const int64_t o = (int64_t)p * a.ldy + q;
+        if (TB_BOUNDS_OK(o + 4 <= (int64_t)a.P * a.ldy, kBndGemmDst))
+          *reinterpret_cast<uint2*>(a.Y + o) = make_uint2((uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16),
+                                                          (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16));
+      }
+    }
+    return;
   }
 
   if constexpr (EPI == kEpiF32) {
@@ -562,6 +661,38 @@ void gemm_bf16(const void* X, int64_t ldx, bool tx, const void* W, bool tw, void
     if (gs > 2048) gs = 2048;
     splitk_reduce_k<<<(int)gs, 256, 0, st>>>(part, splits, P, Q, (uint16_t*)Y, ldy);
   }
+}
+
+// ---- language-model head: fixed 256 x 128 tile (waves 4P x 2Q, 2 LDS stages), whole k per tile in
+// forward and backward alike, so the backward's recomputed logits equal the forward's bit for bit
+constexpr int kLmBP = 256, kLmBQ = 128, kLmWP = 4;
+int lm_loss_tile_q() { return kLmBQ; }
+
+// part[t][p] = (max, sum exp) of row p of X W^T over the columns of tile t (t < ceil(V / tile_q)),
+// xy[p] = the logit of column labels[p] (rows whose label is outside [0, V) are not written)
+void lm_loss_partials(const void* X, int64_t ldx, const void* W, const int64_t* labels, float* part, float* xy, int M,
+                      int V, int K, hipStream_t st) {
+  if (M <= 0 || V <= 0) return;
+  GemmArgs a{};
+  a.X = (const uint16_t*)X, a.W = (const uint16_t*)W, a.P = M, a.Q = V, a.K = K, a.ldx = ldx;
+  a.labels = labels, a.lse_part = reinterpret_cast<float2*>(part), a.xy = xy;
+  const int nwg = ((M + kLmBP - 1) / kLmBP) * ((V + kLmBQ - 1) / kLmBQ);
+  gemm_k<kLmBP, kLmBQ, kLmWP, false, false, kEpiLse, 2><<<dim3(nwg, 1), kGemmThreads, 0, st>>>(a);
+}
+
+// D [M][ldd] (bf16, ldd >= v1 - v0, ldd % 8 == 0) = the loss gradient w.r.t. the logits of columns
+// [v0, v1); W is the whole [V][K] weight
+void lm_loss_dlogits(const void* X, int64_t ldx, const void* W, const int64_t* labels, const float* lse,
+                     const float* stats3, const float* gout, void* D, int64_t ldd, int M, int V, int K, int v0, int v1,
+                     int64_t ignore_index, hipStream_t st) {
+  if (M <= 0 || v1 <= v0) return;
+  GemmArgs a{};
+  a.X = (const uint16_t*)X, a.W = (const uint16_t*)W + (int64_t)v0 * K, a.Y = (uint16_t*)D;
+  a.P = M, a.Q = v1 - v0, a.K = K, a.ldx = ldx, a.ldy = ldd;
+  a.labels = labels, a.lse = lse, a.stats = stats3, a.gout = gout;
+  a.ignore_index = ignore_index, a.v0 = v0, a.vocab = V;
+  const int nwg = ((M + kLmBP - 1) / kLmBP) * ((a.Q + kLmBQ - 1) / kLmBQ);
+  gemm_k<kLmBP, kLmBQ, kLmWP, false, false, kEpiDlogits, 2><<<dim3(nwg, 1), kGemmThreads, 0, st>>>(a);
 }
 
 // split count for a split-K GEMM: enough workgroups to cover the CUs twice, each

@@ -10,6 +10,7 @@
 //           per-row loss / lse / correct are written, then a single-block
 //           finalize produces mean loss and accuracy (deterministic).
 // backward: dlogits = (softmax - (1-ε)·onehot - ε/K) · gout / n_valid.
+// lm_merge_k: merge of the per-tile log-sum-exp partials of the fused language-model head.
 #include "common.h"
 #include "tbamd.h"
 
@@ -120,6 +121,41 @@ __global__ __launch_bounds__(256) void ce_bwd_k(const storage_t<DT>* __restrict_
     if (k == (int)y) d -= (1.f - smoothing);
     Elem<DT>::st(dx, k, d * g);
   }
+}
+
+// Fused vocabulary projection + cross entropy (ops/loss.py linear_cross_entropy): the GEMM epilogue
+// of csrc/gemm.hip leaves (max, sum exp) per column tile and row; one thread per row folds the
+// tiles in ascending order (adjacent threads read adjacent rows of a tile).  A row whose label is
+// ignore_index or outside [0, V) is ignored: loss 0, not counted (row_ok = -1, as ce_fwd_k marks it).
+__global__ __launch_bounds__(256) void lm_merge_k(const float2* __restrict__ part, const float* __restrict__ xy,
+                                                  const int64_t* __restrict__ labels, int M, int ntiles, int V,
+                                                  int64_t ignore_index, float* __restrict__ row_loss,
+                                                  float* __restrict__ row_lse, float* __restrict__ row_ok) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= M) return;
+  float m = -INFINITY, s = 0.f;
+  for (int t = 0; t < ntiles; ++t) {
+    const float2 v = part[(int64_t)t * M + p];
+    const float nm = fmaxf(m, v.x);
+    if (nm == -INFINITY) continue;
+    s = s * __expf(m - nm) + v.y * __expf(v.x - nm);  // rescale to the running maximum
+    m = nm;
+  }
+  const float lse = m + __logf(s);
+  const int64_t y = labels[p];
+  const bool valid = y != ignore_index && y >= 0 && y < V;
+  row_lse[p] = lse;
+  row_loss[p] = valid ? lse - xy[p] : 0.f;
+  row_ok[p] = valid ? 0.f : -1.f;
+}
+
+void lm_loss_merge(const float* part, const float* xy, const int64_t* labels, int M, int ntiles, int V,
+                   int64_t ignore_index, float* row_loss, float* row_lse, float* row_ok, float* stats3,
+                   hipStream_t st) {
+  if (M > 0)
+    lm_merge_k<<<cdiv(M, 256), 256, 0, st>>>(reinterpret_cast<const float2*>(part), xy, labels, M, ntiles, V,
+                                             ignore_index, row_loss, row_lse, row_ok);
+  ce_finalize_k<<<1, 256, 0, st>>>(row_loss, row_ok, M, stats3);  // (mean loss, 0, n_valid); NaN when none is valid
 }
 
 void ce_forward(int dt, const void* logits, const int64_t* labels, int64_t N, int K, float smoothing,

@@ -444,6 +444,18 @@ void gemm_bf16(const void* X, int64_t ldx, bool tx, const void* W, bool tw, void
                hipStream_t st);
 int gemm_pick_splits(int P, int Q, int K, int tile);
 
+// ---- fused vocabulary projection + cross entropy (gemm_k epilogues of csrc/gemm.hip; merge in csrc/loss.hip)
+int lm_loss_tile_q();
+void lm_loss_partials(const void* X, int64_t ldx, const void* W, const int64_t* labels, float* part, float* xy, int M,
+                      int V, int K, hipStream_t st);
+void lm_loss_dlogits(const void* X, int64_t ldx, const void* W, const int64_t* labels, const float* lse,
+                     const float* stats3, const float* gout, void* D, int64_t ldd, int M, int V, int K, int v0, int v1,
+                     int64_t ignore_index, hipStream_t st);
+// lse / loss of every row from the per-tile partials, then stats3 = (mean loss over valid rows, 0, n_valid)
+void lm_loss_merge(const float* part, const float* xy, const int64_t* labels, int M, int ntiles, int V,
+                   int64_t ignore_index, float* row_loss, float* row_lse, float* row_ok, float* stats3,
+                   hipStream_t st);
+
 // ---- one-shot all-reduce over IPC-mapped peer buffers (csrc/oneshot.hip)
 class OneShotComm {
  public:

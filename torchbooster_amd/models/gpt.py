@@ -10,7 +10,9 @@ LayerNorm and an untied, bias-free vocabulary projection.
 ``forward(tokens, lengths=None)``: ``tokens`` is an integer ``[B, N]`` tensor, ``lengths`` an optional
 int32 ``[B]`` tensor of the valid tokens per sequence of a right-padded batch (clamped into ``[1, N]``
 by the attention, ops/attention.py).  Logits are returned for every position, padded ones included:
-the caller masks their loss.
+the caller masks their loss.  ``features`` stops before the vocabulary projection, and ``loss`` trains
+through the fused head (ops/loss.py ``linear_cross_entropy``), which masks the padded positions itself
+and never stores the logits.
 
 Generation (forward only, ``torch.no_grad()``): :class:`KVCache` holds the keys and values of every
 layer, ``prefill`` runs the prompt once and fills it, ``decode_step`` runs ONE new token per sequence
@@ -28,6 +30,7 @@ from torch import Tensor, nn
 
 from torchbooster_amd.models.vit import Block
 from torchbooster_amd.ops.linear import Linear
+from torchbooster_amd.ops.loss import linear_cross_entropy
 from torchbooster_amd.ops.norm import LayerNorm
 
 __all__ = ["TransformerLM", "KVCache", "gpt_tiny", "gpt2_small"]
@@ -90,8 +93,8 @@ class TransformerLM(nn.Module):
                 if m.bias is not None:
                     nn.init.zeros_(m.bias)
 
-    def forward(self, tokens: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
-        """[B, N] token ids -> [B, N, vocab] logits."""
+    def features(self, tokens: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
+        """[B, N] token ids -> [B, N, dim], the output of the final LayerNorm (the input of ``head``)."""
         B, N = tokens.shape
         if N > self.max_len:
             raise ValueError(f"sequence length {N} exceeds max_len {self.max_len}")
@@ -100,7 +103,32 @@ class TransformerLM(nn.Module):
         for blk in self.blocks:
             x, pending = blk(x, pending, lengths)
         h, _ = self.norm(x, pending)
-        return self.head(h)
+        return h
+
+    def forward(self, tokens: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
+        """[B, N] token ids -> [B, N, vocab] logits."""
+        return self.head(self.features(tokens, lengths))
+
+    def loss(self, tokens: Tensor, lengths: Optional[Tensor] = None, targets: Optional[Tensor] = None, *,
+             ignore_index: int = -100) -> Tensor:
+        """Mean next-token cross entropy of ``tokens`` ``[B, N]`` as an f32 scalar, through the fused head
+        (ops/loss.py ``linear_cross_entropy``): no ``[B, N, vocab]`` logits are stored.
+
+        ``targets`` ``[B, N]`` are used as given (``ignore_index`` entries do not count).  Without them
+        ``targets[b, t] = tokens[b, t + 1]`` where ``t + 1 < clamp(lengths[b], 1, N)`` (``< N`` without
+        ``lengths``) and ``ignore_index`` elsewhere, built on the device without a sync: the last position
+        is always ignored, so all ``B * N`` rows go through the head without a slice copy."""
+        B, N = tokens.shape
+        if targets is None:
+            if N < 2:
+                raise ValueError("loss needs at least 2 tokens per sequence to form next-token targets")
+            nxt = torch.roll(tokens, -1, dims=1).to(torch.int64)
+            t1 = torch.arange(1, N + 1, device=tokens.device)
+            end = N if lengths is None else lengths.to(torch.int64).clamp(1, N)[:, None]
+            targets = torch.where(t1 < end, nxt, torch.full_like(nxt, ignore_index))
+        elif targets.shape != tokens.shape:
+            raise ValueError(f"targets {tuple(targets.shape)} must have the shape of tokens {tuple(tokens.shape)}")
+        return linear_cross_entropy(self.features(tokens, lengths), self.head.weight, targets, ignore_index)
 
     # ---------------------------------------------------------------- generation (forward only)
     def prefill(self, tokens: Tensor, lengths: Optional[Tensor] = None,
