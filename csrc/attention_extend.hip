@@ -1,0 +1,306 @@
+// KV-cache "extend" attention: T >= 1 new queries per (batch, head) against a cache that already
+// holds tokens.  Head dim 64, bf16, gfx950, wave64.
+//
+// Not in the reference (it has no attention model).  csrc/attention_decode.hip runs
+// ONE query per (batch, head) and is pure VALU by design; a prefill (csrc/attention.hip) attends
+// only within the new tokens.  This file is the piece between them: query t of batch b, whose k / v
+// row was just appended at pos[b] + t, sees the cache rows
+//
+//     j < L(b, t) = clamp(pos[b] + t + 1, 1, cap)        (64-bit arithmetic, as decode_len)
+//
+// which is what continuing a conversation, chunked prefill and scoring several candidate tokens in
+// one pass (speculative decoding) need.  With 16 queries there is work for v_mfma_f32_16x16x32_bf16.
+//
+//   attn_extend_split_k  one wave (one workgroup) per (batch, head, tile of 16 queries, key split).
+//                      Swapped orientation as csrc/attention.hip: Sᵀ[key][q] = K·Qᵀ puts ONE query
+//                      on a lane (fr = lane & 15), so the online softmax (log2 domain, bare exp2)
+//                      is per-lane scalars, and the accumulator pair is the B operand of
+//                      Oᵀ[d][q] += Vᵀ·Pᵀ.  Keys run in tiles of 64: the K operand rows are read
+//                      straight from global memory (a lane's 16 B of a key row IS its A fragment;
+//                      a one-wave workgroup has nobody to share a staged tile with), V goes
+//                      through a swizzled LDS tile (direct global->LDS loads) for the transposed
+//                      read.  Both are double buffered: the loads of tile i + 1 are issued before
+//                      tile i's products (the compiler drains them ahead of tile i's first LDS
+//                      read, so they overlap Sᵀ and the softmax, not P·V: profiles/extend).
+//                      With one split the wave normalises and writes bf16 itself; otherwise it
+//                      writes a partial: un-normalised fp32 o[16][64], running max and sum per row.
+//   attn_extend_merge_k  one wave per (batch, query, head), lane = output dim: merges the split
+//                      partials in split order, divides by the sum, writes bf16.  No atomics:
+//                      deterministic, every output element written exactly once.
+//
+// pos is read on the device; the grid and the workspace are functions of (B, H, T, cap) only: no
+// host sync, a capture is safe and a replay follows in-place changes of pos.  The last query tile
+// is padded (pad queries take zeros for q and the last real query's limit; they are never stored).
+//
+// Key splits.  hi = the largest L of the tile's queries, cut to the split's end.  A split that
+// starts at or past hi writes "empty" (m = -inf, l = 0 for its 16 rows) and exits: a
+// workgroup-uniform decision.  Inside a live split a row may see no key (L(b, t) <= the split's
+// start): visibility is a prefix of the split, so such a row sees nothing in ANY of its tiles, keeps
+// m = -inf, l = 0, and the merge skips it without reading its o.  Split 0 holds key 0, which every
+// row sees: it is never empty for any row.
+//
+// What may enter arithmetic.  Cache rows at or past clamp(pos[b] + T, 1, cap) NEVER do: rows at or
+// past hi (<= that bound) are not loaded -- the K fragment is the constant zero and its row index is
+// replaced by the split's first row before an address is formed, the V rows are staged from a zero
+// row -- so the never-written part of a torch.empty cache, NaN / Inf bit patterns included, cannot
+// reach the output (0 * NaN in the P·V MFMA would be NaN: masking after a load is not enough).
+// Rows between a query's own limit L(b, t) and hi are the rows this call's tokens just appended
+// for later queries of the same 16-query tile: real finite data.  Their scores are masked to -inf,
+// their probability is an exact 0, and that 0 IS multiplied with their v in the MFMA.
+#include "common.h"
+#include "mfma_tile.h"
+#include "tbamd.h"
+
+namespace tbamd {
+namespace {
+
+constexpr float kLog2e = 1.4426950408889634f;
+constexpr int kQT = 16;  // queries per wave
+
+// s_waitcnt vmcnt(0) (gfx9 encoding: expcnt and lgkmcnt left at their maxima)
+__device__ __forceinline__ void wait_loads() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+
+__device__ __forceinline__ int extend_len(const int* pos, int b, int t, int cap) {
+  const int64_t l = (int64_t)pos[b] + t + 1;
+  return (int)(l < 1 ? 1 : (l > cap ? cap : l));
+}
+
+// A fragments of key rows k0 .. k0 + 63: lane holds K[k0 + 16 mt + fr][32 ks + 8 fg .. + 7]
+__device__ __forceinline__ void load_k(bf16x8_t (&kf)[4][2], const uint16_t* kb, int64_t rs, int k0, int start, int hi,
+                                       int fr, int fg) {
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) {
+    const int r = k0 + 16 * mt + fr;
+    const bool ok = r < hi;
+    const int rr = ok ? r : start;  // a hidden row never forms an address
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      kf[mt][ks] = bf16x8_t{};
+      if (ok) kf[mt][ks] = ld_frag(kb + rr * rs + 32 * ks + 8 * fg);
+    }
+  }
+}
+
+// V rows k0 .. k0 + 63 -> swizzled LDS tile by ONE wave (stage_tile's four wave slots in turn);
+// rows at or past hi come from the zero row
+__device__ __forceinline__ void stage_v(uint4* tile, const uint16_t* vb, int64_t rs, int k0, int hi, int lane) {
+#pragma unroll
+  for (int w = 0; w < 4; ++w) stage_tile(tile, vb, rs, k0, hi, w, lane);
+}
+
+// grid: B * H * nqt * nsplit one-wave workgroups, split fastest
+__global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
+  __shared__ __attribute__((aligned(16))) uint4 lds[2 * kTileU4];  // V, double buffered: 16 KiB
+  const int lane = threadIdx.x;
+  const int fr = lane & 15, fg = lane >> 4;
+  const int part = blockIdx.x;
+  const int sp = part % a.nsplit;
+  int r = part / a.nsplit;
+  const int qt = r % a.nqt;
+  r /= a.nqt;
+  const int h = r % a.H, b = r / a.H;
+  const int q0 = qt * kQT;
+  const int start = sp * a.split;  // host: nsplit * split < 2^31
+  // the tile's largest limit (L grows with t) cut to the split: workgroup-uniform
+  const int hi = min(extend_len(a.pos, b, min(q0 + kQT, a.T) - 1, a.cap), start + a.split);
+  float* wm = a.ws + (int64_t)a.nparts * (kQT * 64);
+  float* wl = wm + (int64_t)a.nparts * kQT;
+  if (start >= hi) {
+    if (lane < kQT) {
+      wm[(int64_t)part * kQT + lane] = -INFINITY;
+      wl[(int64_t)part * kQT + lane] = 0.f;
+    }
+    return;
+  }
+  const int qi = q0 + fr;
+  const bool qreal = qi < a.T;
+  const int lim = min(extend_len(a.pos, b, qreal ? qi : a.T - 1, a.cap), hi);  // the lane's own query
+
+  // Qᵀ as the B operand: lane holds Q[q0 + fr][32 ks + 8 fg .. + 7]
+  bf16x8_t qf[2];
+  {
+    const uint16_t* qp = a.q + b * a.sq[0] + (qreal ? qi : 0) * a.sq[1] + h * a.sq[2] + 8 * fg;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) qf[ks] = qreal ? ld_frag(qp + 32 * ks) : bf16x8_t{};
+  }
+  const float c = a.scale * kLog2e;
+  const uint16_t* kb = a.k + b * a.sk[0] + h * a.sk[1];
+  const uint16_t* vb = a.v + b * a.sv[0] + h * a.sv[1];
+
+  f32x4_t acc[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) acc[dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.f;
+
+  bf16x8_t kn[4][2];
+  load_k(kn, kb, a.sk[2], start, start, hi, fr, fg);
+  stage_v(lds, vb, a.sv[2], start, hi, lane);
+  int buf = 0;
+  for (int k0 = start; k0 < hi; k0 += kTile, buf ^= 1) {
+    wait_loads();
+    __syncthreads();  // tile k0 landed (registers and LDS); the other buffer's reads are done
+    bf16x8_t kf[4][2];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) kf[mt][ks] = kn[mt][ks];
+    if (k0 + kTile < hi) {
+      load_k(kn, kb, a.sk[2], k0 + kTile, start, hi, fr, fg);
+      stage_v(lds + (buf ^ 1) * kTileU4, vb, a.sv[2], k0 + kTile, hi, lane);
+    }
+    const uint4* Vt = lds + buf * kTileU4;
+
+    f32x4_t s[4];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      s[mt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) s[mt] = mfma(kf[mt][ks], qf[ks], s[mt]);
+    }
+    // s[mt][i]: key k0 + 16 mt + 4 fg + i, query fr.  Hidden keys -> -inf; rows at or past hi were
+    // zeros in both operands, rows in [lim, hi) real data.
+    const int key0 = k0 + 4 * fg;
+    float mx = -INFINITY;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        s[mt][i] = key0 + 16 * mt + i < lim ? s[mt][i] * c : -INFINITY;
+        mx = fmaxf(mx, s[mt][i]);
+      }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float mn = fmaxf(m, mx);
+    // a row that has seen no key yet (mn = -inf) must not form -inf - -inf
+    const float ms = mn == -INFINITY ? 0.f : mn;
+    const float alpha = __builtin_amdgcn_exp2f(m - ms);  // m = -inf: 0, and acc, l are 0 anyway
+    m = mn;
+    float ls = 0.f;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float p = __builtin_amdgcn_exp2f(s[mt][i] - ms);  // hidden: exp2(-inf) = 0 exactly
+        s[mt][i] = p;
+        ls += p;
+      }
+    l = l * alpha + ls;  // lane-partial; summed over the 4 lane groups at the end
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) acc[dt] *= alpha;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const bf16x8_t pf = pack_frag(s[2 * ks], s[2 * ks + 1]);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) acc[dt] = mfma(tr_frag(Vt, 32 * ks, dt, fr, fg), pf, acc[dt]);
+    }
+  }
+
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  // acc[dt][i] = Oᵀ[16 dt + 4 fg + i][fr]
+  if (a.nsplit == 1) {
+    if (qreal) {  // split 0 holds key 0: l > 0
+      const float inv = 1.f / l;
+      uint16_t* op = a.o + b * a.so[0] + qi * a.so[1] + h * 64 + 4 * fg;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) st4(op + 16 * dt, acc[dt], inv);
+    }
+    return;
+  }
+  float* wo = a.ws + ((int64_t)part * kQT + fr) * 64 + 4 * fg;
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt)
+    *reinterpret_cast<float4*>(wo + 16 * dt) = make_float4(acc[dt][0], acc[dt][1], acc[dt][2], acc[dt][3]);
+  if (fg == 0) {
+    wm[(int64_t)part * kQT + fr] = m;
+    wl[(int64_t)part * kQT + fr] = l;
+  }
+}
+
+// grid: B * T * H one-wave workgroups (head fastest); lane = output dim
+__global__ __launch_bounds__(64) void attn_extend_merge_k(AttnExtendArgs a) {
+  const int d = threadIdx.x;
+  int r = blockIdx.x;
+  const int h = r % a.H;
+  r /= a.H;
+  const int t = r % a.T, b = r / a.T;
+  const int64_t part0 = (((int64_t)b * a.H + h) * a.nqt + t / kQT) * a.nsplit;
+  const int row = t % kQT;
+  const float* wo = a.ws + (part0 * kQT + row) * 64 + d;
+  const float* wm = a.ws + (int64_t)a.nparts * (kQT * 64) + part0 * kQT + row;
+  const float* wl = wm + (int64_t)a.nparts * kQT;
+  float M = -INFINITY;
+  for (int s = 0; s < a.nsplit; ++s) M = fmaxf(M, wm[s * kQT]);  // split 0 is never empty: finite
+  float o = 0.f, L = 0.f;
+  for (int s = 0; s < a.nsplit; ++s) {
+    const float ms = wm[s * kQT];
+    if (ms == -INFINITY) continue;  // empty split or a row that saw nothing: its o is never read
+    const float f = __builtin_amdgcn_exp2f(ms - M);
+    L = fmaf(f, wl[s * kQT], L);
+    o = fmaf(f, wo[(int64_t)s * (kQT * 64)], o);
+  }
+  a.o[b * a.so[0] + t * a.so[1] + h * 64 + d] = f2bf(o / L);
+}
+
+}  // namespace
+
+// The default policy, a function of (B, H, T, cap) only.  tiles = B * H * ceil(T / 16) one-wave
+// workgroups.  With 256 tiles or more (one per CU) the keys are not split, so a long continuation
+// needs no workspace of the order of T * cap.  Below that the keys are split 128 to a workgroup, and
+// the split size doubles while tiles * nsplit exceeds 512: past two waves per CU more splits add
+// partials and merge steps and no parallelism.  Measured (profiles/extend/README.md; us per call,
+// median of 5 interleaved rounds, spread < 2 %; T = 8, H = 12, cap = len, pos = len - T):
+//
+//     B*H  len    tiles   64     128    256    512    one split
+//     12   512    12      9.2    8.2    9.3    11.3   11.2
+//     12   1024   12      12.7   10.1   10.2   14.0   20.2
+//     96   512    96      11.6   9.8    10.3   11.7   11.6
+//     96   1024   96      18.7   13.8   12.3   14.7   20.5
+//
+// T = 2 .. 16 differ from these by a few per cent (one tile whatever T is).  128 is the fastest or
+// within 2 % of it in three rows; in the fourth (768 waves at 128) 256 wins by 8 .. 15 %, which is
+// the doubling rule.  A single wave walks the keys at about 1.2 us per 64-key tile, which is what
+// one split costs at len 1024.
+static int g_extend_split = 0;  // 0: the default policy; otherwise a forced split size
+constexpr int kExtendSplit = 128;
+constexpr int kExtendFullTiles = 256;
+constexpr int kExtendMaxWaves = 512;
+
+int attn_extend_set_split(int n) {
+  const int old = g_extend_split;
+  if (n == 0 || (n >= 8 && n % 8 == 0)) g_extend_split = n;
+  return old;
+}
+
+static int extend_split_size(int B, int H, int T, int cap) {
+  if (g_extend_split) return g_extend_split < cap ? g_extend_split : cap;
+  const int64_t tiles = (int64_t)B * H * ((T + kQT - 1) / kQT);
+  if (tiles >= kExtendFullTiles) return cap;
+  int s = kExtendSplit;
+  while (s < cap && tiles * ((cap + s - 1) / s) > kExtendMaxWaves) s *= 2;  // s <= 2 * cap: no overflow
+  return s < cap ? s : cap;
+}
+
+int attn_extend_splits(int B, int H, int T, int cap) {
+  const int s = extend_split_size(B, H, T, cap);
+  return (cap + s - 1) / s;
+}
+
+int64_t attn_extend_workspace(int B, int H, int T, int cap) {
+  const int ns = attn_extend_splits(B, H, T, cap);
+  if (ns == 1) return 0;
+  return (int64_t)B * H * ((T + kQT - 1) / kQT) * ns * (kQT * 66);
+}
+
+void attn_extend(const AttnExtendArgs& a_, hipStream_t st) {
+  AttnExtendArgs a = a_;
+  if (a.B == 0 || a.T == 0) return;
+  a.split = extend_split_size(a.B, a.H, a.T, a.cap);
+  a.nsplit = (a.cap + a.split - 1) / a.split;
+  a.nqt = (a.T + kQT - 1) / kQT;
+  a.nparts = a.B * a.H * a.nqt * a.nsplit;
+  hipLaunchKernelGGL(attn_extend_split_k, dim3(a.nparts), dim3(64), 0, st, a);
+  if (a.nsplit > 1) hipLaunchKernelGGL(attn_extend_merge_k, dim3(a.B * a.T * a.H), dim3(64), 0, st, a);
+}
+
+}  // namespace tbamd

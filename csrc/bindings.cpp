@@ -2269,6 +2269,60 @@ Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const 
   return o;
 }
 
+// q: [B, T, H, 64] (any batch / token / head strides; the q part of a packed [B, T, 3*H*64] is such
+// a view) -> o [B, T, H*64].  Query t sees cache rows j < clamp(positions[b] + t + 1, 1, cap).
+// workspace (optional, tests): f32, at least attn_extend_workspace floats; by default it comes
+// from the caching allocator (none at all with a single key split).
+Tensor attn_extend(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& positions,
+                   double scale, const c10::optional<Tensor>& workspace) {
+  const at::DeviceGuard guard(k_cache.device());
+  TORCH_CHECK(k_cache.dim() == 4, "attention extend: cache must be [B, H, cap, 64]");
+  const int64_t B = k_cache.size(0), H = k_cache.size(1), cap = k_cache.size(2);
+  check_cuda(q, "q");
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.dim() == 4 && q.size(0) == B && q.size(2) == H &&
+                  q.size(3) == 64 && q.stride(3) == 1,
+              "attention extend: q must be bf16 [B, T, H, 64] with a unit head-dim stride");
+  const int64_t T = q.size(1);
+  TORCH_CHECK(B >= 1 && H >= 1 && T >= 1 && cap >= 1 && cap < (int64_t)INT32_MAX / 2 && T < (int64_t)INT32_MAX / 2,
+              "attention extend: bad size");
+  TORCH_CHECK(q.device() == k_cache.device(), "attention extend: q must be on the device of the cache");
+  tbamd::AttnExtendArgs a{};
+  for (int i = 0; i < 3; ++i) {
+    TORCH_CHECK(q.stride(i) % 8 == 0 || q.size(i) == 1, "attention extend: q strides must be multiples of 8");
+    a.sq[i] = q.stride(i);
+  }
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0, "attention extend: q not 16-B aligned");
+  a.q = reinterpret_cast<const uint16_t*>(q.data_ptr());
+  attn_view(k_cache, "k_cache", B, H, cap, &a.k, a.sk);
+  attn_view(v_cache, "v_cache", B, H, cap, &a.v, a.sv);
+  TORCH_CHECK(v_cache.device() == k_cache.device(), "attention extend: caches on different devices");
+  a.pos = decode_lengths(positions, "positions", k_cache, B);
+  // the split kernel's grid (one workgroup per partial) and the merge kernel's (one per output row)
+  const int64_t nqt = (T + 15) / 16;
+  TORCH_CHECK(B * H * nqt * (int64_t)tbamd::attn_extend_splits((int)B, (int)H, (int)T, (int)cap) <
+                      (int64_t)INT32_MAX / (16 * 66) &&
+                  B * T * H < (int64_t)INT32_MAX / 64,
+              "attention extend: bad size");
+  const int64_t need = tbamd::attn_extend_workspace((int)B, (int)H, (int)T, (int)cap);
+  Tensor ws;
+  if (workspace.has_value() && workspace->defined()) {
+    ws = *workspace;
+    check_cuda(ws, "workspace");
+    TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() && ws.numel() >= need &&
+                    ws.device() == k_cache.device() && reinterpret_cast<uintptr_t>(ws.data_ptr()) % 16 == 0,
+                "attention extend: workspace must be contiguous, 16-B aligned f32 with at least ", need, " elements");
+  } else if (need > 0) {
+    ws = at::empty({need}, k_cache.options().dtype(at::kFloat));
+  }
+  Tensor o = at::empty({B, T, H * 64}, k_cache.options());
+  a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
+  a.so[0] = T * H * 64, a.so[1] = H * 64;
+  a.ws = need > 0 ? ws.data_ptr<float>() : nullptr;
+  a.B = (int)B, a.T = (int)T, a.H = (int)H, a.cap = (int)cap, a.scale = (float)scale;
+  tbamd::attn_extend(a, cur_stream());
+  return o;
+}
+
 // ------------------------------------------------------------ Gram matrix
 // f: [B, C, H, W] bf16 channels_last (NHWC memory) -> [B, C, C] f32 = F_b^T F_b * scale
 // x: bf16 [N, C, H, W] channels_last -> col [N*P*Q, KP] (KP = RSC rounded up to 8)
@@ -2708,6 +2762,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_set_chunk", [](int64_t n) {
     TORCH_CHECK(n < 0 || (n >= 8 && n % 8 == 0 && n <= (1 << 20)), "attn_decode_set_chunk: a multiple of 8, >= 8");
     return (int64_t)tbamd::attn_decode_set_chunk((int)n);
+  });
+  m.def("attn_extend", &attn_extend, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("positions"),
+        py::arg("scale"), py::arg("workspace") = py::none());
+  m.def("attn_extend_splits", [](int64_t B, int64_t H, int64_t T, int64_t cap) {
+    return (int64_t)tbamd::attn_extend_splits((int)B, (int)H, (int)T, (int)cap);
+  });
+  m.def("attn_extend_workspace", [](int64_t B, int64_t H, int64_t T, int64_t cap) {
+    return tbamd::attn_extend_workspace((int)B, (int)H, (int)T, (int)cap);
+  });
+  m.def("attn_extend_set_split", [](int64_t n) {
+    TORCH_CHECK(n <= 0 || (n >= 8 && n % 8 == 0 && n <= (1 << 20)),
+                "attn_extend_set_split: 0 (the default policy) or a multiple of 8, >= 8");
+    return (int64_t)tbamd::attn_extend_set_split((int)n);
   });
   m.def("gram_forward", &gram_forward);
   m.def("gram_sym", &gram_sym);

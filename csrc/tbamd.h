@@ -305,6 +305,35 @@ int attn_decode_chunks(int cap);
 int64_t attn_decode_workspace(int B, int H, int cap);  // floats
 void attn_decode(const AttnDecodeArgs& a, hipStream_t st);
 
+// ---- KV-cache extend attention (csrc/attention_extend.hip; head dim 64, bf16) ----
+// T new queries per (batch, head) against the cache AFTER their own k / v rows were appended at
+// pos[b] + t: query t sees rows j < L(b, t) = clamp(pos[b] + t + 1, 1, cap) (64-bit arithmetic).
+// pos: [B] int32 in device memory, read by the kernels.  Rows at or past clamp(pos[b] + T, 1, cap)
+// never enter arithmetic; rows between a query's own limit and that bound (this call's tokens) may
+// be multiplied by an exact-zero probability.  q: strides in elements over (batch, token, head),
+// head-dim stride 1.  o: [B][T][H*64], strides over (batch, token).  ws: attn_extend_workspace(B, H,
+// T, cap) floats (0 with a single split: the first kernel then writes o itself); split / nsplit /
+// nqt / nparts are filled in by attn_extend.
+struct AttnExtendArgs {
+  const uint16_t* q;
+  const uint16_t* k;
+  const uint16_t* v;
+  uint16_t* o;
+  const int* pos;
+  float* ws;
+  int B, T, H, cap;
+  float scale;
+  int64_t sq[3], sk[3], sv[3], so[2];
+  int split, nsplit, nqt, nparts;
+};
+// keys per split: 0 = the default policy (split only when B * H * ceil(T / 16) cannot occupy the
+// chip), otherwise a forced size (a multiple of 8, >= 8; at or above cap: one split); n < 0 only
+// reads it.  Returns the previous value.
+int attn_extend_set_split(int n);
+int attn_extend_splits(int B, int H, int T, int cap);
+int64_t attn_extend_workspace(int B, int H, int T, int cap);  // floats
+void attn_extend(const AttnExtendArgs& a, hipStream_t st);
+
 // ---- Gram matrix (NHWC bf16 features, C % 64 == 0) ----
 void gram_sym(const float* dg, void* sym, int B, int C, float scale, hipStream_t st);
 void im2col_nhwc(const void* x, void* col, int N, int H, int W, int C, int R, int S, int P, int Q, int stride,

@@ -19,7 +19,10 @@ layer, ``prefill`` runs the prompt once and fills it, ``decode_step`` runs ONE n
 against it (the split-KV decode kernels of csrc/attention_decode.hip) and ``generate`` ties the two to
 greedy / temperature / top-k sampling.  Nothing in a decode step reads a device value on the host --
 positions and lengths live in device memory -- so a step can be captured into a graph and replayed
-(``generate(graph=True)``).
+(``generate(graph=True)``).  ``extend`` runs T >= 1 new tokens per sequence on top of what a cache holds
+(csrc/attention_extend.hip): ``generate(cache=...)`` continues a conversation with it, and
+``generate(draft=...)`` is greedy speculative decoding, the target scoring a draft's proposals in one
+``extend`` per round.
 """
 from __future__ import annotations
 
@@ -174,9 +177,90 @@ class TransformerLM(nn.Module):
             cache.positions.add_(1)
             return logits
 
+    def extend(self, tokens: Tensor, cache: KVCache, lengths: Optional[Tensor] = None, *,
+               last_only: bool = False) -> Tensor:
+        """``T`` new tokens per sequence, ``tokens`` ``[B, T]``, on top of what ``cache`` holds: token ``t``
+        of sequence ``b`` runs at position ``cache.positions[b] + t`` and attends to the cache rows up to
+        and including its own (the extend kernel of csrc/attention_extend.hip) -> logits ``[B, T, vocab]``.
+
+        ``lengths`` (int32 ``[B]``): the valid tokens of each right-padded row, clamped into ``[1, T]``.
+        ``cache.positions`` advance in place by them (by ``T`` without ``lengths``); the k / v rows of the
+        pad tokens land past the new position and are overwritten as the sequence grows, the rule of the
+        ragged prefill.  ``last_only=True`` returns ``[B, vocab]``, the logits of token
+        ``clamp(lengths[b], 1, T) - 1`` alone (gathered before the final LayerNorm and the head).
+        No device value is read on the host."""
+        B, T = tokens.shape
+        if T < 1:
+            raise ValueError("extend needs at least one token per sequence")
+        if T > cache.capacity:
+            raise ValueError(f"{T} new tokens exceed the cache capacity {cache.capacity}")
+        with torch.no_grad():
+            at = cache.positions.to(torch.int64)[:, None] + torch.arange(T, device=tokens.device)[None, :]
+            x = self.tok(tokens) + self.pos[0][at.clamp(0, self.max_len - 1)].to(self.tok.weight.dtype)
+            pending = None
+            for blk, kv in zip(self.blocks, cache.layers):
+                x, pending = blk(x, pending, cache=kv, positions=cache.positions, extend=True)
+            adv = None if lengths is None else lengths.clamp(1, T).to(torch.int32)
+            if last_only:
+                if adv is None:
+                    x, pending = x[:, T - 1:], pending[:, T - 1:]
+                else:
+                    last = (adv.to(torch.int64) - 1)[:, None, None].expand(B, 1, x.shape[-1])
+                    x, pending = x.gather(1, last), pending.gather(1, last)
+                h, _ = self.norm(x.contiguous(), pending.contiguous())
+                logits = self.head(h[:, 0])
+            else:
+                h, _ = self.norm(x, pending)
+                logits = self.head(h)
+            cache.positions.add_(T if adv is None else adv)
+            return logits
+
+    def _speculative(self, tokens: Tensor, max_new_tokens: int, lengths: Optional[Tensor], eos: Optional[int],
+                     draft: "TransformerLM", gamma: int) -> Tuple[Tensor, Tensor]:
+        """Greedy speculative decoding (``generate(draft=...)``)."""
+        B, N = tokens.shape
+        dev = tokens.device
+        cap = N + max_new_tokens + gamma
+        tc, dc = KVCache(self, B, capacity=cap), KVCache(draft, B, capacity=cap)
+        logits, _ = self.prefill(tokens, lengths, tc)
+        draft.prefill(tokens, lengths, dc)
+        # invariant at the top of a round: both caches hold the history up to, but not including, `cur`
+        cur = logits.argmax(dim=-1)
+        out = torch.zeros(B, max_new_tokens + gamma + 1, dtype=torch.int64, device=dev)
+        out[:, 0] = cur
+        slot = torch.ones(B, dtype=torch.int64, device=dev)  # tokens emitted so far
+        steps = torch.arange(gamma + 1, device=dev)[None, :]
+        while int(slot.min()) < max_new_tokens:  # the one host read of a round
+            base = tc.positions.clone()
+            block = [cur]
+            for _ in range(gamma):
+                block.append(draft.decode_step(block[-1], dc).argmax(dim=-1))
+            draft.decode_step(block[-1], dc)  # the last proposal's k / v: the caches stay in step
+            block = torch.stack(block, dim=1)  # [B, gamma + 1]: cur, d_1 .. d_gamma
+            tgt = self.extend(block, tc).argmax(dim=-1)  # tgt[:, i]: the target's token after block[:, :i + 1]
+            agree = (block[:, 1:] == tgt[:, :-1]).to(torch.int64).cumprod(dim=1).sum(dim=1)
+            n_emit = torch.minimum(agree + 1, (max_new_tokens - slot).clamp_min(0))  # 0: the sequence is done
+            idx = slot[:, None] + steps
+            out.scatter_(1, idx, torch.where(steps < n_emit[:, None], tgt, out.gather(1, idx)))
+            cur = torch.where(n_emit > 0, tgt.gather(1, (n_emit - 1).clamp_min(0)[:, None])[:, 0], cur)
+            slot = slot + n_emit
+            # rejected rows are just rows past the position
+            tc.positions.copy_(base + n_emit.to(torch.int32))
+            dc.positions.copy_(tc.positions)
+        out = out[:, :max_new_tokens]
+        out_lengths = torch.full((B,), max_new_tokens, dtype=torch.int64, device=dev)
+        if eos is not None:
+            hit = out == eos
+            first = hit.to(torch.int64).argmax(dim=1) + 1
+            out_lengths = torch.where(hit.any(dim=1), first, out_lengths)
+            past = torch.arange(max_new_tokens, device=dev)[None, :] >= out_lengths[:, None]
+            out = torch.where(past, torch.full_like(out, eos), out)
+        return out.contiguous(), out_lengths
+
     def generate(self, tokens: Tensor, max_new_tokens: int, lengths: Optional[Tensor] = None, *,
                  temperature: float = 0.0, top_k: Optional[int] = None, eos: Optional[int] = None,
-                 generator=None, graph: bool = False) -> Tuple[Tensor, Tensor]:
+                 generator=None, graph: bool = False, cache: Optional[KVCache] = None,
+                 draft: Optional["TransformerLM"] = None, draft_tokens: int = 4) -> Tuple[Tensor, Tensor]:
         """Continue the prompts ``tokens`` ``[B, N]`` (``lengths``: valid tokens of each, right-padded) by
         ``max_new_tokens`` tokens -> ``(out [B, max_new_tokens], out_lengths [B])``.
 
@@ -186,7 +270,25 @@ class TransformerLM(nn.Module):
         to and including the first ``eos`` (the mask lives on the device: no per-step sync, no early exit).
         ``graph=True`` (CUDA): after the prefill and one eager decode step, ONE decode step plus the
         sampling is captured into a graph and replayed for the remaining tokens; greedy results equal
-        ``graph=False`` bit for bit."""
+        ``graph=False`` bit for bit.
+
+        ``cache`` (a :class:`KVCache` of batch ``B``): continue what it holds.  ``tokens`` are NEW tokens
+        appended at ``cache.positions`` through ``extend(last_only=True)`` instead of a prefill; decoding
+        then proceeds as above, ``graph=True`` included.  ``cache.positions.max()`` is read on the host
+        once at entry (outside any capture): ``max + N + max_new_tokens`` must not exceed
+        ``min(cache.capacity, max_len)``.  On return ``cache.positions[b] = start[b] + prompt_len[b] +
+        out_lengths[b] - 1`` (set on the device): the cache holds the prompt and every emitted token BUT
+        THE LAST, so the caller begins the next turn's ``tokens`` with ``out[b, out_lengths[b] - 1]``.
+
+        ``draft`` (another :class:`TransformerLM` over the same vocabulary): greedy speculative decoding.
+        Per round the draft proposes ``draft_tokens`` tokens with its own cache and ``decode_step``, the
+        target scores ``[cur, d_1 .. d_γ]`` in ONE ``extend``, and the longest prefix on which the two
+        argmaxes agree is accepted plus the target's own next token: 1 to γ + 1 tokens per sequence and
+        round, equal to what greedy ``generate`` without a draft emits wherever the target's argmax is
+        unambiguous.  Greedy only, eager only, own caches only (``temperature != 0``, ``top_k``,
+        ``graph=True`` and ``cache`` raise), and ``N + max_new_tokens + draft_tokens`` must fit both
+        models' ``max_len``.  Termination reads ONE device value (``slot.min()``) per round; ``eos`` is
+        applied after the loop."""
         B, N = tokens.shape
         max_new_tokens = int(max_new_tokens)
         if max_new_tokens < 1:
@@ -195,10 +297,36 @@ class TransformerLM(nn.Module):
             raise ValueError(f"prompt {N} + max_new_tokens {max_new_tokens} exceeds max_len {self.max_len}")
         if graph and not tokens.is_cuda:
             raise ValueError("graph=True needs CUDA tensors")
+        if draft is not None:
+            gamma = int(draft_tokens)
+            if temperature != 0 or top_k is not None or graph or cache is not None:
+                raise ValueError("speculative decoding is greedy and eager with its own caches: no temperature, "
+                                 "top_k, graph=True or cache")
+            if gamma < 1:
+                raise ValueError("draft_tokens must be at least 1")
+            if draft.tok.num_embeddings != self.tok.num_embeddings:
+                raise ValueError("the draft model must share the target's vocabulary")
+            if N + max_new_tokens + gamma > min(self.max_len, draft.max_len):
+                raise ValueError(f"prompt {N} + max_new_tokens {max_new_tokens} + draft_tokens {gamma} exceeds "
+                                 f"max_len {min(self.max_len, draft.max_len)}")
+            with torch.no_grad():
+                return self._speculative(tokens, max_new_tokens, lengths, eos, draft, gamma)
+        start = None
+        if cache is not None:
+            if cache.positions.shape[0] != B:
+                raise ValueError(f"the cache holds {cache.positions.shape[0]} sequences, tokens {B}")
+            held = int(cache.positions.max())
+            room = min(cache.capacity, self.max_len)
+            if held + N + max_new_tokens > room:
+                raise ValueError(f"cache position {held} + prompt {N} + max_new_tokens {max_new_tokens} exceeds {room}")
         with torch.no_grad():
             dev = tokens.device
-            cache = KVCache(self, B, capacity=N + max_new_tokens)
-            logits, _ = self.prefill(tokens, lengths, cache)
+            if cache is None:
+                cache = KVCache(self, B, capacity=N + max_new_tokens)
+                logits, _ = self.prefill(tokens, lengths, cache)
+            else:
+                logits = self.extend(tokens, cache, lengths, last_only=True)
+                start = cache.positions.clone()  # start[b] + prompt_len[b]
             out = torch.zeros(B, max_new_tokens, dtype=torch.int64, device=dev)
             out_lengths = torch.zeros(B, dtype=torch.int64, device=dev)
             finished = torch.zeros(B, dtype=torch.bool, device=dev)
@@ -234,6 +362,8 @@ class TransformerLM(nn.Module):
                     g.replay()
             for _ in range(eager):
                 step()
+            if start is not None:  # a caller's cache: keep every emitted token but the last
+                cache.positions.copy_(start + (out_lengths - 1).to(torch.int32))
             return out, out_lengths
 
 

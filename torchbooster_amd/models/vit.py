@@ -19,7 +19,8 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor, nn
 
-from torchbooster_amd.ops.attention import attention_decode_packed, attention_packed, kv_cache_append
+from torchbooster_amd.ops.attention import (attention_decode_packed, attention_extend_packed, attention_packed,
+                                            kv_cache_append)
 from torchbooster_amd.ops.conv import Conv2d
 
 from torchbooster_amd.ops.norm import LayerNorm
@@ -36,7 +37,10 @@ class Attention(nn.Module):
     ``[B, H, cap, hd]``, and ``positions`` (int32 [B], the row each sequence writes next), an ``x`` of
     ``[B, 1, dim]`` is one decode step -- its k / v are appended at ``positions`` and the query attends to
     the cache rows ``j <= positions[b]`` -- and an ``x`` of ``[B, N > 1, dim]`` is a prefill: the masked
-    self-attention as without a cache, plus one append of the same k / v at ``positions``."""
+    self-attention as without a cache, plus one append of the same k / v at ``positions``.  With
+    ``extend=True`` an ``x`` of any ``[B, T >= 1, dim]`` is T new tokens on top of what the cache holds:
+    their k / v are appended at ``positions[b] + t`` and query ``t`` attends to the cache rows
+    ``j <= positions[b] + t`` (``attention_extend_packed``; ``key_lengths`` is not used)."""
 
     def __init__(self, dim: int, heads: int, causal: bool = False) -> None:
         super().__init__()
@@ -47,7 +51,7 @@ class Attention(nn.Module):
         self.proj = Linear(dim, dim)
 
     def forward(self, x: Tensor, key_lengths: Optional[Tensor] = None, *, cache=None,
-                positions: Optional[Tensor] = None) -> Tensor:
+                positions: Optional[Tensor] = None, extend: bool = False) -> Tensor:
         scale = 1.0 / math.sqrt(self.hd)
         if cache is None:
             return self.proj(attention_packed(self.qkv(x), self.heads, scale, causal=self.causal,
@@ -58,6 +62,8 @@ class Attention(nn.Module):
             raise ValueError("a KV cache needs positions")
         k_cache, v_cache = cache
         qkv = self.qkv(x)
+        if extend:
+            return self.proj(attention_extend_packed(qkv, self.heads, k_cache, v_cache, positions, scale))
         if x.shape[1] == 1:
             return self.proj(attention_decode_packed(qkv, self.heads, k_cache, v_cache, positions, scale))
         kv_cache_append(k_cache, v_cache, qkv, self.heads, positions)
@@ -86,16 +92,16 @@ class Block(nn.Module):
         self.mlp = MLP(dim, int(dim * mlp_ratio))
 
     def forward(self, x: Tensor, pending: Optional[Tensor] = None, key_lengths: Optional[Tensor] = None, *,
-                cache=None, positions: Optional[Tensor] = None):
+                cache=None, positions: Optional[Tensor] = None, extend: bool = False):
         """``x``: residual stream; ``pending``: a sub-block output not yet added
         to it.  Returns (stream, pending) so adds fuse into the next LayerNorm.
         ``key_lengths``: per-batch key lengths for the attention (None: every key).
-        ``cache`` / ``positions``: this layer's KV cache, passed to :class:`Attention`."""
+        ``cache`` / ``positions`` / ``extend``: this layer's KV cache, passed to :class:`Attention`."""
         if pending is None:
             h = self.ln1(x)
         else:
             h, x = self.ln1(x, pending)
-        a = self.attn(h, key_lengths, cache=cache, positions=positions)
+        a = self.attn(h, key_lengths, cache=cache, positions=positions, extend=extend)
         h, x = self.ln2(x, a)
         return x, self.mlp(h)
 

@@ -49,6 +49,27 @@ of an uninitialised cache, the pad rows of a ragged prefill) cannot reach the ou
 (CUDA, bf16, D = 64) splits the keys over workgroups (``attn_decode_set_chunk`` keys each, grid fixed
 from ``cap``) and merges the partials in a second launch in fixed order: deterministic, no atomics.
 These functions do not build an autograd graph and raise if an input requires grad in grad mode.
+
+Extend (forward only; csrc/attention_extend.hip): ``T >= 1`` new tokens per sequence against a cache
+that already holds tokens -- continuing a conversation, chunked prefill, scoring several candidate
+tokens in one pass.
+
+* :func:`attention_extend` takes ``q`` ``[B, T, H, D]`` (any view with a contiguous last dim) whose
+  k / v rows are already in the caches at rows ``positions[b] + t``: query ``t`` of batch ``b`` sees
+  the cache rows ``j < L(b, t) = clamp(positions[b] + t + 1, 1, cap)`` -> ``[B, T, H, D]``.  A bad
+  position never moves an address and no row is ever fully masked.
+* :func:`attention_extend_packed` takes the packed ``[B, T, 3*H*D]`` projection of the new tokens:
+  :func:`kv_cache_append`, then extend -> ``[B, T, H*D]``.  ``T == 1`` IS
+  :func:`attention_decode_packed` (the same calls, bit-equal results).
+
+What may enter arithmetic: cache rows at or past ``clamp(positions[b] + T, 1, cap)`` NEVER do (not
+loaded by the native kernel, selected away before the multiply on the PyTorch path), which covers the
+never-written part of a ``torch.empty`` cache.  Rows between a query's own limit ``L(b, t)`` and that
+bound are the rows this call's tokens just appended: real finite data, which MAY be multiplied by an
+exact-zero probability.  The native path (CUDA, bf16, D = 64) runs 16 queries per wave on the MFMA and
+splits the keys over workgroups only when ``B * H * ceil(T / 16)`` cannot occupy the chip
+(``attn_extend_set_split`` forces a split size, ``attn_extend_splits(B, H, T, cap)`` tells the count);
+the partials are merged in fixed order, and ``positions`` are read on the device as above.
 """
 from __future__ import annotations
 
@@ -63,7 +84,7 @@ from torch.autograd.function import once_differentiable
 from torchbooster_amd.ops._ext import native, use_native
 
 __all__ = ["attention", "attention_packed", "attention_ref", "native_supported", "kv_cache_append",
-           "attention_decode", "attention_decode_packed"]
+           "attention_decode", "attention_decode_packed", "attention_extend", "attention_extend_packed"]
 
 
 def _visible(N: int, device, causal: bool, key_lengths: Optional[Tensor]) -> Optional[Tensor]:
@@ -296,3 +317,71 @@ def attention_decode_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: T
         _append_ref(k_cache, v_cache, qkv, heads, positions)
         q = qkv.reshape(B, 3, heads, D)[:, 0]
         return _decode_ref(q, k_cache, v_cache, positions.to(torch.int64) + 1, scale).reshape(B, 1, heads * D)
+
+
+def _extend_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor, scale: float) -> Tensor:
+    """The PyTorch path of :func:`attention_extend` (softmax in fp32, or fp64 for fp64 inputs), sync-free.
+    ``q`` ``[B, T, H, D]`` -> ``[B, T, H, D]``.  Scores are masked to -inf by ``L(b, t)``; v is zeroed at
+    rows ``>= clamp(positions[b] + T, 1, cap)`` before the product because 0 * NaN is NaN.  Rows between
+    a query's limit and that bound (this call's tokens) are multiplied by an exact-zero probability."""
+    B, T, H, D = q.shape
+    cap = k_cache.shape[2]
+    pos = positions.to(torch.int64)
+    lim = (pos[:, None] + torch.arange(1, T + 1, device=q.device)[None, :]).clamp(1, cap)  # L(b, t): [B, T]
+    j = torch.arange(cap, device=q.device)
+    vis = (j[None, None, :] < lim[:, :, None])[:, None]  # [B, 1, T, cap]
+    held = (j[None, :] < (pos + T).clamp(1, cap)[:, None])[:, None, :, None]  # [B, 1, cap, 1]
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    s = torch.einsum("bthd,bhjd->bhtj", q.to(ct), k_cache.to(ct)) * scale
+    p = torch.softmax(s.masked_fill(~vis, float("-inf")), dim=-1)
+    v = torch.where(held, v_cache, torch.zeros((), dtype=v_cache.dtype, device=q.device)).to(ct)
+    return torch.einsum("bhtj,bhjd->bthd", p, v).to(q.dtype)
+
+
+def attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
+                     scale: Optional[float] = None) -> Tensor:
+    """``T`` queries per (batch, head): ``q`` ``[B, T, H, D]`` (any view with a contiguous last dim), whose
+    k / v rows are already in ``k_cache`` / ``v_cache`` ``[B, H, cap, D]`` at rows ``positions[b] + t``.
+    Query ``t`` sees rows ``j < clamp(positions[b] + t + 1, 1, cap)`` -> ``[B, T, H, D]``.
+
+    Cache rows at or past ``clamp(positions[b] + T, 1, cap)`` never enter arithmetic; rows between a
+    query's own limit and that bound are this call's tokens (real finite data) and may be multiplied by
+    an exact-zero probability."""
+    _forward_only(q, k_cache, v_cache)
+    if q.dim() != 4 or q.shape[1] < 1:
+        raise RuntimeError("q must be [B, T >= 1, H, D]")
+    B, T, H, D = q.shape
+    scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
+    with torch.no_grad():
+        if _decode_native(q, k_cache, v_cache):
+            q = q if _rows_ok(q) else q.contiguous()
+            return native().attn_extend(q, k_cache, v_cache, positions, scale).view(B, T, H, D)
+        _check_cache(k_cache, v_cache, B, H, D, positions, "positions")
+        return _extend_ref(q, k_cache, v_cache, positions, scale)
+
+
+def attention_extend_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
+                            scale: Optional[float] = None) -> Tensor:
+    """``T`` new tokens on their packed ``[B, T, 3*H*D]`` projection: append their k / v at rows
+    ``positions[b] + t`` (rows outside ``[0, cap)`` are dropped), then query ``t`` attends to rows
+    ``j < clamp(positions[b] + t + 1, 1, cap)`` -> ``[B, T, H*D]``.  ``T == 1`` is
+    :func:`attention_decode_packed`.  What may enter arithmetic: see :func:`attention_extend`."""
+    if qkv.dim() != 3 or qkv.shape[1] < 1 or qkv.shape[2] % (3 * heads):
+        raise RuntimeError("qkv must be [B, T >= 1, 3*H*D]")
+    B, T, E3 = qkv.shape
+    if T == 1:
+        return attention_decode_packed(qkv, heads, k_cache, v_cache, positions, scale)
+    _forward_only(qkv, k_cache, v_cache)
+    D = E3 // (3 * heads)
+    scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
+    with torch.no_grad():
+        if _decode_native(qkv, k_cache, v_cache):
+            qkv = qkv if _rows_ok(qkv) else qkv.contiguous()
+            C = native()
+            C.attn_kv_append(qkv, heads, k_cache, v_cache, positions)
+            q = qkv.view(B, T, 3, heads, D)[:, :, 0]
+            return C.attn_extend(q, k_cache, v_cache, positions, scale)
+        _check_cache(k_cache, v_cache, B, heads, D, positions, "positions")
+        _append_ref(k_cache, v_cache, qkv, heads, positions)
+        q = qkv.reshape(B, T, 3, heads, D)[:, :, 0]
+        return _extend_ref(q, k_cache, v_cache, positions, scale).reshape(B, T, heads * D)
