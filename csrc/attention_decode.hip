@@ -16,6 +16,9 @@
 //                      8 row groups are merged once at the end (xor-shuffles 8, 16, 32: a fixed
 //                      tree) and lanes 0..7 write the partial: un-normalised fp32 o[64], running max
 //                      (log2 domain) and sum.
+//   attn_decode_append_split_k  the same wave with the append folded in (attn_decode_append): the
+//                      step's own row comes from the packed qkv and is stored to the cache by the
+//                      lanes that load it; a single-chunk cache is normalised and written here too.
 //   attn_decode_merge_k  one wave per (batch, head): merges the chunk partials in chunk order, divides
 //                      by the sum and writes bf16.  No float atomics: deterministic, every output
 //                      element written exactly once.
@@ -79,8 +82,21 @@ __global__ __launch_bounds__(256) void attn_kv_append_k(AttnAppendArgs a) {
   *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
 }
 
-// grid: B * H * nchunks one-wave workgroups, chunk fastest
-__global__ __launch_bounds__(64) void attn_decode_split_k(AttnDecodeArgs a) {
+// The k / v row of this step's token for the fused append: the k and v parts of the packed qkv.
+struct AttnNewRow {
+  const uint16_t* k;
+  const uint16_t* v;
+  int64_t s;  // batch stride; the head stride is 64
+};
+
+// grid: B * H * nchunks one-wave workgroups, chunk fastest.  FUSED (attn_decode_append): row
+// p = klen[b] comes from `n` instead of the cache and the lanes that load it store it to the cache;
+// it is the last visible row (len = p + 1), so exactly one wave of a (batch, head) meets it and no
+// other wave reads it.  p outside [0, cap) equals no visible row index: nothing is stored.  With one
+// chunk the wave finishes with the merge kernel's own arithmetic (M - M, fma by exp2 of it, divide)
+// and writes bf16.
+template <bool FUSED>
+__device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, const AttnNewRow& n) {
   const int lane = threadIdx.x;
   const int g = lane >> 3, c = lane & 7;
   const int part = blockIdx.x;
@@ -105,6 +121,7 @@ __global__ __launch_bounds__(64) void attn_decode_split_k(AttnDecodeArgs a) {
   const float sc = a.scale * kLog2e;
   const uint16_t* kb = a.k + b * a.sk[0] + h * a.sk[1] + c * 8;
   const uint16_t* vb = a.v + b * a.sv[0] + h * a.sv[1] + c * 8;
+  const int64_t p = FUSED ? (int64_t)a.klen[b] : -1;
 
   float m = -INFINITY, l = 0.f, acc[8];
 #pragma unroll
@@ -120,7 +137,12 @@ __global__ __launch_bounds__(64) void attn_decode_split_k(AttnDecodeArgs a) {
       const int rr = ok[u] ? r : start;  // a hidden row never forms an address
       kr[u] = make_uint4(0, 0, 0, 0);
       vr[u] = make_uint4(0, 0, 0, 0);
-      if (ok[u]) {
+      if (FUSED && ok[u] && (int64_t)r == p) {  // 0 <= r < len <= cap: the store is inside the cache
+        kr[u] = *reinterpret_cast<const uint4*>(n.k + b * n.s + h * 64 + c * 8);
+        vr[u] = *reinterpret_cast<const uint4*>(n.v + b * n.s + h * 64 + c * 8);
+        *reinterpret_cast<uint4*>(const_cast<uint16_t*>(kb) + rr * a.sk[2]) = kr[u];
+        *reinterpret_cast<uint4*>(const_cast<uint16_t*>(vb) + rr * a.sv[2]) = vr[u];
+      } else if (ok[u]) {
         kr[u] = *reinterpret_cast<const uint4*>(kb + rr * a.sk[2]);
         vr[u] = *reinterpret_cast<const uint4*>(vb + rr * a.sv[2]);
       }
@@ -170,6 +192,17 @@ __global__ __launch_bounds__(64) void attn_decode_split_k(AttnDecodeArgs a) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[i] += __shfl_xor(acc[i], o, 64);
   }
+  if (FUSED && a.nchunks == 1) {  // what attn_decode_merge_k computes from this one partial
+    if (g == 0) {
+      const float f = __builtin_amdgcn_exp2f(M - M);
+      const float L = fmaf(f, l, 0.f);
+      float o[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o[i] = fmaf(f, acc[i], 0.f) / L;
+      Vec8<kBF16>::store(a.o + b * a.so[0] + h * a.so[1] + c * 8, o);
+    }
+    return;
+  }
   if (g == 0) {
     float* wo = a.ws + (int64_t)part * 64 + c * 8;
     *reinterpret_cast<float4*>(wo) = make_float4(acc[0], acc[1], acc[2], acc[3]);
@@ -179,6 +212,14 @@ __global__ __launch_bounds__(64) void attn_decode_split_k(AttnDecodeArgs a) {
       wl[part] = l;
     }
   }
+}
+
+__global__ __launch_bounds__(64) void attn_decode_split_k(AttnDecodeArgs a) {
+  attn_decode_split_body<false>(a, AttnNewRow{nullptr, nullptr, 0});
+}
+
+__global__ __launch_bounds__(64) void attn_decode_append_split_k(AttnDecodeArgs a, AttnNewRow n) {
+  attn_decode_split_body<true>(a, n);
 }
 
 // grid: B * H one-wave workgroups; lane = output dim
@@ -239,6 +280,17 @@ void attn_decode(const AttnDecodeArgs& a_, hipStream_t st) {
   a.nparts = a.B * a.H * a.nchunks;
   hipLaunchKernelGGL(attn_decode_split_k, dim3(a.nparts), dim3(64), 0, st, a);
   hipLaunchKernelGGL(attn_decode_merge_k, dim3(a.B * a.H), dim3(64), 0, st, a);
+}
+
+void attn_decode_append(const AttnDecodeArgs& a_, const uint16_t* nk, const uint16_t* nv, int64_t snew,
+                        hipStream_t st) {
+  AttnDecodeArgs a = a_;
+  a.add = 1;
+  a.chunk = g_decode_chunk;
+  a.nchunks = attn_decode_chunks(a.cap);
+  a.nparts = a.B * a.H * a.nchunks;
+  hipLaunchKernelGGL(attn_decode_append_split_k, dim3(a.nparts), dim3(64), 0, st, a, AttnNewRow{nk, nv, snew});
+  if (a.nchunks > 1) hipLaunchKernelGGL(attn_decode_merge_k, dim3(a.B * a.H), dim3(64), 0, st, a);
 }
 
 }  // namespace tbamd

@@ -2269,6 +2269,146 @@ Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const 
   return o;
 }
 
+// One decode step with the append folded in: qkv packed [B, 1, 3*H*64]; the k / v of the token go to
+// cache row positions[b] (dropped outside [0, cap)) and the query sees rows j <= positions[b] ->
+// o [B, H*64].  Same bits, output and caches, as attn_kv_append followed by attn_decode(add = 1).
+Tensor attn_decode_append(const Tensor& qkv, int64_t heads, const Tensor& k_cache, const Tensor& v_cache,
+                          const Tensor& positions, double scale) {
+  const at::DeviceGuard guard(k_cache.device());
+  TORCH_CHECK(k_cache.dim() == 4 && heads >= 1 && k_cache.size(1) == heads,
+              "attention decode: cache must be [B, H, cap, 64]");
+  const int64_t B = k_cache.size(0), H = heads, cap = k_cache.size(2);
+  TORCH_CHECK(B >= 1 && cap >= 1 && cap < (int64_t)INT32_MAX / 2, "attention decode: bad size");
+  TORCH_CHECK(B * H * (int64_t)tbamd::attn_decode_chunks((int)cap) < (int64_t)INT32_MAX / 64,
+              "attention decode: bad size");
+  TORCH_CHECK(qkv.dim() == 3 && qkv.size(1) == 1, "attention decode: qkv must be bf16 [B, 1, 3*H*64]");
+  tbamd::AttnDecodeArgs a{};
+  int64_t s[2];
+  a.q = packed_qkv(qkv, B, H, k_cache, s);
+  a.sq[0] = s[0], a.sq[1] = 64;
+  attn_view(k_cache, "k_cache", B, H, cap, &a.k, a.sk);
+  attn_view(v_cache, "v_cache", B, H, cap, &a.v, a.sv);
+  TORCH_CHECK(v_cache.device() == k_cache.device(), "attention decode: caches on different devices");
+  a.klen = decode_lengths(positions, "positions", k_cache, B);
+  const int64_t need = tbamd::attn_decode_chunks((int)cap) > 1 ? tbamd::attn_decode_workspace((int)B, (int)H, (int)cap) : 0;
+  Tensor ws;
+  if (need > 0) ws = at::empty({need}, k_cache.options().dtype(at::kFloat));
+  Tensor o = at::empty({B, H * 64}, k_cache.options());
+  a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
+  a.so[0] = H * 64, a.so[1] = 64;
+  a.ws = need > 0 ? ws.data_ptr<float>() : nullptr;
+  a.B = (int)B, a.H = (int)H, a.cap = (int)cap, a.add = 1, a.scale = (float)scale;
+  tbamd::attn_decode_append(a, a.q + H * 64, a.q + 2 * H * 64, s[0], cur_stream());
+  return o;
+}
+
+// ------------------------------------------------------------ few-row products (csrc/rows_gemm.hip)
+// x [M, K] bf16 (1 <= M <= 16, unit column stride, row stride a multiple of 8) . weight [Q, K]^T ->
+// [M, Q].  gamma / beta: f32 [K] LayerNorm prologue (both or neither); epi: 0 none, 1 GELU, 2
+// + residual [M, Q].  out (optional, tests): contiguous bf16 [M, Q] written instead of a fresh tensor.
+Tensor rows_linear(const Tensor& x, const Tensor& weight, const optional<Tensor>& bias, const optional<Tensor>& gamma,
+                   const optional<Tensor>& beta, double eps, int64_t epi, const optional<Tensor>& residual,
+                   const optional<Tensor>& out) {
+  check_cuda(x, "x");
+  const at::DeviceGuard guard(x.device());
+  check_cuda(weight, "weight");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && weight.scalar_type() == at::kBFloat16, "rows_linear: bf16 only");
+  TORCH_CHECK(x.dim() == 2 && weight.dim() == 2 && weight.is_contiguous() && weight.device() == x.device(),
+              "rows_linear: x [M, K], weight [Q, K] contiguous, on one device");
+  const int64_t M = x.size(0), K = x.size(1), Q = weight.size(0);
+  TORCH_CHECK(M >= 1 && M <= 16 && K % 8 == 0 && K >= 8 && K <= 4096 && weight.size(1) == K && Q >= 1 &&
+                  Q < (int64_t)INT32_MAX / 16,
+              "rows_linear: 1 <= M <= 16, K % 8 == 0, K <= 4096");
+  TORCH_CHECK(x.stride(1) == 1 && (M == 1 || x.stride(0) % 8 == 0) && (M == 1 || x.stride(0) >= 0) &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(weight.data_ptr()) % 16 == 0,
+              "rows_linear: rows must be 16-B aligned with a unit column stride");
+  TORCH_CHECK(epi >= 0 && epi <= 2, "rows_linear: epilogue 0 (none), 1 (gelu) or 2 (residual)");
+  tbamd::RowsLinearArgs a{};
+  a.x = reinterpret_cast<const uint16_t*>(x.data_ptr());
+  a.w = reinterpret_cast<const uint16_t*>(weight.data_ptr());
+  a.sx = M == 1 ? 0 : x.stride(0);
+  if (bias.has_value() && bias->defined()) {
+    check_cuda(*bias, "bias");
+    TORCH_CHECK(bias->scalar_type() == at::kBFloat16 && bias->dim() == 1 && bias->size(0) == Q &&
+                    bias->is_contiguous() && bias->device() == x.device(),
+                "rows_linear: bias must be contiguous bf16 [Q]");
+    a.bias = reinterpret_cast<const uint16_t*>(bias->data_ptr());
+  }
+  const bool ln = gamma.has_value() && gamma->defined();
+  TORCH_CHECK(ln == (beta.has_value() && beta->defined()), "rows_linear: gamma and beta come together");
+  if (ln) {
+    for (const Tensor* t : {&*gamma, &*beta}) {
+      check_cuda(*t, "gamma / beta");
+      TORCH_CHECK(t->scalar_type() == at::kFloat && t->dim() == 1 && t->size(0) == K && t->is_contiguous() &&
+                      t->device() == x.device() && reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                  "rows_linear: gamma / beta must be contiguous, 16-B aligned f32 [K]");
+    }
+    a.gamma = gamma->data_ptr<float>();
+    a.beta = beta->data_ptr<float>();
+  }
+  Tensor y;
+  if (out.has_value() && out->defined()) {
+    y = *out;
+    check_cuda(y, "out");
+    TORCH_CHECK(y.scalar_type() == at::kBFloat16 && y.dim() == 2 && y.size(0) == M && y.size(1) == Q &&
+                    y.is_contiguous() && y.device() == x.device(),
+                "rows_linear: out must be contiguous bf16 [M, Q]");
+  } else {
+    y = at::empty({M, Q}, x.options());
+  }
+  if (epi == 2) {
+    TORCH_CHECK(residual.has_value() && residual->defined(), "rows_linear: the residual epilogue needs a residual");
+    const Tensor& r = *residual;
+    check_cuda(r, "residual");
+    TORCH_CHECK(r.scalar_type() == at::kBFloat16 && r.dim() == 2 && r.size(0) == M && r.size(1) == Q &&
+                    r.stride(1) == 1 && (M == 1 || r.stride(0) >= 0) && r.device() == x.device(),
+                "rows_linear: residual must be bf16 [M, Q] with a unit column stride");
+    a.res = reinterpret_cast<const uint16_t*>(r.data_ptr());
+    a.sres = M == 1 ? 0 : r.stride(0);
+  }
+  a.y = reinterpret_cast<uint16_t*>(y.data_ptr());
+  a.M = (int)M, a.K = (int)K, a.Q = (int)Q, a.epi = (int)epi, a.eps = (float)eps;
+  tbamd::rows_linear(a, cur_stream());
+  return y;
+}
+
+// tokens int64 [B, T] (any strides); tok_weight [vocab, D], pos_weight [max_len, D] bf16 contiguous; positions
+// int32 [B] or none -> [B, T, D].  Token ids and positions are clamped into range by the kernel.
+Tensor embed_rows(const Tensor& tokens, const Tensor& tok_weight, const Tensor& pos_weight,
+                  const optional<Tensor>& positions) {
+  check_cuda(tok_weight, "tok_weight");
+  const at::DeviceGuard guard(tok_weight.device());
+  check_cuda(tokens, "tokens");
+  check_cuda(pos_weight, "pos_weight");
+  TORCH_CHECK(tokens.scalar_type() == at::kLong && tokens.dim() == 2 && tokens.device() == tok_weight.device(),
+              "embed_rows: tokens must be int64 [B, T] on the device of the weights");
+  TORCH_CHECK(tok_weight.scalar_type() == at::kBFloat16 && pos_weight.scalar_type() == at::kBFloat16 &&
+                  tok_weight.dim() == 2 && pos_weight.dim() == 2 && tok_weight.is_contiguous() &&
+                  pos_weight.is_contiguous() && pos_weight.size(1) == tok_weight.size(1) &&
+                  pos_weight.device() == tok_weight.device(),
+              "embed_rows: weights must be contiguous bf16 [vocab, D] and [max_len, D]");
+  const int64_t B = tokens.size(0), T = tokens.size(1), D = tok_weight.size(1);
+  TORCH_CHECK(D % 8 == 0 && D >= 8 && tok_weight.size(0) >= 1 && pos_weight.size(0) >= 1 &&
+                  tok_weight.size(0) < (int64_t)INT32_MAX && pos_weight.size(0) < (int64_t)INT32_MAX &&
+                  D < (int64_t)INT32_MAX && B * T < (int64_t)INT32_MAX,
+              "embed_rows: D % 8 == 0; bad size");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(tok_weight.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(pos_weight.data_ptr()) % 16 == 0,
+              "embed_rows: weights not 16-B aligned");
+  tbamd::EmbedRowsArgs a{};
+  if (positions.has_value() && positions->defined()) a.pos = decode_lengths(*positions, "positions", tok_weight, B);
+  Tensor y = at::empty({B, T, D}, tok_weight.options());
+  a.tokens = tokens.data_ptr<int64_t>();
+  a.stok[0] = tokens.stride(0), a.stok[1] = tokens.stride(1);
+  a.tok_w = reinterpret_cast<const uint16_t*>(tok_weight.data_ptr());
+  a.pos_w = reinterpret_cast<const uint16_t*>(pos_weight.data_ptr());
+  a.y = reinterpret_cast<uint16_t*>(y.data_ptr());
+  a.B = (int)B, a.T = (int)T, a.D = (int)D, a.vocab = (int)tok_weight.size(0), a.max_len = (int)pos_weight.size(0);
+  tbamd::embed_rows(a, cur_stream());
+  return y;
+}
+
 // q: [B, T, H, 64] (any batch / token / head strides; the q part of a packed [B, T, 3*H*64] is such
 // a view) -> o [B, T, H*64].  Query t sees cache rows j < clamp(positions[b] + t + 1, 1, cap).
 // workspace (optional, tests): f32, at least attn_extend_workspace floats; by default it comes
@@ -2756,6 +2896,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("positions"));
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("heads"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("lengths"), py::arg("add"), py::arg("scale"), py::arg("workspace") = py::none());
+  m.def("attn_decode_append", &attn_decode_append, py::arg("qkv"), py::arg("heads"), py::arg("k_cache"),
+        py::arg("v_cache"), py::arg("positions"), py::arg("scale"));
+  m.def("rows_linear", &rows_linear, py::arg("x"), py::arg("weight"), py::arg("bias") = py::none(),
+        py::arg("gamma") = py::none(), py::arg("beta") = py::none(), py::arg("eps") = 0.0, py::arg("epi") = 0,
+        py::arg("residual") = py::none(), py::arg("out") = py::none());
+  m.def("embed_rows", &embed_rows, py::arg("tokens"), py::arg("tok_weight"), py::arg("pos_weight"),
+        py::arg("positions") = py::none());
   m.def("attn_decode_workspace", [](int64_t B, int64_t H, int64_t cap) {
     return tbamd::attn_decode_workspace((int)B, (int)H, (int)cap);
   });

@@ -304,6 +304,50 @@ int attn_decode_set_chunk(int n);
 int attn_decode_chunks(int cap);
 int64_t attn_decode_workspace(int B, int H, int cap);  // floats
 void attn_decode(const AttnDecodeArgs& a, hipStream_t st);
+// The append folded into the decode: klen holds the positions and add is 1.  nk / nv are the k and v
+// parts of the packed qkv [B][1][3*H*64] (batch stride snew, head stride 64).  The one wave whose
+// chunk contains row p = klen[b], 0 <= p < cap, takes that row from nk / nv instead of the cache and
+// stores it to the cache itself; any other p is dropped as attn_kv_append drops it.  Output and
+// caches have the bits of attn_kv_append followed by attn_decode.  With a single chunk (cap <=
+// chunk) the split kernel normalises and writes o itself: no merge launch, ws may be null.
+void attn_decode_append(const AttnDecodeArgs& a, const uint16_t* nk, const uint16_t* nv, int64_t snew,
+                        hipStream_t st);
+
+// ---- few-row products and the fused embedding (csrc/rows_gemm.hip; bf16, forward only) ----
+// y[M][Q] = epilogue(prologue(x)[M][K] . w[Q][K]^T + bias), 1 <= M <= 16, K % 8 == 0, K <= 4096.
+// x: row stride sx (elements, a multiple of 8 unless M == 1), unit column stride, 16-B aligned rows.
+// gamma / beta (f32 [K], both or neither): LayerNorm prologue with eps.  epi: kRowsGelu (exact GELU)
+// or kRowsResidual (+ res[M][Q], row stride sres; not y).  bias (bf16 [Q]) may be null.  cpw is
+// filled in by rows_linear.  Row m of y does not depend on M or on the other rows.
+enum : int { kRowsNone = 0, kRowsGelu = 1, kRowsResidual = 2 };
+struct RowsLinearArgs {
+  const uint16_t* x;
+  const uint16_t* w;
+  const uint16_t* bias;
+  const float* gamma;
+  const float* beta;
+  const uint16_t* res;
+  uint16_t* y;
+  int M, K, Q, epi;
+  int64_t sx, sres;
+  float eps;
+  int cpw;
+};
+int rows_linear_cols_per_wave(int Q);
+void rows_linear(const RowsLinearArgs& a, hipStream_t st);
+// y[b][t][:] = tok_w[clamp(tokens[b][t], 0, vocab - 1)] + pos_w[clamp(pos[b] + t, 0, max_len - 1)]
+// (f32 sum, one rounding); tokens int64 [B][T] with strides stok (elements), pos int32 [B] or null
+// (0), D % 8 == 0.
+struct EmbedRowsArgs {
+  const int64_t* tokens;
+  const uint16_t* tok_w;
+  const uint16_t* pos_w;
+  const int* pos;
+  uint16_t* y;
+  int64_t stok[2];
+  int B, T, D, vocab, max_len;
+};
+void embed_rows(const EmbedRowsArgs& a, hipStream_t st);
 
 // ---- KV-cache extend attention (csrc/attention_extend.hip; head dim 64, bf16) ----
 // T new queries per (batch, head) against the cache AFTER their own k / v rows were appended at

@@ -23,6 +23,12 @@ positions and lengths live in device memory -- so a step can be captured into a 
 (csrc/attention_extend.hip): ``generate(cache=...)`` continues a conversation with it, and
 ``generate(draft=...)`` is greedy speculative decoding, the target scoring a draft's proposals in one
 ``extend`` per round.
+
+Fused decoding (``fused=True`` on ``decode_step`` / ``extend`` / ``generate``, off by default): the same
+step on the few-row kernels -- ``embed_rows``, then per layer ``Block.forward_rows`` (LayerNorm, bias,
+GELU and residual folded into four ``linear_rows`` products, the cache append folded into the decode
+attention), then the final LayerNorm as the prologue of the vocabulary product.  ``embed_rows`` clamps a
+token id outside ``[0, vocab)`` into range, the one difference from the default path.
 """
 from __future__ import annotations
 
@@ -32,7 +38,7 @@ import torch
 from torch import Tensor, nn
 
 from torchbooster_amd.models.vit import Block
-from torchbooster_amd.ops.linear import Linear
+from torchbooster_amd.ops.linear import Linear, embed_rows, linear_rows
 from torchbooster_amd.ops.loss import linear_cross_entropy
 from torchbooster_amd.ops.norm import LayerNorm
 
@@ -163,9 +169,21 @@ class TransformerLM(nn.Module):
             h, _ = self.norm(x.contiguous(), pending.contiguous())
             return self.head(h[:, 0]), cache
 
-    def decode_step(self, token: Tensor, cache: KVCache) -> Tensor:
+    def _norm_ln(self):
+        return self.norm.weight, self.norm.bias, self.norm.eps
+
+    def decode_step(self, token: Tensor, cache: KVCache, *, fused: bool = False) -> Tensor:
         """One new token per sequence, ``token`` ``[B]``, at ``cache.positions`` -> logits ``[B, vocab]``;
-        ``cache.positions`` advance by one in place.  No device value is read on the host."""
+        ``cache.positions`` advance by one in place.  No device value is read on the host.
+        ``fused=True``: the few-row kernels (module docstring); same result to rounding."""
+        if fused:
+            with torch.no_grad():
+                x = embed_rows(token[:, None], self.tok.weight, self.pos[0], cache.positions)
+                for blk, kv in zip(self.blocks, cache.layers):
+                    x = blk.forward_rows(x, cache=kv, positions=cache.positions)
+                logits = linear_rows(x[:, 0], self.head.weight, self.head.bias, ln=self._norm_ln())
+                cache.positions.add_(1)
+                return logits
         with torch.no_grad():
             at = cache.positions.to(torch.int64).clamp(0, self.max_len - 1)
             x = (self.tok(token) + self.pos[0].index_select(0, at).to(self.tok.weight.dtype))[:, None]
@@ -178,7 +196,7 @@ class TransformerLM(nn.Module):
             return logits
 
     def extend(self, tokens: Tensor, cache: KVCache, lengths: Optional[Tensor] = None, *,
-               last_only: bool = False) -> Tensor:
+               last_only: bool = False, fused: bool = False) -> Tensor:
         """``T`` new tokens per sequence, ``tokens`` ``[B, T]``, on top of what ``cache`` holds: token ``t``
         of sequence ``b`` runs at position ``cache.positions[b] + t`` and attends to the cache rows up to
         and including its own (the extend kernel of csrc/attention_extend.hip) -> logits ``[B, T, vocab]``.
@@ -188,12 +206,28 @@ class TransformerLM(nn.Module):
         pad tokens land past the new position and are overwritten as the sequence grows, the rule of the
         ragged prefill.  ``last_only=True`` returns ``[B, vocab]``, the logits of token
         ``clamp(lengths[b], 1, T) - 1`` alone (gathered before the final LayerNorm and the head).
-        No device value is read on the host."""
+        No device value is read on the host.  ``fused=True``: the few-row kernels (module docstring; native
+        while ``B * T <= 16``, the PyTorch composition of ``linear_rows`` beyond); same result to rounding."""
         B, T = tokens.shape
         if T < 1:
             raise ValueError("extend needs at least one token per sequence")
         if T > cache.capacity:
             raise ValueError(f"{T} new tokens exceed the cache capacity {cache.capacity}")
+        if fused:
+            with torch.no_grad():
+                x = embed_rows(tokens, self.tok.weight, self.pos[0], cache.positions)
+                for blk, kv in zip(self.blocks, cache.layers):
+                    x = blk.forward_rows(x, cache=kv, positions=cache.positions, extend=True)
+                adv = None if lengths is None else lengths.clamp(1, T).to(torch.int32)
+                if last_only:
+                    if adv is None:
+                        x = x[:, T - 1]
+                    else:
+                        last = (adv.to(torch.int64) - 1)[:, None, None].expand(B, 1, x.shape[-1])
+                        x = x.gather(1, last)[:, 0]
+                logits = linear_rows(x, self.head.weight, self.head.bias, ln=self._norm_ln())
+                cache.positions.add_(T if adv is None else adv)
+                return logits
         with torch.no_grad():
             at = cache.positions.to(torch.int64)[:, None] + torch.arange(T, device=tokens.device)[None, :]
             x = self.tok(tokens) + self.pos[0][at.clamp(0, self.max_len - 1)].to(self.tok.weight.dtype)
@@ -216,11 +250,12 @@ class TransformerLM(nn.Module):
             return logits
 
     def _speculative(self, tokens: Tensor, max_new_tokens: int, lengths: Optional[Tensor], eos: Optional[int],
-                     draft: "TransformerLM", gamma: int) -> Tuple[Tensor, Tensor]:
+                     draft: "TransformerLM", gamma: int, fused: bool = False) -> Tuple[Tensor, Tensor]:
         """Greedy speculative decoding (``generate(draft=...)``)."""
         B, N = tokens.shape
         dev = tokens.device
         cap = N + max_new_tokens + gamma
+        kw = {"fused": True} if fused else {}  # fused=False makes exactly the calls it always made
         tc, dc = KVCache(self, B, capacity=cap), KVCache(draft, B, capacity=cap)
         logits, _ = self.prefill(tokens, lengths, tc)
         draft.prefill(tokens, lengths, dc)
@@ -234,10 +269,10 @@ class TransformerLM(nn.Module):
             base = tc.positions.clone()
             block = [cur]
             for _ in range(gamma):
-                block.append(draft.decode_step(block[-1], dc).argmax(dim=-1))
-            draft.decode_step(block[-1], dc)  # the last proposal's k / v: the caches stay in step
+                block.append(draft.decode_step(block[-1], dc, **kw).argmax(dim=-1))
+            draft.decode_step(block[-1], dc, **kw)  # the last proposal's k / v: the caches stay in step
             block = torch.stack(block, dim=1)  # [B, gamma + 1]: cur, d_1 .. d_gamma
-            tgt = self.extend(block, tc).argmax(dim=-1)  # tgt[:, i]: the target's token after block[:, :i + 1]
+            tgt = self.extend(block, tc, **kw).argmax(dim=-1)  # tgt[:, i]: the target's token after block[:, :i + 1]
             agree = (block[:, 1:] == tgt[:, :-1]).to(torch.int64).cumprod(dim=1).sum(dim=1)
             n_emit = torch.minimum(agree + 1, (max_new_tokens - slot).clamp_min(0))  # 0: the sequence is done
             idx = slot[:, None] + steps
@@ -260,7 +295,8 @@ class TransformerLM(nn.Module):
     def generate(self, tokens: Tensor, max_new_tokens: int, lengths: Optional[Tensor] = None, *,
                  temperature: float = 0.0, top_k: Optional[int] = None, eos: Optional[int] = None,
                  generator=None, graph: bool = False, cache: Optional[KVCache] = None,
-                 draft: Optional["TransformerLM"] = None, draft_tokens: int = 4) -> Tuple[Tensor, Tensor]:
+                 draft: Optional["TransformerLM"] = None, draft_tokens: int = 4,
+                 fused: bool = False) -> Tuple[Tensor, Tensor]:
         """Continue the prompts ``tokens`` ``[B, N]`` (``lengths``: valid tokens of each, right-padded) by
         ``max_new_tokens`` tokens -> ``(out [B, max_new_tokens], out_lengths [B])``.
 
@@ -288,7 +324,11 @@ class TransformerLM(nn.Module):
         unambiguous.  Greedy only, eager only, own caches only (``temperature != 0``, ``top_k``,
         ``graph=True`` and ``cache`` raise), and ``N + max_new_tokens + draft_tokens`` must fit both
         models' ``max_len``.  Termination reads ONE device value (``slot.min()``) per round; ``eos`` is
-        applied after the loop."""
+        applied after the loop.
+
+        ``fused=True``: every ``decode_step`` / ``extend`` made here runs on the few-row kernels (module
+        docstring) -- with ``cache``, with ``graph=True`` and, with ``draft``, in both models.  ``prefill`` is
+        unchanged."""
         B, N = tokens.shape
         max_new_tokens = int(max_new_tokens)
         if max_new_tokens < 1:
@@ -310,8 +350,9 @@ class TransformerLM(nn.Module):
                 raise ValueError(f"prompt {N} + max_new_tokens {max_new_tokens} + draft_tokens {gamma} exceeds "
                                  f"max_len {min(self.max_len, draft.max_len)}")
             with torch.no_grad():
-                return self._speculative(tokens, max_new_tokens, lengths, eos, draft, gamma)
+                return self._speculative(tokens, max_new_tokens, lengths, eos, draft, gamma, fused)
         start = None
+        kw = {"fused": True} if fused else {}  # fused=False makes exactly the calls it always made
         if cache is not None:
             if cache.positions.shape[0] != B:
                 raise ValueError(f"the cache holds {cache.positions.shape[0]} sequences, tokens {B}")
@@ -325,7 +366,7 @@ class TransformerLM(nn.Module):
                 cache = KVCache(self, B, capacity=N + max_new_tokens)
                 logits, _ = self.prefill(tokens, lengths, cache)
             else:
-                logits = self.extend(tokens, cache, lengths, last_only=True)
+                logits = self.extend(tokens, cache, lengths, last_only=True, **kw)
                 start = cache.positions.clone()  # start[b] + prompt_len[b]
             out = torch.zeros(B, max_new_tokens, dtype=torch.int64, device=dev)
             out_lengths = torch.zeros(B, dtype=torch.int64, device=dev)
@@ -345,7 +386,7 @@ class TransformerLM(nn.Module):
                 cur.copy_(tok)
 
             def step() -> None:
-                emit(self.decode_step(cur, cache))
+                emit(self.decode_step(cur, cache, **kw))
 
             emit(logits)
             eager = max_new_tokens - 1

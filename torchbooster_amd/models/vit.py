@@ -24,7 +24,7 @@ from torchbooster_amd.ops.attention import (attention_decode_packed, attention_e
 from torchbooster_amd.ops.conv import Conv2d
 
 from torchbooster_amd.ops.norm import LayerNorm
-from torchbooster_amd.ops.linear import GeluLink, Linear, LinearGELU, linear
+from torchbooster_amd.ops.linear import GeluLink, Linear, LinearGELU, linear, linear_rows
 
 __all__ = ["ViT", "vit_b_16", "vit_s_16", "vit_tiny", "Attention", "Block"]
 
@@ -104,6 +104,31 @@ class Block(nn.Module):
         a = self.attn(h, key_lengths, cache=cache, positions=positions, extend=extend)
         h, x = self.ln2(x, a)
         return x, self.mlp(h)
+
+    def forward_rows(self, x: Tensor, *, cache, positions: Tensor, extend: bool = False) -> Tensor:
+        """The decoding layer on the few-row kernels (ops/linear.py ``linear_rows``; causal, forward only):
+        ``x`` ``[B, T, dim]`` is the residual stream itself -- there is no ``pending`` -- and so is the
+        result.  Both LayerNorms run as prologues of the product behind them, bias / GELU / residual as
+        epilogues, and with ``T == 1`` the cache append is folded into the decode attention
+        (``attention_decode_packed(fused=True)``): 5 launches with a single-chunk cache, 6 otherwise.
+        ``T > 1`` needs ``extend=True`` and uses ``attention_extend_packed``.  Computes what ``forward``
+        computes with ``cache`` / ``positions`` / ``extend``, to rounding."""
+        at = self.attn
+        if not at.causal:
+            raise ValueError("a KV cache needs causal attention")
+        if x.shape[1] != 1 and not extend:
+            raise ValueError("forward_rows: more than one token per sequence needs extend=True")
+        k_cache, v_cache = cache
+        scale = 1.0 / math.sqrt(at.hd)
+        qkv = linear_rows(x, at.qkv.weight, at.qkv.bias, ln=(self.ln1.weight, self.ln1.bias, self.ln1.eps))
+        if x.shape[1] == 1:
+            a = attention_decode_packed(qkv, at.heads, k_cache, v_cache, positions, scale, fused=True)
+        else:
+            a = attention_extend_packed(qkv, at.heads, k_cache, v_cache, positions, scale)
+        x = linear_rows(a, at.proj.weight, at.proj.bias, residual=x)
+        h = linear_rows(x, self.mlp.fc1.weight, self.mlp.fc1.bias, ln=(self.ln2.weight, self.ln2.bias, self.ln2.eps),
+                        act="gelu")
+        return linear_rows(h, self.mlp.fc2.weight, self.mlp.fc2.bias, residual=x)
 
 
 class ViT(nn.Module):

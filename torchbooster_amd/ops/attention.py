@@ -298,9 +298,14 @@ def attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tenso
 
 
 def attention_decode_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
-                            scale: Optional[float] = None) -> Tensor:
+                            scale: Optional[float] = None, *, fused: bool = False) -> Tensor:
     """One decode step on the packed ``[B, 1, 3*H*D]`` projection of the new token: append its k / v at
-    row ``positions[b]``, then attend to keys ``j <= positions[b]`` -> ``[B, 1, H*D]``."""
+    row ``positions[b]``, then attend to keys ``j <= positions[b]`` -> ``[B, 1, H*D]``.
+
+    ``fused=True`` (native path): the append is folded into the split kernel -- the wave whose chunk
+    holds row ``positions[b]`` takes it from ``qkv`` and stores it to the cache -- and a cache of a single
+    chunk is normalised there too, so a step is one or two launches instead of three.  Output and caches
+    have the bits of ``fused=False``."""
     _forward_only(qkv, k_cache, v_cache)
     if qkv.dim() != 3 or qkv.shape[1] != 1 or qkv.shape[2] % (3 * heads):
         raise RuntimeError("qkv must be [B, 1, 3*H*D]")
@@ -311,6 +316,8 @@ def attention_decode_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: T
         if _decode_native(qkv, k_cache, v_cache):
             qkv = qkv if _rows_ok(qkv) else qkv.contiguous()
             C = native()
+            if fused:
+                return C.attn_decode_append(qkv, heads, k_cache, v_cache, positions, scale).view(B, 1, heads * D)
             C.attn_kv_append(qkv, heads, k_cache, v_cache, positions)
             return C.attn_decode(qkv, heads, k_cache, v_cache, positions, 1, scale).view(B, 1, heads * D)
         _check_cache(k_cache, v_cache, B, heads, D, positions, "positions")

@@ -10,6 +10,11 @@ img_cls/lenet/lenet.py:33-35, resnet.py:112) -> cuBLAS.  Here, per step:
 * weight gradient ``dW = dYᵀ X`` (split-K over the batch x tokens rows);
 * ``db = Σ dY`` — a native column sum (``LinearGELU``: fused with GELU').
 
+Decoding has 1 - 16 rows per product, nothing for that engine's 128 - 256 row tiles:
+``linear_rows`` is the weight-streaming few-row kernel of csrc/rows_gemm.hip with a LayerNorm
+prologue and bias / GELU / residual epilogues, ``embed_rows`` the fused token + position embedding
+(both forward only).
+
 Weight/bias gradients land straight in the parameter's persistent gradient
 slot (ops/_ext.py ``take_slot``) — no accumulate-add or bucket copy per step.
 Shapes the engine does not take (a feature count not a multiple of 8, fp32 /
@@ -27,7 +32,7 @@ from torch import Tensor, nn
 from torchbooster_amd.ops import gemm as G
 from torchbooster_amd.ops._ext import native, slot_alias, take_slot, use_native
 
-__all__ = ["Linear", "linear", "LinearGELU", "linear_gelu", "GeluLink"]
+__all__ = ["Linear", "linear", "LinearGELU", "linear_gelu", "GeluLink", "linear_rows", "embed_rows"]
 
 # The fused epilogue stages the z tile through LDS with coalesced 16-B loads: 0.221 vs 0.273 ms
 # unfused, ViT-B/16 5245 / 5241 vs 5134 / 5137 img/s alternated (profiles/r03_gemm_nn/README.md;
@@ -270,3 +275,98 @@ class LinearGELU(nn.Linear):
 
     def forward(self, x: Tensor, link: Optional[GeluLink] = None) -> Tensor:
         return linear_gelu(x, self.weight, self.bias, link)
+
+
+# ---------------------------------------------------------------- few-row products (forward only)
+ROWS_MAX = 16  # rows the few-row kernel takes
+ROWS_MAX_K = 4096  # its reduction limit, the limit of ops.norm.layer_norm
+
+
+def _rows_forward_only(*tensors: Optional[Tensor]) -> None:
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError("linear_rows / embed_rows are forward-only: call them under torch.no_grad() or detach "
+                           "the inputs")
+
+
+def linear_rows(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, ln=None, act: Optional[str] = None,
+                residual: Optional[Tensor] = None) -> Tensor:
+    """``epilogue(linear(prologue(x), weight, bias))`` for the few rows of a decode step, in ONE kernel.
+
+    ``x`` ``[..., K]``, ``weight`` ``[Q, K]`` (the ``nn.Linear`` layout, read once), ``bias`` ``[Q]`` ->
+    ``[..., Q]``.  ``ln = (gamma, beta, eps)``: LayerNorm over ``K`` first (f32 statistics; no normalised
+    tensor is written).  ``act="gelu"``: exact GELU; ``residual`` ``[..., Q]``: added.  Both epilogues work
+    on the f32 accumulator, which is rounded once at the store; they exclude each other.
+
+    The native kernel (csrc/rows_gemm.hip) takes CUDA bf16 operands with at most 16 rows, ``K % 8 == 0``
+    and ``K <= 4096``; row ``m`` of its result has the same bits whether it is computed alone or among 16
+    rows.  Everything else (CPU tensors, other dtypes, more rows, another ``K``,
+    ``TBAMD_FORCE_REFERENCE=1``) is the PyTorch composition ``F.layer_norm -> F.linear -> F.gelu`` /
+    ``+ residual`` in the dtype of ``x``.  Forward only."""
+    _rows_forward_only(x, weight, bias, residual, *((ln[0], ln[1]) if ln is not None else ()))
+    if act not in (None, "gelu"):
+        raise ValueError(f"linear_rows: unsupported activation {act!r}")
+    if act is not None and residual is not None:
+        raise ValueError("linear_rows: one epilogue, act or residual")
+    K, Q = x.shape[-1], weight.shape[0]
+    lead = x.shape[:-1]
+    with torch.no_grad():
+        rows = x.reshape(-1, K)
+        M = rows.shape[0]
+        bf = torch.bfloat16
+        if (use_native(x) and x.dtype == bf and weight.dtype == bf and weight.is_cuda and 1 <= M <= ROWS_MAX
+                and K % 8 == 0 and 8 <= K <= ROWS_MAX_K and not torch.is_autocast_enabled("cuda")
+                and (bias is None or bias.dtype == bf) and (residual is None or residual.dtype == bf)
+                and (ln is None or (ln[0] is not None and ln[1] is not None and ln[0].dtype == torch.float32
+                                    and ln[1].dtype == torch.float32))):
+            if rows.stride(1) != 1 or (M > 1 and rows.stride(0) % 8) or rows.data_ptr() % 16:
+                rows = rows.contiguous()
+            res = None
+            if residual is not None:
+                res = residual.reshape(-1, Q)
+                if res.stride(1) != 1:
+                    res = res.contiguous()
+            g, b, eps = (ln[0].contiguous(), ln[1].contiguous(), float(ln[2])) if ln is not None else (None, None, 0.0)
+            y = native().rows_linear(rows, weight.contiguous(), None if bias is None else bias.contiguous(), g, b, eps,
+                                     1 if act == "gelu" else 2 if res is not None else 0, res)
+            return y.view(*lead, Q)
+        h = x
+        if ln is not None:
+            g, b, eps = ln
+            h = F.layer_norm(h, (K,), None if g is None else g.to(h.dtype), None if b is None else b.to(h.dtype),
+                             float(eps))
+        y = F.linear(h, weight.to(h.dtype), None if bias is None else bias.to(h.dtype))
+        if act == "gelu":
+            y = F.gelu(y)
+        if residual is not None:
+            y = y + residual.to(y.dtype)
+        return y
+
+
+def embed_rows(tokens: Tensor, tok_weight: Tensor, pos_weight: Tensor, positions: Optional[Tensor] = None) -> Tensor:
+    """Token plus learned position embedding of ``tokens`` ``[B, T]`` in one kernel -> ``[B, T, dim]`` in the
+    dtype of ``tok_weight`` ``[vocab, dim]``: ``tok_weight[id] + pos_weight[clamp(positions[b] + t, 0,
+    max_len - 1)]`` with ``pos_weight`` ``[max_len, dim]`` and ``positions`` int ``[B]`` (zeros when None),
+    summed in f32 and rounded once.
+
+    The one difference from ``nn.Embedding``: a token id outside ``[0, vocab)`` is CLAMPED into range, on
+    every path, instead of raising (CPU) or tripping a device-side assert (GPU) -- a bad id never becomes
+    an address.  Forward only."""
+    _rows_forward_only(tok_weight, pos_weight)
+    if tokens.dim() != 2:
+        raise RuntimeError("tokens must be [B, T]")
+    B, T = tokens.shape
+    if positions is not None and positions.shape != (B,):
+        raise RuntimeError("positions must have shape [B]")
+    with torch.no_grad():
+        bf = torch.bfloat16
+        if (use_native(tok_weight) and tokens.is_cuda and tok_weight.dtype == bf and pos_weight.dtype == bf
+                and pos_weight.is_cuda and tok_weight.shape[1] % 8 == 0 and B * T > 0
+                and (positions is None or (positions.is_cuda and positions.dtype == torch.int32))):
+            return native().embed_rows(tokens.to(torch.int64), tok_weight.contiguous(),
+                                       pos_weight.contiguous(), None if positions is None else positions.contiguous())
+        ids = tokens.to(torch.int64).clamp(0, tok_weight.shape[0] - 1)
+        at = torch.arange(T, device=tokens.device)[None, :].expand(B, T)
+        if positions is not None:
+            at = positions.to(torch.int64)[:, None] + at
+        at = at.clamp(0, pos_weight.shape[0] - 1)
+        return F.embedding(ids, tok_weight) + pos_weight[at].to(tok_weight.dtype)
