@@ -1,0 +1,413 @@
+// Bindings of the attention kernels (attention.hip, attention_decode.hip, attention_extend.hip) and
+// of the few-row decode products (rows_gemm.hip).
+#include "bind_common.h"
+
+namespace {
+using namespace tbbind;
+
+// the leading nd strides of a bf16 view into s (each a multiple of 8 elements unless its dim has
+// size 1) and its 16-B aligned base pointer
+const uint16_t* aligned_rows(const Tensor& t, int nd, int64_t* s, const char* what, const char* name) {
+  for (int i = 0; i < nd; ++i) {
+    TORCH_CHECK(t.stride(i) % 8 == 0 || t.size(i) == 1, what, ": ", name, " strides must be multiples of 8");
+    s[i] = t.stride(i);
+  }
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, what, ": ", name, " not 16-B aligned");
+  return reinterpret_cast<const uint16_t*>(t.data_ptr());
+}
+
+// q, k, v (and dq, dk, dv, o, dout): [B, H, N, 64] bf16 views with a unit
+// head-dim stride and 16-B aligned rows (any batch/head/token strides, so the
+// packed qkv projection output is consumed and the packed dqkv written in place)
+void attn_view(const Tensor& t, const char* name, int64_t B, int64_t H, int64_t N, const uint16_t** p, int64_t* s) {
+  check_cuda(t, name);
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16 && t.dim() == 4, "attention: ", name, " must be bf16 [B, H, N, D]");
+  TORCH_CHECK(t.size(0) == B && t.size(1) == H && t.size(2) == N && t.size(3) == 64 && t.stride(3) == 1,
+              "attention: ", name, " shape/stride mismatch (head dim 64, unit stride)");
+  *p = aligned_rows(t, 3, s, "attention", name);
+}
+
+// the caller's f32 workspace (tests) when given, else `need` floats from the caching allocator
+Tensor workspace_or_new(const optional<Tensor>& workspace, int64_t need, const Tensor& like, const char* what) {
+  if (!given(workspace)) return need > 0 ? at::empty({need}, like.options().dtype(at::kFloat)) : Tensor();
+  const Tensor& ws = *workspace;
+  check_cuda(ws, "workspace");
+  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() && ws.numel() >= need &&
+                  ws.device() == like.device() && reinterpret_cast<uintptr_t>(ws.data_ptr()) % 16 == 0,
+              what, ": workspace must be contiguous, 16-B aligned f32 with at least ", need, " elements");
+  return ws;
+}
+
+// The masks (self-attention; both optional): causal, and key_lengths = [B] int32 on q's device,
+// contiguous -- keys j >= key_lengths[b] are hidden from every query of batch b.  The kernels read
+// the lengths from device memory (no host sync, graph-capture safe) and clamp each into [1, N].
+void attn_masks(tbamd::AttnArgs& a, const Tensor& q, int64_t B, bool causal, const optional<Tensor>& key_lengths) {
+  a.causal = causal ? 1 : 0;
+  a.klen = nullptr;
+  if (!given(key_lengths)) return;
+  const Tensor& kl = *key_lengths;
+  check_cuda(kl, "key_lengths");
+  TORCH_CHECK(kl.scalar_type() == at::kInt, "attention: key_lengths must be int32");
+  TORCH_CHECK(kl.device() == q.device(), "attention: key_lengths must be on the device of q");
+  TORCH_CHECK(kl.dim() == 1 && kl.size(0) == B, "attention: key_lengths must have shape [B]");
+  TORCH_CHECK(kl.is_contiguous(), "attention: key_lengths must be contiguous");
+  a.klen = kl.data_ptr<int>();
+}
+
+// -> (o [B, N, H, 64] contiguous, lse [B, H, N] f32)
+std::vector<Tensor> attn_forward(const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool causal,
+                                 const optional<Tensor>& key_lengths) {
+  const at::DeviceGuard guard(q.device());
+  const int64_t B = q.size(0), H = q.size(1), N = q.size(2);
+  TORCH_CHECK(N >= 1 && B * H * ((N + 127) / 128) < (int64_t)INT32_MAX, "attention: bad size");
+  tbamd::AttnArgs a{};
+  attn_view(q, "q", B, H, N, &a.q, a.sq);
+  attn_view(k, "k", B, H, N, &a.k, a.sk);
+  attn_view(v, "v", B, H, N, &a.v, a.sv);
+  Tensor o = at::empty({B, N, H, 64}, q.options());
+  Tensor lse = at::empty({B, H, N}, q.options().dtype(at::kFloat));
+  Tensor ov = o.permute({0, 2, 1, 3});
+  const uint16_t* op;
+  attn_view(ov, "o", B, H, N, &op, a.so);
+  a.o = const_cast<uint16_t*>(op);
+  a.lse = lse.data_ptr<float>();
+  a.B = (int)B, a.H = (int)H, a.N = (int)N, a.scale = (float)scale;
+  attn_masks(a, q, B, causal, key_lengths);
+  tbamd::attn_fwd(a, cur_stream());
+  return {o, lse};
+}
+
+// writes dq, dk, dv (views, e.g. slices of one packed dqkv buffer)
+void attn_backward(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o, const Tensor& dout,
+                   const Tensor& lse, double scale, const Tensor& dq, const Tensor& dk, const Tensor& dv, bool causal,
+                   const optional<Tensor>& key_lengths) {
+  const at::DeviceGuard guard(q.device());
+  const int64_t B = q.size(0), H = q.size(1), N = q.size(2);
+  tbamd::AttnArgs a{};
+  attn_view(q, "q", B, H, N, &a.q, a.sq);
+  attn_view(k, "k", B, H, N, &a.k, a.sk);
+  attn_view(v, "v", B, H, N, &a.v, a.sv);
+  const uint16_t* p;
+  attn_view(o, "o", B, H, N, &p, a.so);
+  a.o = const_cast<uint16_t*>(p);
+  attn_view(dout, "dout", B, H, N, &a.dout, a.sdo);
+  attn_view(dq, "dq", B, H, N, &p, a.sdq);
+  a.dq = const_cast<uint16_t*>(p);
+  attn_view(dk, "dk", B, H, N, &p, a.sdk);
+  a.dk = const_cast<uint16_t*>(p);
+  attn_view(dv, "dv", B, H, N, &p, a.sdv);
+  a.dv = const_cast<uint16_t*>(p);
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() && lse.numel() == B * H * N, "attention: lse");
+  Tensor delta = at::empty({B, H, N}, lse.options());
+  a.lse = lse.data_ptr<float>();
+  a.delta = delta.data_ptr<float>();
+  a.B = (int)B, a.H = (int)H, a.N = (int)N, a.scale = (float)scale;
+  attn_masks(a, q, B, causal, key_lengths);
+  tbamd::attn_bwd(a, cur_stream());
+}
+
+// ---- KV-cache decoding (csrc/attention_decode.hip).  Cache: [B, H, cap, 64] bf16 views (checked as
+// attn_view checks q/k/v); lengths / positions: [B] int32 on the same device, read by the kernels.
+const int* decode_lengths(const Tensor& t, const char* name, const Tensor& like, int64_t B) {
+  check_cuda(t, name);
+  TORCH_CHECK(t.scalar_type() == at::kInt, "attention decode: ", name, " must be int32");
+  TORCH_CHECK(t.device() == like.device(), "attention decode: ", name, " must be on the device of the cache");
+  TORCH_CHECK(t.dim() == 1 && t.size(0) == B, "attention decode: ", name, " must have shape [B]");
+  TORCH_CHECK(t.is_contiguous(), "attention decode: ", name, " must be contiguous");
+  return t.data_ptr<int>();
+}
+
+// packed [B, T, 3*H*64] bf16: unit last stride, batch / token strides multiples of 8, 16-B aligned
+const uint16_t* packed_qkv(const Tensor& t, int64_t B, int64_t H, const Tensor& like, int64_t* s) {
+  check_cuda(t, "qkv");
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16 && t.dim() == 3, "attention decode: qkv must be bf16 [B, T, 3*H*64]");
+  TORCH_CHECK(t.size(0) == B && t.size(2) == 3 * H * 64 && t.stride(2) == 1,
+              "attention decode: qkv shape/stride mismatch (head dim 64, unit stride)");
+  TORCH_CHECK(t.device() == like.device(), "attention decode: qkv must be on the device of the cache");
+  return aligned_rows(t, 2, s, "attention decode", "qkv");
+}
+
+void attn_kv_append(const Tensor& qkv, int64_t heads, const Tensor& k_cache, const Tensor& v_cache,
+                    const Tensor& positions) {
+  const at::DeviceGuard guard(k_cache.device());
+  TORCH_CHECK(k_cache.dim() == 4 && heads >= 1 && k_cache.size(1) == heads,
+              "attention decode: cache must be [B, H, cap, 64]");
+  const int64_t B = k_cache.size(0), H = heads, cap = k_cache.size(2);
+  TORCH_CHECK(qkv.dim() == 3, "attention decode: qkv must be bf16 [B, T, 3*H*64]");
+  const int64_t T = qkv.size(1);
+  TORCH_CHECK(B >= 1 && cap >= 1 && T >= 0 && B * T * H < (int64_t)1 << 34 && cap < (int64_t)INT32_MAX,
+              "attention decode: bad size");
+  tbamd::AttnAppendArgs a{};
+  a.qkv = packed_qkv(qkv, B, H, k_cache, a.sqkv);
+  const uint16_t* p;
+  attn_view(k_cache, "k_cache", B, H, cap, &p, a.sk);
+  a.kc = const_cast<uint16_t*>(p);
+  attn_view(v_cache, "v_cache", B, H, cap, &p, a.sv);
+  a.vc = const_cast<uint16_t*>(p);
+  TORCH_CHECK(v_cache.device() == k_cache.device(), "attention decode: caches on different devices");
+  a.pos = decode_lengths(positions, "positions", k_cache, B);
+  a.B = (int)B, a.T = (int)T, a.H = (int)H, a.cap = (int)cap;
+  tbamd::attn_kv_append(a, cur_stream());
+}
+
+// q: [B, H, 64] (any batch / head strides) or the packed [B, 1, 3*H*64] whose q part is read in
+// place -> o [B, H*64].  len = clamp(lengths[b] + add, 1, cap).  workspace (optional, tests): f32,
+// at least attn_decode_workspace floats; by default it comes from the caching allocator.
+Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const Tensor& v_cache, const Tensor& lengths,
+                   int64_t add, double scale, const optional<Tensor>& workspace) {
+  const at::DeviceGuard guard(k_cache.device());
+  TORCH_CHECK(k_cache.dim() == 4 && heads >= 1 && k_cache.size(1) == heads,
+              "attention decode: cache must be [B, H, cap, 64]");
+  const int64_t B = k_cache.size(0), H = heads, cap = k_cache.size(2);
+  TORCH_CHECK(B >= 1 && cap >= 1 && cap < (int64_t)INT32_MAX / 2 && add >= -cap && add <= cap,
+              "attention decode: bad size");
+  TORCH_CHECK(B * H * (int64_t)tbamd::attn_decode_chunks((int)cap) < (int64_t)INT32_MAX / 64,
+              "attention decode: bad size");
+  tbamd::AttnDecodeArgs a{};
+  if (q.dim() == 3 && q.size(1) == 1 && q.size(2) == 3 * H * 64) {
+    int64_t s[2];
+    a.q = packed_qkv(q, B, H, k_cache, s);
+    a.sq[0] = s[0], a.sq[1] = 64;
+  } else {
+    check_cuda(q, "q");
+    TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.dim() == 3 && q.size(0) == B && q.size(1) == H &&
+                    q.size(2) == 64 && q.stride(2) == 1,
+                "attention decode: q must be bf16 [B, H, 64] with a unit head-dim stride (or packed [B, 1, 3*H*64])");
+    TORCH_CHECK(q.device() == k_cache.device(), "attention decode: q must be on the device of the cache");
+    a.q = aligned_rows(q, 2, a.sq, "attention decode", "q");
+  }
+  attn_view(k_cache, "k_cache", B, H, cap, &a.k, a.sk);
+  attn_view(v_cache, "v_cache", B, H, cap, &a.v, a.sv);
+  TORCH_CHECK(v_cache.device() == k_cache.device(), "attention decode: caches on different devices");
+  a.klen = decode_lengths(lengths, "lengths", k_cache, B);
+  const int64_t need = tbamd::attn_decode_workspace((int)B, (int)H, (int)cap);
+  Tensor ws = workspace_or_new(workspace, need, k_cache, "attention decode");
+  Tensor o = at::empty({B, H * 64}, k_cache.options());
+  a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
+  a.so[0] = H * 64, a.so[1] = 64;
+  a.ws = ws.data_ptr<float>();
+  a.B = (int)B, a.H = (int)H, a.cap = (int)cap, a.add = (int)add, a.scale = (float)scale;
+  tbamd::attn_decode(a, cur_stream());
+  return o;
+}
+
+// One decode step with the append folded in: qkv packed [B, 1, 3*H*64]; the k / v of the token go to
+// cache row positions[b] (dropped outside [0, cap)) and the query sees rows j <= positions[b] ->
+// o [B, H*64].  Same bits, output and caches, as attn_kv_append followed by attn_decode(add = 1).
+Tensor attn_decode_append(const Tensor& qkv, int64_t heads, const Tensor& k_cache, const Tensor& v_cache,
+                          const Tensor& positions, double scale) {
+  const at::DeviceGuard guard(k_cache.device());
+  TORCH_CHECK(k_cache.dim() == 4 && heads >= 1 && k_cache.size(1) == heads,
+              "attention decode: cache must be [B, H, cap, 64]");
+  const int64_t B = k_cache.size(0), H = heads, cap = k_cache.size(2);
+  TORCH_CHECK(B >= 1 && cap >= 1 && cap < (int64_t)INT32_MAX / 2, "attention decode: bad size");
+  TORCH_CHECK(B * H * (int64_t)tbamd::attn_decode_chunks((int)cap) < (int64_t)INT32_MAX / 64,
+              "attention decode: bad size");
+  TORCH_CHECK(qkv.dim() == 3 && qkv.size(1) == 1, "attention decode: qkv must be bf16 [B, 1, 3*H*64]");
+  tbamd::AttnDecodeArgs a{};
+  int64_t s[2];
+  a.q = packed_qkv(qkv, B, H, k_cache, s);
+  a.sq[0] = s[0], a.sq[1] = 64;
+  attn_view(k_cache, "k_cache", B, H, cap, &a.k, a.sk);
+  attn_view(v_cache, "v_cache", B, H, cap, &a.v, a.sv);
+  TORCH_CHECK(v_cache.device() == k_cache.device(), "attention decode: caches on different devices");
+  a.klen = decode_lengths(positions, "positions", k_cache, B);
+  const int64_t need = tbamd::attn_decode_chunks((int)cap) > 1 ? tbamd::attn_decode_workspace((int)B, (int)H, (int)cap) : 0;
+  Tensor ws;
+  if (need > 0) ws = at::empty({need}, k_cache.options().dtype(at::kFloat));
+  Tensor o = at::empty({B, H * 64}, k_cache.options());
+  a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
+  a.so[0] = H * 64, a.so[1] = 64;
+  a.ws = need > 0 ? ws.data_ptr<float>() : nullptr;
+  a.B = (int)B, a.H = (int)H, a.cap = (int)cap, a.add = 1, a.scale = (float)scale;
+  tbamd::attn_decode_append(a, a.q + H * 64, a.q + 2 * H * 64, s[0], cur_stream());
+  return o;
+}
+
+// ------------------------------------------------------------ few-row products (csrc/rows_gemm.hip)
+// x [M, K] bf16 (1 <= M <= 16, unit column stride, row stride a multiple of 8) . weight [Q, K]^T ->
+// [M, Q].  gamma / beta: f32 [K] LayerNorm prologue (both or neither); epi: 0 none, 1 GELU, 2
+// + residual [M, Q].  out (optional, tests): contiguous bf16 [M, Q] written instead of a fresh tensor.
+Tensor rows_linear(const Tensor& x, const Tensor& weight, const optional<Tensor>& bias, const optional<Tensor>& gamma,
+                   const optional<Tensor>& beta, double eps, int64_t epi, const optional<Tensor>& residual,
+                   const optional<Tensor>& out) {
+  const at::DeviceGuard guard = on_device_of(x, "x");
+  check_cuda(weight, "weight");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && weight.scalar_type() == at::kBFloat16, "rows_linear: bf16 only");
+  TORCH_CHECK(x.dim() == 2 && weight.dim() == 2 && weight.is_contiguous() && weight.device() == x.device(),
+              "rows_linear: x [M, K], weight [Q, K] contiguous, on one device");
+  const int64_t M = x.size(0), K = x.size(1), Q = weight.size(0);
+  TORCH_CHECK(M >= 1 && M <= 16 && K % 8 == 0 && K >= 8 && K <= 4096 && weight.size(1) == K && Q >= 1 &&
+                  Q < (int64_t)INT32_MAX / 16,
+              "rows_linear: 1 <= M <= 16, K % 8 == 0, K <= 4096");
+  TORCH_CHECK(x.stride(1) == 1 && (M == 1 || x.stride(0) % 8 == 0) && (M == 1 || x.stride(0) >= 0) &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(weight.data_ptr()) % 16 == 0,
+              "rows_linear: rows must be 16-B aligned with a unit column stride");
+  TORCH_CHECK(epi >= 0 && epi <= 2, "rows_linear: epilogue 0 (none), 1 (gelu) or 2 (residual)");
+  tbamd::RowsLinearArgs a{};
+  a.x = reinterpret_cast<const uint16_t*>(x.data_ptr());
+  a.w = reinterpret_cast<const uint16_t*>(weight.data_ptr());
+  a.sx = M == 1 ? 0 : x.stride(0);
+  if (given(bias)) {
+    check_cuda(*bias, "bias");
+    TORCH_CHECK(bias->scalar_type() == at::kBFloat16 && bias->dim() == 1 && bias->size(0) == Q &&
+                    bias->is_contiguous() && bias->device() == x.device(),
+                "rows_linear: bias must be contiguous bf16 [Q]");
+    a.bias = reinterpret_cast<const uint16_t*>(bias->data_ptr());
+  }
+  const bool ln = given(gamma);
+  TORCH_CHECK(ln == given(beta), "rows_linear: gamma and beta come together");
+  if (ln) {
+    for (const Tensor* t : {&*gamma, &*beta}) {
+      check_cuda(*t, "gamma / beta");
+      TORCH_CHECK(t->scalar_type() == at::kFloat && t->dim() == 1 && t->size(0) == K && t->is_contiguous() &&
+                      t->device() == x.device() && reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                  "rows_linear: gamma / beta must be contiguous, 16-B aligned f32 [K]");
+    }
+    a.gamma = gamma->data_ptr<float>();
+    a.beta = beta->data_ptr<float>();
+  }
+  Tensor y;
+  if (given(out)) {
+    y = *out;
+    check_cuda(y, "out");
+    TORCH_CHECK(y.scalar_type() == at::kBFloat16 && y.dim() == 2 && y.size(0) == M && y.size(1) == Q &&
+                    y.is_contiguous() && y.device() == x.device(),
+                "rows_linear: out must be contiguous bf16 [M, Q]");
+  } else {
+    y = at::empty({M, Q}, x.options());
+  }
+  if (epi == 2) {
+    TORCH_CHECK(given(residual), "rows_linear: the residual epilogue needs a residual");
+    const Tensor& r = *residual;
+    check_cuda(r, "residual");
+    TORCH_CHECK(r.scalar_type() == at::kBFloat16 && r.dim() == 2 && r.size(0) == M && r.size(1) == Q &&
+                    r.stride(1) == 1 && (M == 1 || r.stride(0) >= 0) && r.device() == x.device(),
+                "rows_linear: residual must be bf16 [M, Q] with a unit column stride");
+    a.res = reinterpret_cast<const uint16_t*>(r.data_ptr());
+    a.sres = M == 1 ? 0 : r.stride(0);
+  }
+  a.y = reinterpret_cast<uint16_t*>(y.data_ptr());
+  a.M = (int)M, a.K = (int)K, a.Q = (int)Q, a.epi = (int)epi, a.eps = (float)eps;
+  tbamd::rows_linear(a, cur_stream());
+  return y;
+}
+
+// tokens int64 [B, T] (any strides); tok_weight [vocab, D], pos_weight [max_len, D] bf16 contiguous; positions
+// int32 [B] or none -> [B, T, D].  Token ids and positions are clamped into range by the kernel.
+Tensor embed_rows(const Tensor& tokens, const Tensor& tok_weight, const Tensor& pos_weight,
+                  const optional<Tensor>& positions) {
+  const at::DeviceGuard guard = on_device_of(tok_weight, "tok_weight");
+  check_cuda(tokens, "tokens");
+  check_cuda(pos_weight, "pos_weight");
+  TORCH_CHECK(tokens.scalar_type() == at::kLong && tokens.dim() == 2 && tokens.device() == tok_weight.device(),
+              "embed_rows: tokens must be int64 [B, T] on the device of the weights");
+  TORCH_CHECK(tok_weight.scalar_type() == at::kBFloat16 && pos_weight.scalar_type() == at::kBFloat16 &&
+                  tok_weight.dim() == 2 && pos_weight.dim() == 2 && tok_weight.is_contiguous() &&
+                  pos_weight.is_contiguous() && pos_weight.size(1) == tok_weight.size(1) &&
+                  pos_weight.device() == tok_weight.device(),
+              "embed_rows: weights must be contiguous bf16 [vocab, D] and [max_len, D]");
+  const int64_t B = tokens.size(0), T = tokens.size(1), D = tok_weight.size(1);
+  TORCH_CHECK(D % 8 == 0 && D >= 8 && tok_weight.size(0) >= 1 && pos_weight.size(0) >= 1 &&
+                  tok_weight.size(0) < (int64_t)INT32_MAX && pos_weight.size(0) < (int64_t)INT32_MAX &&
+                  D < (int64_t)INT32_MAX && B * T < (int64_t)INT32_MAX,
+              "embed_rows: D % 8 == 0; bad size");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(tok_weight.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(pos_weight.data_ptr()) % 16 == 0,
+              "embed_rows: weights not 16-B aligned");
+  tbamd::EmbedRowsArgs a{};
+  if (given(positions)) a.pos = decode_lengths(*positions, "positions", tok_weight, B);
+  Tensor y = at::empty({B, T, D}, tok_weight.options());
+  a.tokens = tokens.data_ptr<int64_t>();
+  a.stok[0] = tokens.stride(0), a.stok[1] = tokens.stride(1);
+  a.tok_w = reinterpret_cast<const uint16_t*>(tok_weight.data_ptr());
+  a.pos_w = reinterpret_cast<const uint16_t*>(pos_weight.data_ptr());
+  a.y = reinterpret_cast<uint16_t*>(y.data_ptr());
+  a.B = (int)B, a.T = (int)T, a.D = (int)D, a.vocab = (int)tok_weight.size(0), a.max_len = (int)pos_weight.size(0);
+  tbamd::embed_rows(a, cur_stream());
+  return y;
+}
+
+// q: [B, T, H, 64] (any batch / token / head strides; the q part of a packed [B, T, 3*H*64] is such
+// a view) -> o [B, T, H*64].  Query t sees cache rows j < clamp(positions[b] + t + 1, 1, cap).
+// workspace (optional, tests): f32, at least attn_extend_workspace floats; by default it comes
+// from the caching allocator (none at all with a single key split).
+Tensor attn_extend(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& positions,
+                   double scale, const optional<Tensor>& workspace) {
+  const at::DeviceGuard guard(k_cache.device());
+  TORCH_CHECK(k_cache.dim() == 4, "attention extend: cache must be [B, H, cap, 64]");
+  const int64_t B = k_cache.size(0), H = k_cache.size(1), cap = k_cache.size(2);
+  check_cuda(q, "q");
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.dim() == 4 && q.size(0) == B && q.size(2) == H &&
+                  q.size(3) == 64 && q.stride(3) == 1,
+              "attention extend: q must be bf16 [B, T, H, 64] with a unit head-dim stride");
+  const int64_t T = q.size(1);
+  TORCH_CHECK(B >= 1 && H >= 1 && T >= 1 && cap >= 1 && cap < (int64_t)INT32_MAX / 2 && T < (int64_t)INT32_MAX / 2,
+              "attention extend: bad size");
+  TORCH_CHECK(q.device() == k_cache.device(), "attention extend: q must be on the device of the cache");
+  tbamd::AttnExtendArgs a{};
+  a.q = aligned_rows(q, 3, a.sq, "attention extend", "q");
+  attn_view(k_cache, "k_cache", B, H, cap, &a.k, a.sk);
+  attn_view(v_cache, "v_cache", B, H, cap, &a.v, a.sv);
+  TORCH_CHECK(v_cache.device() == k_cache.device(), "attention extend: caches on different devices");
+  a.pos = decode_lengths(positions, "positions", k_cache, B);
+  // the split kernel's grid (one workgroup per partial) and the merge kernel's (one per output row)
+  const int64_t nqt = (T + 15) / 16;
+  TORCH_CHECK(B * H * nqt * (int64_t)tbamd::attn_extend_splits((int)B, (int)H, (int)T, (int)cap) <
+                      (int64_t)INT32_MAX / (16 * 66) &&
+                  B * T * H < (int64_t)INT32_MAX / 64,
+              "attention extend: bad size");
+  const int64_t need = tbamd::attn_extend_workspace((int)B, (int)H, (int)T, (int)cap);
+  Tensor ws = workspace_or_new(workspace, need, k_cache, "attention extend");
+  Tensor o = at::empty({B, T, H * 64}, k_cache.options());
+  a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
+  a.so[0] = T * H * 64, a.so[1] = H * 64;
+  a.ws = need > 0 ? ws.data_ptr<float>() : nullptr;
+  a.B = (int)B, a.T = (int)T, a.H = (int)H, a.cap = (int)cap, a.scale = (float)scale;
+  tbamd::attn_extend(a, cur_stream());
+  return o;
+}
+
+}  // namespace
+
+void register_attn(pybind11::module& m) {
+  m.def("attn_forward", &attn_forward, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
+        py::arg("causal") = false, py::arg("key_lengths") = py::none());
+  m.def("attn_backward", &attn_backward, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("dout"),
+        py::arg("lse"), py::arg("scale"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("causal") = false,
+        py::arg("key_lengths") = py::none());
+  m.def("attn_kv_append", &attn_kv_append, py::arg("qkv"), py::arg("heads"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("positions"));
+  m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("heads"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("lengths"), py::arg("add"), py::arg("scale"), py::arg("workspace") = py::none());
+  m.def("attn_decode_append", &attn_decode_append, py::arg("qkv"), py::arg("heads"), py::arg("k_cache"),
+        py::arg("v_cache"), py::arg("positions"), py::arg("scale"));
+  m.def("rows_linear", &rows_linear, py::arg("x"), py::arg("weight"), py::arg("bias") = py::none(),
+        py::arg("gamma") = py::none(), py::arg("beta") = py::none(), py::arg("eps") = 0.0, py::arg("epi") = 0,
+        py::arg("residual") = py::none(), py::arg("out") = py::none());
+  m.def("embed_rows", &embed_rows, py::arg("tokens"), py::arg("tok_weight"), py::arg("pos_weight"),
+        py::arg("positions") = py::none());
+  m.def("attn_extend", &attn_extend, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("positions"),
+        py::arg("scale"), py::arg("workspace") = py::none());
+  // knobs and workspace sizes
+  m.def("attn_set_head_mask", [](int64_t m) { return (int64_t)tbamd::attn_set_head_mask((int)m); });
+  m.def("attn_decode_workspace", [](int64_t B, int64_t H, int64_t cap) {
+    return tbamd::attn_decode_workspace((int)B, (int)H, (int)cap);
+  });
+  m.def("attn_decode_set_chunk", [](int64_t n) {
+    TORCH_CHECK(n < 0 || (n >= 8 && n % 8 == 0 && n <= (1 << 20)), "attn_decode_set_chunk: a multiple of 8, >= 8");
+    return (int64_t)tbamd::attn_decode_set_chunk((int)n);
+  });
+  m.def("attn_extend_splits", [](int64_t B, int64_t H, int64_t T, int64_t cap) {
+    return (int64_t)tbamd::attn_extend_splits((int)B, (int)H, (int)T, (int)cap);
+  });
+  m.def("attn_extend_workspace", [](int64_t B, int64_t H, int64_t T, int64_t cap) {
+    return tbamd::attn_extend_workspace((int)B, (int)H, (int)T, (int)cap);
+  });
+  m.def("attn_extend_set_split", [](int64_t n) {
+    TORCH_CHECK(n <= 0 || (n >= 8 && n % 8 == 0 && n <= (1 << 20)),
+                "attn_extend_set_split: 0 (the default policy) or a multiple of 8, >= 8");
+    return (int64_t)tbamd::attn_extend_set_split((int)n);
+  });
+}

@@ -1,7 +1,7 @@
 // Host-side launcher ABI shared by the HIP kernel files and the torch bindings.
 // Kernel translation units include only <hip/hip_runtime.h> (fast builds);
-// bindings.cpp includes torch and calls these with raw pointers + the current
-// HIP stream.
+// the bind_*.cpp files include torch and call these with raw pointers + the
+// current HIP stream.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
