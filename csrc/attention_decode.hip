@@ -5,20 +5,33 @@
 // is nothing for MFMA to do: the step is a streaming read of the cache, len x 64 x 2 x 2 bytes per
 // (batch, head), and its parallelism has to come from the keys.
 //
-//   attn_kv_append_k   copies the k and v rows of a packed qkv [B, T, 3*H*64] into the per-layer
-//                      cache [B, H, cap, 64] at rows pos[b] + t, 16 B per lane.
-//   attn_decode_split_k  one wave per (batch, head, chunk of `chunk` keys).  A wave load is 8 key rows
-//                      x 128 B = one coalesced 1 KiB: lane = 8 * rowgroup + c reads dims 8c .. 8c+7 of
-//                      row `rowgroup`.  q.k is a per-lane partial over 8 dims reduced over the 8 lanes
-//                      of the row (xor-shuffles 1, 2, 4); every row group keeps its own online
-//                      softmax (m, l) and each lane the 8 output dims of its c.  kUnroll rows per
+// Grouped-query attention: H query heads share Hkv key / value heads (G = H / Hkv, query head h reads
+// kv head h / G; Hkv = H is plain multi-head attention), the cache is [B, Hkv, cap, 64] and the
+// stream per step is G times shorter in HBM.  A wave serves a HEAD BLOCK of GB in {1, 2, 3, 4} query
+// heads of one group: one load of each row, GB independent copies of the per-head state and
+// arithmetic below.  GB divides G (G = 12: three blocks of 4, G = 6: two of 3, G = 5: five of 1).
+// With GB = 1 the G waves of a group load the same rows and the L2 serves the repeats; the host
+// shares loads only when the grid can spare the waves (attn_decode_head_block below: a block of GB
+// divides the waves by GB).  Per head the operations and their order do not depend on GB, so the
+// output has the bits of the G = 1 kernel on the cache expanded to H heads; the partials stay
+// indexed by query head, so the merge kernel and the workspace do not know about groups.
+//
+//   attn_kv_append_k   copies the k and v rows of a packed qkv [B, T, (H + 2*Hkv)*64] into the
+//                      per-layer cache [B, Hkv, cap, 64] at rows pos[b] + t, 16 B per lane.
+//   attn_decode_split_k  one wave per (batch, kv head, head block, chunk of `chunk` keys).  A wave
+//                      load is 8 key rows x 128 B = one coalesced 1 KiB: lane = 8 * rowgroup + c
+//                      reads dims 8c .. 8c+7 of row `rowgroup`.  Per query head of the block: q.k
+//                      is a per-lane partial over 8 dims reduced over the 8 lanes of the row
+//                      (xor-shuffles 1, 2, 4); every row group keeps its own online softmax
+//                      (m, l) and each lane the 8 output dims of its c.  kUnroll rows per
 //                      group are loaded before any is used (2 * kUnroll KiB in flight per wave).  The
 //                      8 row groups are merged once at the end (xor-shuffles 8, 16, 32: a fixed
 //                      tree) and lanes 0..7 write the partial: un-normalised fp32 o[64], running max
 //                      (log2 domain) and sum.
 //   attn_decode_append_split_k  the same wave with the append folded in (attn_decode_append): the
-//                      step's own row comes from the packed qkv and is stored to the cache by the
-//                      lanes that load it; a single-chunk cache is normalised and written here too.
+//                      step's own row comes from the packed qkv in every wave that meets it and is
+//                      stored to the cache by the lanes of the group's first head block; a
+//                      single-chunk cache is normalised and written here too.
 //   attn_decode_merge_k  one wave per (batch, head): merges the chunk partials in chunk order, divides
 //                      by the sum and writes bf16.  No float atomics: deterministic, every output
 //                      element written exactly once.
@@ -64,19 +77,19 @@ __device__ __forceinline__ int decode_len(const int* klen, int b, int add, int c
 __global__ __launch_bounds__(256) void attn_kv_append_k(AttnAppendArgs a) {
   // one lane per 16 B: (b, t, k|v, h, c)
   const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t total = (int64_t)a.B * a.T * 2 * a.H * 8;
+  const int64_t total = (int64_t)a.B * a.T * 2 * a.Hkv * 8;
   if (id >= total) return;
   const int c = (int)(id & 7);
   int64_t r = id >> 3;
-  const int h = (int)(r % a.H);
-  r /= a.H;
+  const int h = (int)(r % a.Hkv);
+  r /= a.Hkv;
   const int which = (int)(r & 1);
   r >>= 1;
   const int t = (int)(r % a.T);
   const int b = (int)(r / a.T);
   const int64_t row = (int64_t)a.pos[b] + t;
   if (row < 0 || row >= a.cap) return;  // dropped: a bad position never moves an address
-  const uint16_t* src = a.qkv + b * a.sqkv[0] + t * a.sqkv[1] + (int64_t)(1 + which) * a.H * 64 + h * 64 + c * 8;
+  const uint16_t* src = a.qkv + b * a.sqkv[0] + t * a.sqkv[1] + (int64_t)(a.H + which * a.Hkv) * 64 + h * 64 + c * 8;
   uint16_t* dst = which ? a.vc + b * a.sv[0] + h * a.sv[1] + row * a.sv[2] + c * 8
                         : a.kc + b * a.sk[0] + h * a.sk[1] + row * a.sk[2] + c * 8;
   *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
@@ -89,43 +102,55 @@ struct AttnNewRow {
   int64_t s;  // batch stride; the head stride is 64
 };
 
-// grid: B * H * nchunks one-wave workgroups, chunk fastest.  FUSED (attn_decode_append): row
-// p = klen[b] comes from `n` instead of the cache and the lanes that load it store it to the cache;
-// it is the last visible row (len = p + 1), so exactly one wave of a (batch, head) meets it and no
-// other wave reads it.  p outside [0, cap) equals no visible row index: nothing is stored.  With one
-// chunk the wave finishes with the merge kernel's own arithmetic (M - M, fma by exp2 of it, divide)
-// and writes bf16.
-template <bool FUSED>
+// grid: B * Hkv * (G / GB) * nchunks one-wave workgroups, chunk fastest, then the head block: the
+// wave serves query heads h0 .. h0 + GB - 1 of kv head hk, h0 = hk * G + hb * GB, and writes head
+// h0 + j's partial to that head's slot (b * H + h0 + j) * nchunks + ck.  With G = 1 the block index
+// IS that slot.  FUSED (attn_decode_append): row p = klen[b] comes from `n` (kv head hk of the packed
+// k / v parts) instead of the cache, in EVERY wave that meets it -- it is the last visible row (len =
+// p + 1), so one wave per (batch, kv head, head block) does -- and the lanes of head block 0 store it
+// to the cache: exactly one store per row, and no wave reads that cache row.  p outside [0, cap)
+// equals no visible row index: nothing is stored.  With one chunk the wave finishes each head with
+// the merge kernel's own arithmetic (M - M, fma by exp2 of it, divide) and writes bf16.
+template <bool FUSED, int GB>
 __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, const AttnNewRow& n) {
   const int lane = threadIdx.x;
   const int g = lane >> 3, c = lane & 7;
-  const int part = blockIdx.x;
-  const int ck = part % a.nchunks;
-  const int bh = part / a.nchunks;
-  const int h = bh % a.H, b = bh / a.H;
+  const int ck = blockIdx.x % a.nchunks;
+  int bh = blockIdx.x / a.nchunks;
+  const int hb = bh % a.nblk;
+  bh /= a.nblk;
+  const int hk = bh % a.Hkv, b = bh / a.Hkv;
+  const int h0 = hk * a.group + hb * GB;
+  const int part0 = (b * a.H + h0) * a.nchunks + ck;  // head h0 + j: part0 + j * nchunks
   const int len = decode_len(a.klen, b, a.add, a.cap);
   const int start = ck * a.chunk;
   float* wm = a.ws + (int64_t)a.nparts * 64;
   float* wl = wm + a.nparts;
   if (start >= len) {  // wave-uniform
-    if (lane == 0) {
-      wm[part] = -INFINITY;
-      wl[part] = 0.f;
+    if (lane < GB) {
+      wm[part0 + lane * a.nchunks] = -INFINITY;
+      wl[part0 + lane * a.nchunks] = 0.f;
     }
     return;
   }
   const int end = min(start + a.chunk, len);
 
-  float q[8];
-  unpack8(*reinterpret_cast<const uint4*>(a.q + b * a.sq[0] + h * a.sq[1] + c * 8), q);
+  float q[GB][8];
+#pragma unroll
+  for (int j = 0; j < GB; ++j)
+    unpack8(*reinterpret_cast<const uint4*>(a.q + b * a.sq[0] + (h0 + j) * a.sq[1] + c * 8), q[j]);
   const float sc = a.scale * kLog2e;
-  const uint16_t* kb = a.k + b * a.sk[0] + h * a.sk[1] + c * 8;
-  const uint16_t* vb = a.v + b * a.sv[0] + h * a.sv[1] + c * 8;
+  const uint16_t* kb = a.k + b * a.sk[0] + hk * a.sk[1] + c * 8;
+  const uint16_t* vb = a.v + b * a.sv[0] + hk * a.sv[1] + c * 8;
   const int64_t p = FUSED ? (int64_t)a.klen[b] : -1;
 
-  float m = -INFINITY, l = 0.f, acc[8];
+  float m[GB], l[GB], acc[GB][8];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+  for (int j = 0; j < GB; ++j) {
+    m[j] = -INFINITY, l[j] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[j][i] = 0.f;
+  }
 
   for (int r0 = start + g; r0 < end; r0 += 8 * kUnroll) {
     uint4 kr[kUnroll], vr[kUnroll];
@@ -138,88 +163,109 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
       kr[u] = make_uint4(0, 0, 0, 0);
       vr[u] = make_uint4(0, 0, 0, 0);
       if (FUSED && ok[u] && (int64_t)r == p) {  // 0 <= r < len <= cap: the store is inside the cache
-        kr[u] = *reinterpret_cast<const uint4*>(n.k + b * n.s + h * 64 + c * 8);
-        vr[u] = *reinterpret_cast<const uint4*>(n.v + b * n.s + h * 64 + c * 8);
-        *reinterpret_cast<uint4*>(const_cast<uint16_t*>(kb) + rr * a.sk[2]) = kr[u];
-        *reinterpret_cast<uint4*>(const_cast<uint16_t*>(vb) + rr * a.sv[2]) = vr[u];
+        kr[u] = *reinterpret_cast<const uint4*>(n.k + b * n.s + hk * 64 + c * 8);
+        vr[u] = *reinterpret_cast<const uint4*>(n.v + b * n.s + hk * 64 + c * 8);
+        if (hb == 0) {  // wave-uniform: one storing wave per (batch, kv head)
+          *reinterpret_cast<uint4*>(const_cast<uint16_t*>(kb) + rr * a.sk[2]) = kr[u];
+          *reinterpret_cast<uint4*>(const_cast<uint16_t*>(vb) + rr * a.sv[2]) = vr[u];
+        }
       } else if (ok[u]) {
         kr[u] = *reinterpret_cast<const uint4*>(kb + rr * a.sk[2]);
         vr[u] = *reinterpret_cast<const uint4*>(vb + rr * a.sv[2]);
       }
     }
-    float s[kUnroll];
-    float mn = m;
+    // from here on: GB copies of one head's arithmetic on the same rows
+    float s[GB][kUnroll];
+    float mn[GB];
+#pragma unroll
+    for (int j = 0; j < GB; ++j) mn[j] = m[j];
 #pragma unroll
     for (int u = 0; u < kUnroll; ++u) {
       float kf[8];
       unpack8(kr[u], kf);
-      float d = 0.f;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) d = fmaf(q[i], kf[i], d);
-      d = group8_sum(d) * sc;
-      s[u] = ok[u] ? d : -INFINITY;
-      mn = fmaxf(mn, s[u]);
+      for (int j = 0; j < GB; ++j) {
+        float d = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d = fmaf(q[j][i], kf[i], d);
+        d = group8_sum(d) * sc;
+        s[j][u] = ok[u] ? d : -INFINITY;
+        mn[j] = fmaxf(mn[j], s[j][u]);
+      }
     }
     // r0 < end: row u = 0 is visible, so mn is finite from here on
-    const float alpha = m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m - mn);
-    l *= alpha;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) acc[i] *= alpha;
+    for (int j = 0; j < GB; ++j) {
+      const float alpha = m[j] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m[j] - mn[j]);
+      l[j] *= alpha;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc[j][i] *= alpha;
+    }
 #pragma unroll
     for (int u = 0; u < kUnroll; ++u) {
-      const float p = ok[u] ? __builtin_amdgcn_exp2f(s[u] - mn) : 0.f;
       float vf[8];
       unpack8(vr[u], vf);  // zeros where !ok
-      l += p;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) acc[i] = fmaf(p, vf[i], acc[i]);
+      for (int j = 0; j < GB; ++j) {
+        const float p = ok[u] ? __builtin_amdgcn_exp2f(s[j][u] - mn[j]) : 0.f;
+        l[j] += p;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[j][i] = fmaf(p, vf[i], acc[j][i]);
+      }
     }
-    m = mn;
+#pragma unroll
+    for (int j = 0; j < GB; ++j) m[j] = mn[j];
   }
 
-  // merge the 8 row groups (a group with no row has m = -inf, l = 0, acc = 0)
-  float M = m;
-  M = fmaxf(M, __shfl_xor(M, 8, 64));
-  M = fmaxf(M, __shfl_xor(M, 16, 64));
-  M = fmaxf(M, __shfl_xor(M, 32, 64));
-  const float f = m == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m - M);
-  l *= f;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) acc[i] *= f;
+  for (int j = 0; j < GB; ++j) {
+    // merge the 8 row groups (a group with no row has m = -inf, l = 0, acc = 0)
+    float M = m[j];
+    M = fmaxf(M, __shfl_xor(M, 8, 64));
+    M = fmaxf(M, __shfl_xor(M, 16, 64));
+    M = fmaxf(M, __shfl_xor(M, 32, 64));
+    const float f = m[j] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m[j] - M);
+    l[j] *= f;
 #pragma unroll
-  for (int o = 8; o < 64; o <<= 1) {
-    l += __shfl_xor(l, o, 64);
+    for (int i = 0; i < 8; ++i) acc[j][i] *= f;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) acc[i] += __shfl_xor(acc[i], o, 64);
-  }
-  if (FUSED && a.nchunks == 1) {  // what attn_decode_merge_k computes from this one partial
+    for (int o = 8; o < 64; o <<= 1) {
+      l[j] += __shfl_xor(l[j], o, 64);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc[j][i] += __shfl_xor(acc[j][i], o, 64);
+    }
+    if (FUSED && a.nchunks == 1) {  // what attn_decode_merge_k computes from this one partial
+      if (g == 0) {
+        const float f = __builtin_amdgcn_exp2f(M - M);
+        const float L = fmaf(f, l[j], 0.f);
+        float o[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] = fmaf(f, acc[j][i], 0.f) / L;
+        Vec8<kBF16>::store(a.o + b * a.so[0] + (h0 + j) * a.so[1] + c * 8, o);
+      }
+      continue;
+    }
     if (g == 0) {
-      const float f = __builtin_amdgcn_exp2f(M - M);
-      const float L = fmaf(f, l, 0.f);
-      float o[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) o[i] = fmaf(f, acc[i], 0.f) / L;
-      Vec8<kBF16>::store(a.o + b * a.so[0] + h * a.so[1] + c * 8, o);
-    }
-    return;
-  }
-  if (g == 0) {
-    float* wo = a.ws + (int64_t)part * 64 + c * 8;
-    *reinterpret_cast<float4*>(wo) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    *reinterpret_cast<float4*>(wo + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
-    if (c == 0) {
-      wm[part] = M;
-      wl[part] = l;
+      const int part = part0 + j * a.nchunks;
+      float* wo = a.ws + (int64_t)part * 64 + c * 8;
+      *reinterpret_cast<float4*>(wo) = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
+      *reinterpret_cast<float4*>(wo + 4) = make_float4(acc[j][4], acc[j][5], acc[j][6], acc[j][7]);
+      if (c == 0) {
+        wm[part] = M;
+        wl[part] = l[j];
+      }
     }
   }
 }
 
+template <int GB>
 __global__ __launch_bounds__(64) void attn_decode_split_k(AttnDecodeArgs a) {
-  attn_decode_split_body<false>(a, AttnNewRow{nullptr, nullptr, 0});
+  attn_decode_split_body<false, GB>(a, AttnNewRow{nullptr, nullptr, 0});
 }
 
+template <int GB>
 __global__ __launch_bounds__(64) void attn_decode_append_split_k(AttnDecodeArgs a, AttnNewRow n) {
-  attn_decode_split_body<true>(a, n);
+  attn_decode_split_body<true, GB>(a, n);
 }
 
 // grid: B * H one-wave workgroups; lane = output dim
@@ -268,17 +314,61 @@ int attn_decode_chunks(int cap) { return (cap + g_decode_chunk - 1) / g_decode_c
 int64_t attn_decode_workspace(int B, int H, int cap) { return (int64_t)B * H * attn_decode_chunks(cap) * 66; }
 
 void attn_kv_append(const AttnAppendArgs& a, hipStream_t st) {
-  const int64_t total = (int64_t)a.B * a.T * 2 * a.H * 8;
+  const int64_t total = (int64_t)a.B * a.T * 2 * a.Hkv * 8;
   if (total == 0) return;
   hipLaunchKernelGGL(attn_kv_append_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
 }
 
-void attn_decode(const AttnDecodeArgs& a_, hipStream_t st) {
-  AttnDecodeArgs a = a_;
+// Query heads per wave.  A head block of GB loads a K / V row G / GB times instead of G times, and
+// leaves 1 / GB of the waves.  Reasoned from the bytes the first choice was the largest GB that
+// divides G; measured (profiles/gqa/README.md: H = 12, Hkv 6 .. 1, len 1024 .. 16384, B 1 .. 128) the
+// L2 serves the repeats of a group at no visible cost while the grid is small, and the waves are what
+// a call is short of: with W = B * H * nchunks one-head waves, GB = 1 is the fastest at every shape
+// up to W = 3072 (B = 8, len 4096: 23.6 us against 26.1 at GB = 4 and 35.5 on the expanded cache), at
+// W = 6144 GB = 2 leads by 6 % and GB = 4 trails, at W = 12288 GB = 4 leads GB = 1 by 6 .. 11 %, and
+// at W = 49152 sharing wins by 13 .. 18 %.  So the default is the largest GB of 4, 3, 2 that divides
+// G and still leaves kDecodeShareWaves waves (12 per CU on 256 CUs), else 1: a function of shapes
+// only.  The worst this rule does at a measured shape is 2.5 % behind the best block (G = 3,
+// W = 12288).  Any G runs natively whatever the block; G = 1 is always GB = 1.
+static int g_decode_head_block = 0;  // 0: the default policy; otherwise a forced block where it divides G
+constexpr int64_t kDecodeShareWaves = 3072;
+
+int attn_decode_set_head_block(int n) {
+  const int old = g_decode_head_block;
+  if (n >= 0 && n <= 4) g_decode_head_block = n;
+  return old;
+}
+
+int attn_decode_head_block(int B, int H, int Hkv, int cap) {
+  const int G = H / Hkv;
+  if (g_decode_head_block && G % g_decode_head_block == 0) return g_decode_head_block;
+  const int64_t waves = (int64_t)B * H * attn_decode_chunks(cap);
+  for (int gb = 4; gb > 1; --gb)
+    if (G % gb == 0 && waves / gb >= kDecodeShareWaves) return gb;
+  return 1;
+}
+
+// chunk / nchunks / nparts / group / nblk, and the head block the grid is built for
+static int decode_plan(AttnDecodeArgs& a) {
   a.chunk = g_decode_chunk;
   a.nchunks = attn_decode_chunks(a.cap);
   a.nparts = a.B * a.H * a.nchunks;
-  hipLaunchKernelGGL(attn_decode_split_k, dim3(a.nparts), dim3(64), 0, st, a);
+  a.group = a.H / a.Hkv;
+  const int gb = attn_decode_head_block(a.B, a.H, a.Hkv, a.cap);
+  a.nblk = a.group / gb;
+  return gb;
+}
+
+void attn_decode(const AttnDecodeArgs& a_, hipStream_t st) {
+  AttnDecodeArgs a = a_;
+  const int gb = decode_plan(a);
+  const dim3 grid(a.nparts / gb);  // B * Hkv * nblk * nchunks
+  switch (gb) {
+    case 1: hipLaunchKernelGGL(attn_decode_split_k<1>, grid, dim3(64), 0, st, a); break;
+    case 2: hipLaunchKernelGGL(attn_decode_split_k<2>, grid, dim3(64), 0, st, a); break;
+    case 3: hipLaunchKernelGGL(attn_decode_split_k<3>, grid, dim3(64), 0, st, a); break;
+    default: hipLaunchKernelGGL(attn_decode_split_k<4>, grid, dim3(64), 0, st, a); break;
+  }
   hipLaunchKernelGGL(attn_decode_merge_k, dim3(a.B * a.H), dim3(64), 0, st, a);
 }
 
@@ -286,10 +376,15 @@ void attn_decode_append(const AttnDecodeArgs& a_, const uint16_t* nk, const uint
                         hipStream_t st) {
   AttnDecodeArgs a = a_;
   a.add = 1;
-  a.chunk = g_decode_chunk;
-  a.nchunks = attn_decode_chunks(a.cap);
-  a.nparts = a.B * a.H * a.nchunks;
-  hipLaunchKernelGGL(attn_decode_append_split_k, dim3(a.nparts), dim3(64), 0, st, a, AttnNewRow{nk, nv, snew});
+  const int gb = decode_plan(a);
+  const dim3 grid(a.nparts / gb);
+  const AttnNewRow n{nk, nv, snew};
+  switch (gb) {
+    case 1: hipLaunchKernelGGL(attn_decode_append_split_k<1>, grid, dim3(64), 0, st, a, n); break;
+    case 2: hipLaunchKernelGGL(attn_decode_append_split_k<2>, grid, dim3(64), 0, st, a, n); break;
+    case 3: hipLaunchKernelGGL(attn_decode_append_split_k<3>, grid, dim3(64), 0, st, a, n); break;
+    default: hipLaunchKernelGGL(attn_decode_append_split_k<4>, grid, dim3(64), 0, st, a, n); break;
+  }
   if (a.nchunks > 1) hipLaunchKernelGGL(attn_decode_merge_k, dim3(a.B * a.H), dim3(64), 0, st, a);
 }
 

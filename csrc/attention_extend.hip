@@ -28,6 +28,11 @@
 //                      partials in split order, divides by the sum, writes bf16.  No atomics:
 //                      deterministic, every output element written exactly once.
 //
+// Grouped-query attention (caches [B, Hkv, cap, 64], G = H / Hkv): a wave still serves one query
+// head and reads kv head h / G; the G waves of a group read the same rows and the L2 serves the
+// repeats.  Nothing else changes, so the output has the bits of the same call on the cache expanded to
+// H heads.  (Packing the (t, g) rows of a group into one 16-query tile is not done: profiles/gqa.)
+//
 // pos is read on the device; the grid and the workspace are functions of (B, H, T, cap) only: no
 // host sync, a capture is safe and a replay follows in-place changes of pos.  The last query tile
 // is padded (pad queries take zeros for q and the last real query's limit; they are never stored).
@@ -124,8 +129,9 @@ __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
     for (int ks = 0; ks < 2; ++ks) qf[ks] = qreal ? ld_frag(qp + 32 * ks) : bf16x8_t{};
   }
   const float c = a.scale * kLog2e;
-  const uint16_t* kb = a.k + b * a.sk[0] + h * a.sk[1];
-  const uint16_t* vb = a.v + b * a.sv[0] + h * a.sv[1];
+  const int hk = h / a.group;  // grouped-query attention: the G heads of a group read the same rows
+  const uint16_t* kb = a.k + b * a.sk[0] + hk * a.sk[1];
+  const uint16_t* vb = a.v + b * a.sv[0] + hk * a.sv[1];
 
   f32x4_t acc[4];
 #pragma unroll
@@ -299,6 +305,7 @@ void attn_extend(const AttnExtendArgs& a_, hipStream_t st) {
   a.nsplit = (a.cap + a.split - 1) / a.split;
   a.nqt = (a.T + kQT - 1) / kQT;
   a.nparts = a.B * a.H * a.nqt * a.nsplit;
+  a.group = a.H / a.Hkv;
   hipLaunchKernelGGL(attn_extend_split_k, dim3(a.nparts), dim3(64), 0, st, a);
   if (a.nsplit > 1) hipLaunchKernelGGL(attn_extend_merge_k, dim3(a.B * a.T * a.H), dim3(64), 0, st, a);
 }

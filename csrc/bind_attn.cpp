@@ -106,8 +106,10 @@ void attn_backward(const Tensor& q, const Tensor& k, const Tensor& v, const Tens
   tbamd::attn_bwd(a, cur_stream());
 }
 
-// ---- KV-cache decoding (csrc/attention_decode.hip).  Cache: [B, H, cap, 64] bf16 views (checked as
+// ---- KV-cache decoding (csrc/attention_decode.hip).  Cache: [B, Hkv, cap, 64] bf16 views (checked as
 // attn_view checks q/k/v); lengths / positions: [B] int32 on the same device, read by the kernels.
+// kv_heads (trailing, 0 = heads) is grouped-query attention: it must divide heads, the cache must
+// have that many heads and a packed row is (H + 2*Hkv)*64 wide (bind_common.h).
 const int* decode_lengths(const Tensor& t, const char* name, const Tensor& like, int64_t B) {
   check_cuda(t, name);
   TORCH_CHECK(t.scalar_type() == at::kInt, "attention decode: ", name, " must be int32");
@@ -117,67 +119,68 @@ const int* decode_lengths(const Tensor& t, const char* name, const Tensor& like,
   return t.data_ptr<int>();
 }
 
-// packed [B, T, 3*H*64] bf16: unit last stride, batch / token strides multiples of 8, 16-B aligned
-const uint16_t* packed_qkv(const Tensor& t, int64_t B, int64_t H, const Tensor& like, int64_t* s) {
+// packed [B, T, (H + 2*Hkv)*64] bf16: unit last stride, batch / token strides multiples of 8, 16-B aligned
+const uint16_t* packed_qkv(const Tensor& t, int64_t B, int64_t H, int64_t Hkv, const Tensor& like, int64_t* s) {
   check_cuda(t, "qkv");
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16 && t.dim() == 3, "attention decode: qkv must be bf16 [B, T, 3*H*64]");
-  TORCH_CHECK(t.size(0) == B && t.size(2) == 3 * H * 64 && t.stride(2) == 1,
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16 && t.dim() == 3,
+              "attention decode: qkv must be bf16 [B, T, (H + 2*Hkv)*64]");
+  TORCH_CHECK(t.size(0) == B && t.size(2) == packed_qkv_width(H, Hkv) && t.stride(2) == 1,
               "attention decode: qkv shape/stride mismatch (head dim 64, unit stride)");
   TORCH_CHECK(t.device() == like.device(), "attention decode: qkv must be on the device of the cache");
   return aligned_rows(t, 2, s, "attention decode", "qkv");
 }
 
 void attn_kv_append(const Tensor& qkv, int64_t heads, const Tensor& k_cache, const Tensor& v_cache,
-                    const Tensor& positions) {
+                    const Tensor& positions, int64_t kv_heads) {
   const at::DeviceGuard guard(k_cache.device());
-  TORCH_CHECK(k_cache.dim() == 4 && heads >= 1 && k_cache.size(1) == heads,
-              "attention decode: cache must be [B, H, cap, 64]");
+  const int64_t Hkv = kv_heads_of(heads, kv_heads, "attention decode");
+  check_kv_cache(k_cache, Hkv, "attention decode");
   const int64_t B = k_cache.size(0), H = heads, cap = k_cache.size(2);
-  TORCH_CHECK(qkv.dim() == 3, "attention decode: qkv must be bf16 [B, T, 3*H*64]");
+  TORCH_CHECK(qkv.dim() == 3, "attention decode: qkv must be bf16 [B, T, (H + 2*Hkv)*64]");
   const int64_t T = qkv.size(1);
   TORCH_CHECK(B >= 1 && cap >= 1 && T >= 0 && B * T * H < (int64_t)1 << 34 && cap < (int64_t)INT32_MAX,
               "attention decode: bad size");
   tbamd::AttnAppendArgs a{};
-  a.qkv = packed_qkv(qkv, B, H, k_cache, a.sqkv);
+  a.qkv = packed_qkv(qkv, B, H, Hkv, k_cache, a.sqkv);
   const uint16_t* p;
-  attn_view(k_cache, "k_cache", B, H, cap, &p, a.sk);
+  attn_view(k_cache, "k_cache", B, Hkv, cap, &p, a.sk);
   a.kc = const_cast<uint16_t*>(p);
-  attn_view(v_cache, "v_cache", B, H, cap, &p, a.sv);
+  attn_view(v_cache, "v_cache", B, Hkv, cap, &p, a.sv);
   a.vc = const_cast<uint16_t*>(p);
   TORCH_CHECK(v_cache.device() == k_cache.device(), "attention decode: caches on different devices");
   a.pos = decode_lengths(positions, "positions", k_cache, B);
-  a.B = (int)B, a.T = (int)T, a.H = (int)H, a.cap = (int)cap;
+  a.B = (int)B, a.T = (int)T, a.H = (int)H, a.Hkv = (int)Hkv, a.cap = (int)cap;
   tbamd::attn_kv_append(a, cur_stream());
 }
 
-// q: [B, H, 64] (any batch / head strides) or the packed [B, 1, 3*H*64] whose q part is read in
+// q: [B, H, 64] (any batch / head strides) or the packed [B, 1, (H + 2*Hkv)*64] whose q part is read in
 // place -> o [B, H*64].  len = clamp(lengths[b] + add, 1, cap).  workspace (optional, tests): f32,
 // at least attn_decode_workspace floats; by default it comes from the caching allocator.
 Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const Tensor& v_cache, const Tensor& lengths,
-                   int64_t add, double scale, const optional<Tensor>& workspace) {
+                   int64_t add, double scale, const optional<Tensor>& workspace, int64_t kv_heads) {
   const at::DeviceGuard guard(k_cache.device());
-  TORCH_CHECK(k_cache.dim() == 4 && heads >= 1 && k_cache.size(1) == heads,
-              "attention decode: cache must be [B, H, cap, 64]");
+  const int64_t Hkv = kv_heads_of(heads, kv_heads, "attention decode");
+  check_kv_cache(k_cache, Hkv, "attention decode");
   const int64_t B = k_cache.size(0), H = heads, cap = k_cache.size(2);
   TORCH_CHECK(B >= 1 && cap >= 1 && cap < (int64_t)INT32_MAX / 2 && add >= -cap && add <= cap,
               "attention decode: bad size");
   TORCH_CHECK(B * H * (int64_t)tbamd::attn_decode_chunks((int)cap) < (int64_t)INT32_MAX / 64,
               "attention decode: bad size");
   tbamd::AttnDecodeArgs a{};
-  if (q.dim() == 3 && q.size(1) == 1 && q.size(2) == 3 * H * 64) {
+  if (q.dim() == 3 && q.size(1) == 1 && q.size(2) == packed_qkv_width(H, Hkv)) {
     int64_t s[2];
-    a.q = packed_qkv(q, B, H, k_cache, s);
+    a.q = packed_qkv(q, B, H, Hkv, k_cache, s);
     a.sq[0] = s[0], a.sq[1] = 64;
   } else {
     check_cuda(q, "q");
     TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.dim() == 3 && q.size(0) == B && q.size(1) == H &&
                     q.size(2) == 64 && q.stride(2) == 1,
-                "attention decode: q must be bf16 [B, H, 64] with a unit head-dim stride (or packed [B, 1, 3*H*64])");
+                "attention decode: q must be bf16 [B, H, 64] with a unit head-dim stride (or packed [B, 1, (H + 2*Hkv)*64])");
     TORCH_CHECK(q.device() == k_cache.device(), "attention decode: q must be on the device of the cache");
     a.q = aligned_rows(q, 2, a.sq, "attention decode", "q");
   }
-  attn_view(k_cache, "k_cache", B, H, cap, &a.k, a.sk);
-  attn_view(v_cache, "v_cache", B, H, cap, &a.v, a.sv);
+  attn_view(k_cache, "k_cache", B, Hkv, cap, &a.k, a.sk);
+  attn_view(v_cache, "v_cache", B, Hkv, cap, &a.v, a.sv);
   TORCH_CHECK(v_cache.device() == k_cache.device(), "attention decode: caches on different devices");
   a.klen = decode_lengths(lengths, "lengths", k_cache, B);
   const int64_t need = tbamd::attn_decode_workspace((int)B, (int)H, (int)cap);
@@ -186,30 +189,30 @@ Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const 
   a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
   a.so[0] = H * 64, a.so[1] = 64;
   a.ws = ws.data_ptr<float>();
-  a.B = (int)B, a.H = (int)H, a.cap = (int)cap, a.add = (int)add, a.scale = (float)scale;
+  a.B = (int)B, a.H = (int)H, a.Hkv = (int)Hkv, a.cap = (int)cap, a.add = (int)add, a.scale = (float)scale;
   tbamd::attn_decode(a, cur_stream());
   return o;
 }
 
-// One decode step with the append folded in: qkv packed [B, 1, 3*H*64]; the k / v of the token go to
+// One decode step with the append folded in: qkv packed [B, 1, (H + 2*Hkv)*64]; the k / v of the token go to
 // cache row positions[b] (dropped outside [0, cap)) and the query sees rows j <= positions[b] ->
 // o [B, H*64].  Same bits, output and caches, as attn_kv_append followed by attn_decode(add = 1).
 Tensor attn_decode_append(const Tensor& qkv, int64_t heads, const Tensor& k_cache, const Tensor& v_cache,
-                          const Tensor& positions, double scale) {
+                          const Tensor& positions, double scale, int64_t kv_heads) {
   const at::DeviceGuard guard(k_cache.device());
-  TORCH_CHECK(k_cache.dim() == 4 && heads >= 1 && k_cache.size(1) == heads,
-              "attention decode: cache must be [B, H, cap, 64]");
+  const int64_t Hkv = kv_heads_of(heads, kv_heads, "attention decode");
+  check_kv_cache(k_cache, Hkv, "attention decode");
   const int64_t B = k_cache.size(0), H = heads, cap = k_cache.size(2);
   TORCH_CHECK(B >= 1 && cap >= 1 && cap < (int64_t)INT32_MAX / 2, "attention decode: bad size");
   TORCH_CHECK(B * H * (int64_t)tbamd::attn_decode_chunks((int)cap) < (int64_t)INT32_MAX / 64,
               "attention decode: bad size");
-  TORCH_CHECK(qkv.dim() == 3 && qkv.size(1) == 1, "attention decode: qkv must be bf16 [B, 1, 3*H*64]");
+  TORCH_CHECK(qkv.dim() == 3 && qkv.size(1) == 1, "attention decode: qkv must be bf16 [B, 1, (H + 2*Hkv)*64]");
   tbamd::AttnDecodeArgs a{};
   int64_t s[2];
-  a.q = packed_qkv(qkv, B, H, k_cache, s);
+  a.q = packed_qkv(qkv, B, H, Hkv, k_cache, s);
   a.sq[0] = s[0], a.sq[1] = 64;
-  attn_view(k_cache, "k_cache", B, H, cap, &a.k, a.sk);
-  attn_view(v_cache, "v_cache", B, H, cap, &a.v, a.sv);
+  attn_view(k_cache, "k_cache", B, Hkv, cap, &a.k, a.sk);
+  attn_view(v_cache, "v_cache", B, Hkv, cap, &a.v, a.sv);
   TORCH_CHECK(v_cache.device() == k_cache.device(), "attention decode: caches on different devices");
   a.klen = decode_lengths(positions, "positions", k_cache, B);
   const int64_t need = tbamd::attn_decode_chunks((int)cap) > 1 ? tbamd::attn_decode_workspace((int)B, (int)H, (int)cap) : 0;
@@ -219,8 +222,8 @@ Tensor attn_decode_append(const Tensor& qkv, int64_t heads, const Tensor& k_cach
   a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
   a.so[0] = H * 64, a.so[1] = 64;
   a.ws = need > 0 ? ws.data_ptr<float>() : nullptr;
-  a.B = (int)B, a.H = (int)H, a.cap = (int)cap, a.add = 1, a.scale = (float)scale;
-  tbamd::attn_decode_append(a, a.q + H * 64, a.q + 2 * H * 64, s[0], cur_stream());
+  a.B = (int)B, a.H = (int)H, a.Hkv = (int)Hkv, a.cap = (int)cap, a.add = 1, a.scale = (float)scale;
+  tbamd::attn_decode_append(a, a.q + H * 64, a.q + (H + Hkv) * 64, s[0], cur_stream());
   return o;
 }
 
@@ -329,27 +332,30 @@ Tensor embed_rows(const Tensor& tokens, const Tensor& tok_weight, const Tensor& 
   return y;
 }
 
-// q: [B, T, H, 64] (any batch / token / head strides; the q part of a packed [B, T, 3*H*64] is such
-// a view) -> o [B, T, H*64].  Query t sees cache rows j < clamp(positions[b] + t + 1, 1, cap).
+// q: [B, T, H, 64] (any batch / token / head strides; the q part of a packed [B, T, (H + 2*Hkv)*64] is
+// such a view) -> o [B, T, H*64].  H is q's; the caches hold kv_heads (0 = H) heads.  Query t sees cache rows j < clamp(positions[b] + t + 1, 1, cap).
 // workspace (optional, tests): f32, at least attn_extend_workspace floats; by default it comes
 // from the caching allocator (none at all with a single key split).
 Tensor attn_extend(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& positions,
-                   double scale, const optional<Tensor>& workspace) {
+                   double scale, const optional<Tensor>& workspace, int64_t kv_heads) {
   const at::DeviceGuard guard(k_cache.device());
   TORCH_CHECK(k_cache.dim() == 4, "attention extend: cache must be [B, H, cap, 64]");
-  const int64_t B = k_cache.size(0), H = k_cache.size(1), cap = k_cache.size(2);
+  const int64_t B = k_cache.size(0), cap = k_cache.size(2);
   check_cuda(q, "q");
-  TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.dim() == 4 && q.size(0) == B && q.size(2) == H &&
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.dim() == 4 && q.size(0) == B && q.size(2) >= 1 &&
                   q.size(3) == 64 && q.stride(3) == 1,
               "attention extend: q must be bf16 [B, T, H, 64] with a unit head-dim stride");
+  const int64_t H = q.size(2);
+  const int64_t Hkv = kv_heads_of(H, kv_heads, "attention extend");
+  check_kv_cache(k_cache, Hkv, "attention extend");
   const int64_t T = q.size(1);
   TORCH_CHECK(B >= 1 && H >= 1 && T >= 1 && cap >= 1 && cap < (int64_t)INT32_MAX / 2 && T < (int64_t)INT32_MAX / 2,
               "attention extend: bad size");
   TORCH_CHECK(q.device() == k_cache.device(), "attention extend: q must be on the device of the cache");
   tbamd::AttnExtendArgs a{};
   a.q = aligned_rows(q, 3, a.sq, "attention extend", "q");
-  attn_view(k_cache, "k_cache", B, H, cap, &a.k, a.sk);
-  attn_view(v_cache, "v_cache", B, H, cap, &a.v, a.sv);
+  attn_view(k_cache, "k_cache", B, Hkv, cap, &a.k, a.sk);
+  attn_view(v_cache, "v_cache", B, Hkv, cap, &a.v, a.sv);
   TORCH_CHECK(v_cache.device() == k_cache.device(), "attention extend: caches on different devices");
   a.pos = decode_lengths(positions, "positions", k_cache, B);
   // the split kernel's grid (one workgroup per partial) and the merge kernel's (one per output row)
@@ -364,7 +370,7 @@ Tensor attn_extend(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache
   a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
   a.so[0] = T * H * 64, a.so[1] = H * 64;
   a.ws = need > 0 ? ws.data_ptr<float>() : nullptr;
-  a.B = (int)B, a.T = (int)T, a.H = (int)H, a.cap = (int)cap, a.scale = (float)scale;
+  a.B = (int)B, a.T = (int)T, a.H = (int)H, a.Hkv = (int)Hkv, a.cap = (int)cap, a.scale = (float)scale;
   tbamd::attn_extend(a, cur_stream());
   return o;
 }
@@ -378,18 +384,19 @@ void register_attn(pybind11::module& m) {
         py::arg("lse"), py::arg("scale"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("causal") = false,
         py::arg("key_lengths") = py::none());
   m.def("attn_kv_append", &attn_kv_append, py::arg("qkv"), py::arg("heads"), py::arg("k_cache"), py::arg("v_cache"),
-        py::arg("positions"));
+        py::arg("positions"), py::arg("kv_heads") = 0);
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("heads"), py::arg("k_cache"), py::arg("v_cache"),
-        py::arg("lengths"), py::arg("add"), py::arg("scale"), py::arg("workspace") = py::none());
+        py::arg("lengths"), py::arg("add"), py::arg("scale"), py::arg("workspace") = py::none(),
+        py::arg("kv_heads") = 0);
   m.def("attn_decode_append", &attn_decode_append, py::arg("qkv"), py::arg("heads"), py::arg("k_cache"),
-        py::arg("v_cache"), py::arg("positions"), py::arg("scale"));
+        py::arg("v_cache"), py::arg("positions"), py::arg("scale"), py::arg("kv_heads") = 0);
   m.def("rows_linear", &rows_linear, py::arg("x"), py::arg("weight"), py::arg("bias") = py::none(),
         py::arg("gamma") = py::none(), py::arg("beta") = py::none(), py::arg("eps") = 0.0, py::arg("epi") = 0,
         py::arg("residual") = py::none(), py::arg("out") = py::none());
   m.def("embed_rows", &embed_rows, py::arg("tokens"), py::arg("tok_weight"), py::arg("pos_weight"),
         py::arg("positions") = py::none());
   m.def("attn_extend", &attn_extend, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("positions"),
-        py::arg("scale"), py::arg("workspace") = py::none());
+        py::arg("scale"), py::arg("workspace") = py::none(), py::arg("kv_heads") = 0);
   // knobs and workspace sizes
   m.def("attn_set_head_mask", [](int64_t m) { return (int64_t)tbamd::attn_set_head_mask((int)m); });
   m.def("attn_decode_workspace", [](int64_t B, int64_t H, int64_t cap) {
@@ -398,6 +405,16 @@ void register_attn(pybind11::module& m) {
   m.def("attn_decode_set_chunk", [](int64_t n) {
     TORCH_CHECK(n < 0 || (n >= 8 && n % 8 == 0 && n <= (1 << 20)), "attn_decode_set_chunk: a multiple of 8, >= 8");
     return (int64_t)tbamd::attn_decode_set_chunk((int)n);
+  });
+  m.def("attn_decode_set_head_block", [](int64_t n) {
+    TORCH_CHECK(n <= 4, "attn_decode_set_head_block: 0 (the default policy) or 1 .. 4");
+    return (int64_t)tbamd::attn_decode_set_head_block((int)n);
+  });
+  m.def("attn_decode_head_block", [](int64_t B, int64_t H, int64_t kv_heads, int64_t cap) {
+    const int64_t Hkv = kv_heads_of(H, kv_heads, "attn_decode_head_block");
+    TORCH_CHECK(B >= 1 && cap >= 1 && B < (int64_t)INT32_MAX && H < (int64_t)INT32_MAX && cap < (int64_t)INT32_MAX / 2,
+                "attn_decode_head_block: bad size");
+    return (int64_t)tbamd::attn_decode_head_block((int)B, (int)H, (int)Hkv, (int)cap);
   });
   m.def("attn_extend_splits", [](int64_t B, int64_t H, int64_t T, int64_t cap) {
     return (int64_t)tbamd::attn_extend_splits((int)B, (int)H, (int)T, (int)cap);

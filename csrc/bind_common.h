@@ -80,6 +80,21 @@ inline Tensor slot_or_new(const optional<Tensor>& o, int64_t C, const at::Tensor
   return at::empty({C}, fopt);
 }
 
+// ---- grouped-query attention: H query heads share Hkv key / value heads (query head h reads kv head
+// h / (H / Hkv)).  kv_heads = 0 stands for heads; it is never inferred from a cache's shape.
+inline int64_t kv_heads_of(int64_t heads, int64_t kv_heads, const char* what) {
+  TORCH_CHECK(heads >= 1 && kv_heads >= 0, what, ": heads must be >= 1 and kv_heads >= 0");
+  const int64_t hkv = kv_heads == 0 ? heads : kv_heads;
+  TORCH_CHECK(heads % hkv == 0, what, ": kv_heads ", hkv, " must divide heads ", heads);
+  return hkv;
+}
+// the cache of such a layer is [B, Hkv, cap, 64]
+inline void check_kv_cache(const Tensor& cache, int64_t hkv, const char* what) {
+  TORCH_CHECK(cache.dim() == 4 && cache.size(1) == hkv, what, ": cache must be [B, kv_heads = ", hkv, ", cap, 64]");
+}
+// elements of a packed q | k | v row, head dim 64
+inline int64_t packed_qkv_width(int64_t heads, int64_t hkv) { return (heads + 2 * hkv) * 64; }
+
 // ---- conv geometry: x [N, C, H, W], weight [K, C, R, S], output [N, K, P, Q] over the virtual
 // input pad(upsample_nearest(x, up)) (or, with dil > 1, x dilated by dil).  of() takes the sizes;
 // window() adds P, Q and runs the checks the caller names, under the caller's op name.

@@ -271,22 +271,28 @@ void attn_fwd(const AttnArgs& a, hipStream_t st);
 void attn_bwd(const AttnArgs& a, hipStream_t st);
 
 // ---- KV-cache incremental decoding (csrc/attention_decode.hip; head dim 64, bf16) ----
-// Cache, per layer: kc / vc [B][H][cap][64], strides in elements over (batch, head, row), head-dim
-// stride 1.  Append: the k and v rows of a packed qkv [B][T][3*H*64] (strides over batch, token) go
-// to cache rows pos[b] + t; a row outside [0, cap) is dropped.  pos: [B] int32, device memory.
+// Grouped-query attention: H query heads share Hkv key / value heads, Hkv divides H, G = H / Hkv,
+// and query head h reads kv head h / G (Hkv = H is plain multi-head attention).
+// Cache, per layer: kc / vc [B][Hkv][cap][64], strides in elements over (batch, head, row), head-dim
+// stride 1.  Append: the k and v rows of a packed qkv [B][T][(H + 2*Hkv)*64] (q | k | v, strides over
+// batch, token: k at element H*64, v at (H + Hkv)*64 of a row) go to cache rows pos[b] + t; a row
+// outside [0, cap) is dropped.  pos: [B] int32, device memory.
 struct AttnAppendArgs {
   const uint16_t* qkv;
   uint16_t* kc;
   uint16_t* vc;
   const int* pos;
-  int B, T, H, cap;
+  int B, T, H, Hkv, cap;
   int64_t sqkv[2], sk[3], sv[3];
 };
 void attn_kv_append(const AttnAppendArgs& a, hipStream_t st);
-// o[b][h][:] = softmax(q[b][h][:] . K[b][h][:len]^T * scale) . V[b][h][:len],
+// o[b][h][:] = softmax(q[b][h][:] . K[b][h / G][:len]^T * scale) . V[b][h / G][:len],
 // len = clamp(klen[b] + add, 1, cap); klen: [B] int32 in device memory, read by the kernels.  Rows at
 // or past len are never loaded.  q, o: strides over (batch, head).  ws: attn_decode_workspace(B, H,
-// cap) floats of per-chunk partials; chunk / nchunks / nparts are filled in by attn_decode.
+// cap) floats of per-chunk partials, indexed by QUERY head whatever Hkv is; chunk / nchunks / nparts
+// / group (G) / nblk (head blocks per group) are filled in by attn_decode.  A wave serves `head block` query heads of one group from one load
+// of each K / V row; per head the arithmetic and its order are those of Hkv = H, so the output has
+// the bits of the same call on the cache expanded to H heads.
 struct AttnDecodeArgs {
   const uint16_t* q;
   const uint16_t* k;
@@ -294,20 +300,27 @@ struct AttnDecodeArgs {
   uint16_t* o;
   const int* klen;
   float* ws;
-  int B, H, cap, add;
+  int B, H, Hkv, cap, add;
   float scale;
   int64_t sq[2], sk[3], sv[3], so[2];
-  int chunk, nchunks, nparts;
+  int chunk, nchunks, nparts, group, nblk;
 };
+// query heads per wave: 0 = the default policy (the largest of 4, 3, 2 that divides G and leaves the
+// grid enough waves, else 1: a function of B, H, Hkv, cap and the chunk size only), otherwise a
+// forced size in 1 .. 4 (used where it divides G, the default policy elsewhere); n < 0 only reads
+// it.  Returns the previous value.
+int attn_decode_set_head_block(int n);
+int attn_decode_head_block(int B, int H, int Hkv, int cap);
 // keys per workgroup (a multiple of 8, >= 8); n < 0 only reads it.  Returns the previous value.
 int attn_decode_set_chunk(int n);
 int attn_decode_chunks(int cap);
 int64_t attn_decode_workspace(int B, int H, int cap);  // floats
 void attn_decode(const AttnDecodeArgs& a, hipStream_t st);
 // The append folded into the decode: klen holds the positions and add is 1.  nk / nv are the k and v
-// parts of the packed qkv [B][1][3*H*64] (batch stride snew, head stride 64).  The one wave whose
-// chunk contains row p = klen[b], 0 <= p < cap, takes that row from nk / nv instead of the cache and
-// stores it to the cache itself; any other p is dropped as attn_kv_append drops it.  Output and
+// parts of the packed qkv [B][1][(H + 2*Hkv)*64] (batch stride snew, head stride 64).  Every wave
+// whose chunk contains row p = klen[b], 0 <= p < cap, takes that row from nk / nv instead of the
+// cache, and the one of them that serves the group's first head block stores it to the cache; any
+// other p is dropped as attn_kv_append drops it.  Output and
 // caches have the bits of attn_kv_append followed by attn_decode.  With a single chunk (cap <=
 // chunk) the split kernel normalises and writes o itself: no merge launch, ws may be null.
 void attn_decode_append(const AttnDecodeArgs& a, const uint16_t* nk, const uint16_t* nv, int64_t snew,
@@ -354,10 +367,10 @@ void embed_rows(const EmbedRowsArgs& a, hipStream_t st);
 // pos[b] + t: query t sees rows j < L(b, t) = clamp(pos[b] + t + 1, 1, cap) (64-bit arithmetic).
 // pos: [B] int32 in device memory, read by the kernels.  Rows at or past clamp(pos[b] + T, 1, cap)
 // never enter arithmetic; rows between a query's own limit and that bound (this call's tokens) may
-// be multiplied by an exact-zero probability.  q: strides in elements over (batch, token, head),
-// head-dim stride 1.  o: [B][T][H*64], strides over (batch, token).  ws: attn_extend_workspace(B, H,
+// be multiplied by an exact-zero probability.  Caches are [B][Hkv][cap][64] and query head h reads kv
+// head h / (H / Hkv).  q: strides in elements over (batch, token, head), head-dim stride 1.  o: [B][T][H*64], strides over (batch, token).  ws: attn_extend_workspace(B, H,
 // T, cap) floats (0 with a single split: the first kernel then writes o itself); split / nsplit /
-// nqt / nparts are filled in by attn_extend.
+// nqt / nparts / group (G) are filled in by attn_extend.
 struct AttnExtendArgs {
   const uint16_t* q;
   const uint16_t* k;
@@ -365,10 +378,10 @@ struct AttnExtendArgs {
   uint16_t* o;
   const int* pos;
   float* ws;
-  int B, T, H, cap;
+  int B, T, H, Hkv, cap;
   float scale;
   int64_t sq[3], sk[3], sv[3], so[2];
-  int split, nsplit, nqt, nparts;
+  int split, nsplit, nqt, nparts, group;
 };
 // keys per split: 0 = the default policy (split only when B * H * ceil(T / 16) cannot occupy the
 // chip), otherwise a forced size (a multiple of 8, >= 8; at or above cap: one split); n < 0 only

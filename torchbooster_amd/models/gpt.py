@@ -29,6 +29,13 @@ step on the few-row kernels -- ``embed_rows``, then per layer ``Block.forward_ro
 GELU and residual folded into four ``linear_rows`` products, the cache append folded into the decode
 attention), then the final LayerNorm as the prologue of the vocabulary product.  ``embed_rows`` clamps a
 token id outside ``[0, vocab)`` into range, the one difference from the default path.
+
+Grouped-query attention (``TransformerLM(..., kv_heads=Hkv)``, ``Hkv`` dividing ``heads``): the
+``heads`` query heads of every layer share ``Hkv`` key / value heads (``Hkv = 1`` is multi-query
+attention), so a :class:`KVCache` layer is ``[B, Hkv, capacity, hd]`` -- ``heads // Hkv`` times smaller,
+and as many times fewer bytes per decode step, which the decode kernel reads once for the heads that
+share them (ops/attention.py).  Everything above works unchanged in meaning, including a
+``generate(draft=)`` whose two models differ in ``kv_heads``.  ``kv_heads=None`` is ``heads``.
 """
 from __future__ import annotations
 
@@ -49,7 +56,7 @@ class KVCache:
     """Per-layer keys and values of a :class:`TransformerLM` for ``batch`` sequences of up to ``capacity``
     tokens (default and upper limit: the model's ``max_len``).
 
-    ``layers[i]`` is the ``(k, v)`` pair of block ``i``, each ``[B, H, capacity, hd]`` and uninitialised
+    ``layers[i]`` is the ``(k, v)`` pair of block ``i``, each ``[B, kv_heads, capacity, hd]`` and uninitialised
     (``torch.empty``): rows at or past a sequence's position never enter arithmetic (ops/attention.py).
     ``positions`` (int32 ``[B]``) is the row each sequence writes next = the number of tokens it holds."""
 
@@ -64,8 +71,8 @@ class KVCache:
         attn = model.blocks[0].attn
         self.capacity = capacity
         self.layers: List[Tuple[Tensor, Tensor]] = [
-            (torch.empty(batch, attn.heads, capacity, attn.hd, dtype=dtype, device=device),
-             torch.empty(batch, attn.heads, capacity, attn.hd, dtype=dtype, device=device))
+            (torch.empty(batch, attn.kv_heads, capacity, attn.hd, dtype=dtype, device=device),
+             torch.empty(batch, attn.kv_heads, capacity, attn.hd, dtype=dtype, device=device))
             for _ in model.blocks]
         self.positions = torch.zeros(batch, dtype=torch.int32, device=device)
 
@@ -86,12 +93,14 @@ def _sample(logits: Tensor, temperature: float, top_k: Optional[int], generator)
 
 
 class TransformerLM(nn.Module):
-    def __init__(self, vocab: int, dim: int, depth: int, heads: int, max_len: int, mlp_ratio: float = 4.0) -> None:
+    def __init__(self, vocab: int, dim: int, depth: int, heads: int, max_len: int, mlp_ratio: float = 4.0,
+                 kv_heads: Optional[int] = None) -> None:
         super().__init__()
         self.max_len = max_len
         self.tok = nn.Embedding(vocab, dim)
         self.pos = nn.Parameter(torch.zeros(1, max_len, dim))
-        self.blocks = nn.ModuleList([Block(dim, heads, mlp_ratio, causal=True) for _ in range(depth)])
+        self.blocks = nn.ModuleList([Block(dim, heads, mlp_ratio, causal=True, kv_heads=kv_heads)
+                                     for _ in range(depth)])
         self.norm = LayerNorm(dim, eps=1e-6)
         self.head = Linear(dim, vocab, bias=False)
         nn.init.normal_(self.tok.weight, std=0.02)

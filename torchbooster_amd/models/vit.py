@@ -40,22 +40,31 @@ class Attention(nn.Module):
     self-attention as without a cache, plus one append of the same k / v at ``positions``.  With
     ``extend=True`` an ``x`` of any ``[B, T >= 1, dim]`` is T new tokens on top of what the cache holds:
     their k / v are appended at ``positions[b] + t`` and query ``t`` attends to the cache rows
-    ``j <= positions[b] + t`` (``attention_extend_packed``; ``key_lengths`` is not used)."""
+    ``j <= positions[b] + t`` (``attention_extend_packed``; ``key_lengths`` is not used).
 
-    def __init__(self, dim: int, heads: int, causal: bool = False) -> None:
+    ``kv_heads`` (grouped-query attention, ops/attention.py): ``heads`` query heads share ``kv_heads``
+    key / value heads, query head ``h`` reading kv head ``h // (heads // kv_heads)``.  The projection is
+    ``Linear(dim, (heads + 2 * kv_heads) * hd)`` and a cache ``[B, kv_heads, cap, hd]``.  ``None`` is
+    ``heads``: plain multi-head attention, the same parameters and the same calls as without it."""
+
+    def __init__(self, dim: int, heads: int, causal: bool = False, kv_heads: Optional[int] = None) -> None:
         super().__init__()
+        if kv_heads is not None and (kv_heads < 1 or heads % kv_heads):
+            raise ValueError(f"kv_heads {kv_heads} must divide heads {heads}")
         self.heads = heads
+        self.kv_heads = heads if kv_heads is None else int(kv_heads)
         self.hd = dim // heads
         self.causal = causal
-        self.qkv = Linear(dim, 3 * dim)
+        self.qkv = Linear(dim, 3 * dim if kv_heads is None else (heads + 2 * self.kv_heads) * self.hd)
         self.proj = Linear(dim, dim)
 
     def forward(self, x: Tensor, key_lengths: Optional[Tensor] = None, *, cache=None,
                 positions: Optional[Tensor] = None, extend: bool = False) -> Tensor:
         scale = 1.0 / math.sqrt(self.hd)
+        kw = {} if self.kv_heads == self.heads else {"kv_heads": self.kv_heads}  # MHA: the calls it always made
         if cache is None:
             return self.proj(attention_packed(self.qkv(x), self.heads, scale, causal=self.causal,
-                                              key_lengths=key_lengths))
+                                              key_lengths=key_lengths, **kw))
         if not self.causal:
             raise ValueError("a KV cache needs causal attention")
         if positions is None:
@@ -63,11 +72,11 @@ class Attention(nn.Module):
         k_cache, v_cache = cache
         qkv = self.qkv(x)
         if extend:
-            return self.proj(attention_extend_packed(qkv, self.heads, k_cache, v_cache, positions, scale))
+            return self.proj(attention_extend_packed(qkv, self.heads, k_cache, v_cache, positions, scale, **kw))
         if x.shape[1] == 1:
-            return self.proj(attention_decode_packed(qkv, self.heads, k_cache, v_cache, positions, scale))
-        kv_cache_append(k_cache, v_cache, qkv, self.heads, positions)
-        return self.proj(attention_packed(qkv, self.heads, scale, causal=True, key_lengths=key_lengths))
+            return self.proj(attention_decode_packed(qkv, self.heads, k_cache, v_cache, positions, scale, **kw))
+        kv_cache_append(k_cache, v_cache, qkv, self.heads, positions, **kw)
+        return self.proj(attention_packed(qkv, self.heads, scale, causal=True, key_lengths=key_lengths, **kw))
 
 
 class MLP(nn.Module):
@@ -84,10 +93,11 @@ class MLP(nn.Module):
 
 
 class Block(nn.Module):
-    def __init__(self, dim: int, heads: int, mlp_ratio: float = 4.0, causal: bool = False) -> None:
+    def __init__(self, dim: int, heads: int, mlp_ratio: float = 4.0, causal: bool = False,
+                 kv_heads: Optional[int] = None) -> None:
         super().__init__()
         self.ln1 = LayerNorm(dim, eps=1e-6)
-        self.attn = Attention(dim, heads, causal)
+        self.attn = Attention(dim, heads, causal, kv_heads)
         self.ln2 = LayerNorm(dim, eps=1e-6)
         self.mlp = MLP(dim, int(dim * mlp_ratio))
 
@@ -120,11 +130,12 @@ class Block(nn.Module):
             raise ValueError("forward_rows: more than one token per sequence needs extend=True")
         k_cache, v_cache = cache
         scale = 1.0 / math.sqrt(at.hd)
+        kw = {} if at.kv_heads == at.heads else {"kv_heads": at.kv_heads}
         qkv = linear_rows(x, at.qkv.weight, at.qkv.bias, ln=(self.ln1.weight, self.ln1.bias, self.ln1.eps))
         if x.shape[1] == 1:
-            a = attention_decode_packed(qkv, at.heads, k_cache, v_cache, positions, scale, fused=True)
+            a = attention_decode_packed(qkv, at.heads, k_cache, v_cache, positions, scale, fused=True, **kw)
         else:
-            a = attention_extend_packed(qkv, at.heads, k_cache, v_cache, positions, scale)
+            a = attention_extend_packed(qkv, at.heads, k_cache, v_cache, positions, scale, **kw)
         x = linear_rows(a, at.proj.weight, at.proj.bias, residual=x)
         h = linear_rows(x, self.mlp.fc1.weight, self.mlp.fc1.bias, ln=(self.ln2.weight, self.ln2.bias, self.ln2.eps),
                         act="gelu")

@@ -31,7 +31,8 @@ kernels skip the key tiles no query of a workgroup sees instead of masking them;
 hidden keys are zeros.
 
 KV-cache decoding (forward only; csrc/attention_decode.hip).  A cache is, per layer, a ``k_cache`` and
-a ``v_cache`` of ``[B, H, cap, D]`` (``torch.empty`` is fine: see the guarantee below).
+a ``v_cache`` of ``[B, H, cap, D]`` (``torch.empty`` is fine: see the guarantee below; ``[B, Hkv, cap, D]``
+with ``kv_heads``, see the end of this docstring).
 
 * :func:`kv_cache_append` copies the k and v rows of a packed ``qkv`` ``[B, T, 3*H*D]`` into the
   caches: token ``t`` of batch ``b`` goes to row ``positions[b] + t``; a row outside ``[0, cap)`` is
@@ -70,6 +71,20 @@ exact-zero probability.  The native path (CUDA, bf16, D = 64) runs 16 queries pe
 splits the keys over workgroups only when ``B * H * ceil(T / 16)`` cannot occupy the chip
 (``attn_extend_set_split`` forces a split size, ``attn_extend_splits(B, H, T, cap)`` tells the count);
 the partials are merged in fixed order, and ``positions`` are read on the device as above.
+
+Grouped-query attention (``kv_heads=``): ``H`` query heads share ``Hkv`` key / value heads; ``Hkv``
+must divide ``H``, ``G = H // Hkv``, and query head ``h`` reads kv head ``h // G`` (the
+``repeat_interleave(G, dim=heads)`` convention; ``Hkv = 1`` is multi-query attention).  A packed
+projection is then ``[B, T, (H + 2*Hkv)*D]``, still ``q | k | v`` and head-major inside each part, and
+a cache is ``[B, Hkv, cap, D]``: ``G`` times smaller, and ``G`` times fewer bytes per decode step.
+``kv_heads=None`` means ``Hkv = H``, which is everything above unchanged.  ``kv_heads`` is always
+given explicitly, never inferred from a cache's shape: a cache with the wrong head count raises.  A
+``kv_heads`` that does not divide ``heads`` raises ``ValueError``; a cache or a packed width that does
+not match raises ``RuntimeError``.  The native decode kernel loads each cache row once for up to four
+query heads of a group, and the decode / extend results have the bits of the same call on the caches
+expanded to ``H`` heads.  Training and prefill (:func:`attention`, :func:`attention_packed` with
+``Hkv < H``) expand k / v to ``H`` heads -- one materialised copy -- and run the existing kernels under
+autograd, which sums dK / dV over each group; a group-aware training kernel is not part of this.
 """
 from __future__ import annotations
 
@@ -183,6 +198,23 @@ class _AttnPackedFn(torch.autograd.Function):
         return dqkv, None, None, None, None
 
 
+def _kv_heads(heads: int, kv_heads: Optional[int]) -> int:
+    """``Hkv`` of a grouped-query layer: ``heads`` by default, otherwise a divisor of ``heads``."""
+    hkv = heads if kv_heads is None else int(kv_heads)
+    if hkv < 1 or heads % hkv:
+        raise ValueError(f"kv_heads {kv_heads} must divide heads {heads}")
+    return hkv
+
+
+def _expand_kv(x: Tensor, G: int, dim: int) -> Tensor:
+    """Repeat every head of ``x`` (heads at ``dim``) ``G`` times in place (``repeat_interleave``): an
+    ``expand`` then a ``reshape``, one materialised copy whose gradient autograd sums over the group."""
+    shape = list(x.shape)
+    x = x.unsqueeze(dim + 1).expand(*shape[:dim + 1], G, *shape[dim + 1:])
+    shape[dim] *= G
+    return x.reshape(shape)
+
+
 def _rows_ok(t: Tensor) -> bool:
     return t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:-1]) and t.data_ptr() % 16 == 0
 
@@ -190,8 +222,15 @@ def _rows_ok(t: Tensor) -> bool:
 def attention(q: Tensor, k: Tensor, v: Tensor, scale: Optional[float] = None, *, causal: bool = False,
               key_lengths: Optional[Tensor] = None) -> Tensor:
     """[B, H, N, D] -> [B, H, N, D].  ``causal`` / ``key_lengths``: the masks of the module docstring
-    (self-attention: q, k, v of one shape; lengths clamped into [1, N])."""
+    (self-attention: q, k, v of one shape; lengths clamped into [1, N]).
+
+    Grouped-query attention: ``k`` / ``v`` may be ``[B, Hkv, N, D]`` with ``Hkv`` dividing ``H``; they are
+    expanded to ``H`` heads (one copy) and dK / dV are summed over each group by autograd.  There is no
+    group-aware training kernel."""
     scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else float(scale)
+    if q.dim() == 4 and k.dim() == 4 and k.shape == v.shape and k.shape[1] != q.shape[1]:
+        G = q.shape[1] // _kv_heads(q.shape[1], k.shape[1])
+        k, v = _expand_kv(k, G, 1), _expand_kv(v, G, 1)
     if (causal or key_lengths is not None) and not (q.dim() == 4 and q.shape == k.shape == v.shape):
         raise ValueError("attention masks need [B, H, N, D] self-attention inputs of one shape")
     _check_lengths(key_lengths, q.shape[0], q)
@@ -202,8 +241,24 @@ def attention(q: Tensor, k: Tensor, v: Tensor, scale: Optional[float] = None, *,
 
 
 def attention_packed(qkv: Tensor, heads: int, scale: Optional[float] = None, *, causal: bool = False,
-                     key_lengths: Optional[Tensor] = None) -> Tensor:
-    """[B, N, 3*H*D] packed q|k|v (head-major inside each) -> [B, N, H*D]; masks as :func:`attention`."""
+                     key_lengths: Optional[Tensor] = None, kv_heads: Optional[int] = None) -> Tensor:
+    """[B, N, 3*H*D] packed q|k|v (head-major inside each) -> [B, N, H*D]; masks as :func:`attention`.
+
+    ``kv_heads`` (grouped-query attention): ``qkv`` is ``[B, N, (H + 2*Hkv)*D]``.  With ``Hkv < H`` the
+    packed tensor is split, k / v are expanded to ``H`` heads (one materialised copy) and
+    :func:`attention` runs on that under autograd, which sums dK / dV over each group: a group-aware
+    training kernel is out of scope."""
+    hkv = _kv_heads(heads, kv_heads)
+    if hkv != heads:
+        B, N, E = qkv.shape
+        if E % (heads + 2 * hkv):
+            raise RuntimeError("qkv must be [B, N, (H + 2*Hkv)*D]")
+        D = E // (heads + 2 * hkv)
+        q = qkv[..., :heads * D].view(B, N, heads, D).transpose(1, 2)
+        k, v = (_expand_kv(qkv[..., o * D:(o + hkv) * D].view(B, N, hkv, D), heads // hkv, 2).transpose(1, 2)
+                for o in (heads, heads + hkv))
+        o = attention(q, k, v, 1.0 / math.sqrt(D) if scale is None else scale, causal=causal, key_lengths=key_lengths)
+        return o.transpose(1, 2).reshape(B, N, heads * D)
     B, N, E3 = qkv.shape
     D = E3 // (3 * heads)
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
@@ -222,9 +277,10 @@ def _forward_only(*tensors: Tensor) -> None:
 
 
 def _check_cache(k_cache: Tensor, v_cache: Tensor, B: int, H: int, D: int, pos: Tensor, name: str) -> None:
+    """``H``: the cache's head count, i.e. ``Hkv`` of a grouped-query layer."""
     if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or tuple(k_cache.shape[:2]) != (B, H) \
             or k_cache.shape[3] != D or k_cache.shape[2] < 1:
-        raise RuntimeError(f"k_cache / v_cache must be [B, H, cap, D] = [{B}, {H}, cap, {D}]")
+        raise RuntimeError(f"k_cache / v_cache must be [B, Hkv, cap, D] = [{B}, {H}, cap, {D}]")
     if pos.dtype != torch.int32 or pos.shape != (B,) or pos.device != k_cache.device:
         raise RuntimeError(f"{name} must be an int32 tensor of shape [B] on the device of the cache")
 
@@ -234,95 +290,113 @@ def _decode_native(x: Tensor, k_cache: Tensor, v_cache: Tensor) -> bool:
             and x.dtype == torch.bfloat16 and _rows_ok(k_cache) and _rows_ok(v_cache))
 
 
-def _append_ref(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, positions: Tensor) -> None:
+def _append_ref(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, positions: Tensor,
+                hkv: Optional[int] = None) -> None:
     """The PyTorch path of :func:`kv_cache_append`: seen from the cache, row j of batch b takes token
     j - positions[b] if that is one of the T tokens and keeps its bits otherwise (no host sync, no
     duplicate scatter indices, out-of-range rows simply have no cache row that asks for them)."""
     B, T, E3 = qkv.shape
-    D = E3 // (3 * heads)
+    hkv = heads if hkv is None else hkv
+    D = E3 // (heads + 2 * hkv)
     cap = k_cache.shape[2]
     t = torch.arange(cap, device=qkv.device)[None, :] - positions.to(torch.int64)[:, None]  # [B, cap]
     take = ((t >= 0) & (t < T))[:, None, :, None]
-    idx = t.clamp(0, max(T - 1, 0))[:, :, None, None].expand(B, cap, heads, D)
-    kv = qkv.reshape(B, T, 3, heads, D)
-    for cache, i in ((k_cache, 1), (v_cache, 2)):
-        rows = kv[:, :, i].gather(1, idx).permute(0, 2, 1, 3).to(cache.dtype)  # [B, H, cap, D]
+    idx = t.clamp(0, max(T - 1, 0))[:, :, None, None].expand(B, cap, hkv, D)
+    kv = qkv[..., heads * D:].reshape(B, T, 2, hkv, D)  # the k | v parts
+    for cache, i in ((k_cache, 0), (v_cache, 1)):
+        rows = kv[:, :, i].gather(1, idx).permute(0, 2, 1, 3).to(cache.dtype)  # [B, Hkv, cap, D]
         cache.copy_(torch.where(take, rows, cache))
 
 
 def _decode_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tensor, scale: float) -> Tensor:
     """The PyTorch path of :func:`attention_decode` (softmax in fp32, or fp64 for fp64 inputs).  Hidden
     rows are selected away before either product: a masked score is -inf whatever k held, and v is
-    zeroed there because 0 * NaN is NaN."""
+    zeroed there because 0 * NaN is NaN.  A cache of ``Hkv < H`` heads is grouped-query attention."""
     cap = k_cache.shape[2]
     n = lengths.to(torch.int64).clamp(1, cap)  # the kernels' clamp
     vis = (torch.arange(cap, device=q.device)[None, :] < n[:, None])[:, None, :]  # [B, 1, cap]
     ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    v = torch.where(vis[..., None], v_cache, torch.zeros((), dtype=v_cache.dtype, device=q.device)).to(ct)
+    B, H, D = q.shape
+    if k_cache.shape[1] != H:  # query head h reads kv head h // G
+        qg = q.to(ct).view(B, k_cache.shape[1], -1, D)
+        s = torch.einsum("bkgd,bkjd->bkgj", qg, k_cache.to(ct)) * scale
+        p = torch.softmax(s.masked_fill(~vis[:, :, None], float("-inf")), dim=-1)
+        return torch.einsum("bkgj,bkjd->bkgd", p, v).reshape(B, H, D).to(q.dtype)
     s = torch.einsum("bhd,bhjd->bhj", q.to(ct), k_cache.to(ct)) * scale
     p = torch.softmax(s.masked_fill(~vis, float("-inf")), dim=-1)
-    v = torch.where(vis[..., None], v_cache, torch.zeros((), dtype=v_cache.dtype, device=q.device)).to(ct)
     return torch.einsum("bhj,bhjd->bhd", p, v).to(q.dtype)
 
 
-def kv_cache_append(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, positions: Tensor) -> None:
-    """Write the k / v rows of the packed ``qkv`` ``[B, T, 3*H*D]`` into ``k_cache`` / ``v_cache``
-    ``[B, H, cap, D]`` at rows ``positions[b] + t`` (int32 ``[B]``); rows outside ``[0, cap)`` are dropped."""
+def kv_cache_append(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, positions: Tensor, *,
+                    kv_heads: Optional[int] = None) -> None:
+    """Write the k / v rows of the packed ``qkv`` ``[B, T, (H + 2*Hkv)*D]`` into ``k_cache`` / ``v_cache``
+    ``[B, Hkv, cap, D]`` at rows ``positions[b] + t`` (int32 ``[B]``); rows outside ``[0, cap)`` are dropped.
+    ``kv_heads``: ``Hkv`` of grouped-query attention (module docstring); ``None`` is ``H``."""
     _forward_only(qkv, k_cache, v_cache)
-    if qkv.dim() != 3 or qkv.shape[2] % (3 * heads):
-        raise RuntimeError("qkv must be [B, T, 3*H*D]")
+    hkv = _kv_heads(heads, kv_heads)
+    if qkv.dim() != 3 or qkv.shape[2] % (heads + 2 * hkv):
+        raise RuntimeError("qkv must be [B, T, (H + 2*Hkv)*D]")
     B, T, E3 = qkv.shape
     with torch.no_grad():
         if _decode_native(qkv, k_cache, v_cache):
             qkv = qkv if _rows_ok(qkv) else qkv.contiguous()
-            native().attn_kv_append(qkv, heads, k_cache, v_cache, positions)
+            native().attn_kv_append(qkv, heads, k_cache, v_cache, positions, hkv)
             return
-        _check_cache(k_cache, v_cache, B, heads, E3 // (3 * heads), positions, "positions")
-        _append_ref(k_cache, v_cache, qkv, heads, positions)
+        _check_cache(k_cache, v_cache, B, hkv, E3 // (heads + 2 * hkv), positions, "positions")
+        _append_ref(k_cache, v_cache, qkv, heads, positions, hkv)
 
 
 def attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tensor,
-                     scale: Optional[float] = None) -> Tensor:
+                     scale: Optional[float] = None, *, kv_heads: Optional[int] = None) -> Tensor:
     """One query per (batch, head): ``q`` ``[B, H, D]`` against the first ``clamp(lengths[b], 1, cap)``
-    rows of ``k_cache`` / ``v_cache`` ``[B, H, cap, D]`` -> ``[B, H, D]``."""
+    rows of ``k_cache`` / ``v_cache`` ``[B, Hkv, cap, D]`` -> ``[B, H, D]``.  ``kv_heads``: ``Hkv`` of
+    grouped-query attention (module docstring); ``None`` is ``H``."""
     _forward_only(q, k_cache, v_cache)
     if q.dim() != 3:
         raise RuntimeError("q must be [B, H, D]")
     B, H, D = q.shape
+    hkv = _kv_heads(H, kv_heads)
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     with torch.no_grad():
         if _decode_native(q, k_cache, v_cache):
             q = q if _rows_ok(q) else q.contiguous()
-            return native().attn_decode(q, H, k_cache, v_cache, lengths, 0, scale).view(B, H, D)
-        _check_cache(k_cache, v_cache, B, H, D, lengths, "lengths")
+            return native().attn_decode(q, H, k_cache, v_cache, lengths, 0, scale, None, hkv).view(B, H, D)
+        _check_cache(k_cache, v_cache, B, hkv, D, lengths, "lengths")
         return _decode_ref(q, k_cache, v_cache, lengths, scale)
 
 
 def attention_decode_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
-                            scale: Optional[float] = None, *, fused: bool = False) -> Tensor:
-    """One decode step on the packed ``[B, 1, 3*H*D]`` projection of the new token: append its k / v at
-    row ``positions[b]``, then attend to keys ``j <= positions[b]`` -> ``[B, 1, H*D]``.
+                            scale: Optional[float] = None, *, fused: bool = False,
+                            kv_heads: Optional[int] = None) -> Tensor:
+    """One decode step on the packed ``[B, 1, (H + 2*Hkv)*D]`` projection of the new token: append its k / v
+    at row ``positions[b]``, then attend to keys ``j <= positions[b]`` -> ``[B, 1, H*D]``.  ``kv_heads``:
+    ``Hkv`` of grouped-query attention (module docstring); ``None`` is ``H``.
 
     ``fused=True`` (native path): the append is folded into the split kernel -- the wave whose chunk
     holds row ``positions[b]`` takes it from ``qkv`` and stores it to the cache -- and a cache of a single
     chunk is normalised there too, so a step is one or two launches instead of three.  Output and caches
     have the bits of ``fused=False``."""
     _forward_only(qkv, k_cache, v_cache)
-    if qkv.dim() != 3 or qkv.shape[1] != 1 or qkv.shape[2] % (3 * heads):
-        raise RuntimeError("qkv must be [B, 1, 3*H*D]")
+    hkv = _kv_heads(heads, kv_heads)
+    if qkv.dim() != 3 or qkv.shape[1] != 1 or qkv.shape[2] % (heads + 2 * hkv):
+        raise RuntimeError("qkv must be [B, 1, (H + 2*Hkv)*D]")
     B, _, E3 = qkv.shape
-    D = E3 // (3 * heads)
+    D = E3 // (heads + 2 * hkv)
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     with torch.no_grad():
         if _decode_native(qkv, k_cache, v_cache):
             qkv = qkv if _rows_ok(qkv) else qkv.contiguous()
             C = native()
             if fused:
-                return C.attn_decode_append(qkv, heads, k_cache, v_cache, positions, scale).view(B, 1, heads * D)
-            C.attn_kv_append(qkv, heads, k_cache, v_cache, positions)
-            return C.attn_decode(qkv, heads, k_cache, v_cache, positions, 1, scale).view(B, 1, heads * D)
-        _check_cache(k_cache, v_cache, B, heads, D, positions, "positions")
-        _append_ref(k_cache, v_cache, qkv, heads, positions)
-        q = qkv.reshape(B, 3, heads, D)[:, 0]
+                return C.attn_decode_append(qkv, heads, k_cache, v_cache, positions, scale,
+                                            hkv).view(B, 1, heads * D)
+            C.attn_kv_append(qkv, heads, k_cache, v_cache, positions, hkv)
+            return C.attn_decode(qkv, heads, k_cache, v_cache, positions, 1, scale, None,
+                                 hkv).view(B, 1, heads * D)
+        _check_cache(k_cache, v_cache, B, hkv, D, positions, "positions")
+        _append_ref(k_cache, v_cache, qkv, heads, positions, hkv)
+        q = qkv[:, 0, :heads * D].reshape(B, heads, D)
         return _decode_ref(q, k_cache, v_cache, positions.to(torch.int64) + 1, scale).reshape(B, 1, heads * D)
 
 
@@ -330,7 +404,8 @@ def _extend_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor, 
     """The PyTorch path of :func:`attention_extend` (softmax in fp32, or fp64 for fp64 inputs), sync-free.
     ``q`` ``[B, T, H, D]`` -> ``[B, T, H, D]``.  Scores are masked to -inf by ``L(b, t)``; v is zeroed at
     rows ``>= clamp(positions[b] + T, 1, cap)`` before the product because 0 * NaN is NaN.  Rows between
-    a query's limit and that bound (this call's tokens) are multiplied by an exact-zero probability."""
+    a query's limit and that bound (this call's tokens) are multiplied by an exact-zero probability.
+    A cache of ``Hkv < H`` heads is grouped-query attention."""
     B, T, H, D = q.shape
     cap = k_cache.shape[2]
     pos = positions.to(torch.int64)
@@ -339,17 +414,23 @@ def _extend_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor, 
     vis = (j[None, None, :] < lim[:, :, None])[:, None]  # [B, 1, T, cap]
     held = (j[None, :] < (pos + T).clamp(1, cap)[:, None])[:, None, :, None]  # [B, 1, cap, 1]
     ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    v = torch.where(held, v_cache, torch.zeros((), dtype=v_cache.dtype, device=q.device)).to(ct)
+    if k_cache.shape[1] != H:  # query head h reads kv head h // G
+        qg = q.to(ct).reshape(B, T, k_cache.shape[1], -1, D)
+        s = torch.einsum("btkgd,bkjd->bkgtj", qg, k_cache.to(ct)) * scale
+        p = torch.softmax(s.masked_fill(~vis[:, :, None], float("-inf")), dim=-1)
+        return torch.einsum("bkgtj,bkjd->btkgd", p, v).reshape(B, T, H, D).to(q.dtype)
     s = torch.einsum("bthd,bhjd->bhtj", q.to(ct), k_cache.to(ct)) * scale
     p = torch.softmax(s.masked_fill(~vis, float("-inf")), dim=-1)
-    v = torch.where(held, v_cache, torch.zeros((), dtype=v_cache.dtype, device=q.device)).to(ct)
     return torch.einsum("bhtj,bhjd->bthd", p, v).to(q.dtype)
 
 
 def attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
-                     scale: Optional[float] = None) -> Tensor:
+                     scale: Optional[float] = None, *, kv_heads: Optional[int] = None) -> Tensor:
     """``T`` queries per (batch, head): ``q`` ``[B, T, H, D]`` (any view with a contiguous last dim), whose
-    k / v rows are already in ``k_cache`` / ``v_cache`` ``[B, H, cap, D]`` at rows ``positions[b] + t``.
-    Query ``t`` sees rows ``j < clamp(positions[b] + t + 1, 1, cap)`` -> ``[B, T, H, D]``.
+    k / v rows are already in ``k_cache`` / ``v_cache`` ``[B, Hkv, cap, D]`` at rows ``positions[b] + t``.
+    Query ``t`` sees rows ``j < clamp(positions[b] + t + 1, 1, cap)`` -> ``[B, T, H, D]``.  ``kv_heads``:
+    ``Hkv`` of grouped-query attention (module docstring); ``None`` is ``H``.
 
     Cache rows at or past ``clamp(positions[b] + T, 1, cap)`` never enter arithmetic; rows between a
     query's own limit and that bound are this call's tokens (real finite data) and may be multiplied by
@@ -358,37 +439,40 @@ def attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Ten
     if q.dim() != 4 or q.shape[1] < 1:
         raise RuntimeError("q must be [B, T >= 1, H, D]")
     B, T, H, D = q.shape
+    hkv = _kv_heads(H, kv_heads)
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     with torch.no_grad():
         if _decode_native(q, k_cache, v_cache):
             q = q if _rows_ok(q) else q.contiguous()
-            return native().attn_extend(q, k_cache, v_cache, positions, scale).view(B, T, H, D)
-        _check_cache(k_cache, v_cache, B, H, D, positions, "positions")
+            return native().attn_extend(q, k_cache, v_cache, positions, scale, None, hkv).view(B, T, H, D)
+        _check_cache(k_cache, v_cache, B, hkv, D, positions, "positions")
         return _extend_ref(q, k_cache, v_cache, positions, scale)
 
 
 def attention_extend_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
-                            scale: Optional[float] = None) -> Tensor:
-    """``T`` new tokens on their packed ``[B, T, 3*H*D]`` projection: append their k / v at rows
+                            scale: Optional[float] = None, *, kv_heads: Optional[int] = None) -> Tensor:
+    """``T`` new tokens on their packed ``[B, T, (H + 2*Hkv)*D]`` projection: append their k / v at rows
     ``positions[b] + t`` (rows outside ``[0, cap)`` are dropped), then query ``t`` attends to rows
     ``j < clamp(positions[b] + t + 1, 1, cap)`` -> ``[B, T, H*D]``.  ``T == 1`` is
-    :func:`attention_decode_packed`.  What may enter arithmetic: see :func:`attention_extend`."""
-    if qkv.dim() != 3 or qkv.shape[1] < 1 or qkv.shape[2] % (3 * heads):
-        raise RuntimeError("qkv must be [B, T >= 1, 3*H*D]")
+    :func:`attention_decode_packed`.  What may enter arithmetic: see :func:`attention_extend`.
+    ``kv_heads``: ``Hkv`` of grouped-query attention (module docstring); ``None`` is ``H``."""
+    hkv = _kv_heads(heads, kv_heads)
+    if qkv.dim() != 3 or qkv.shape[1] < 1 or qkv.shape[2] % (heads + 2 * hkv):
+        raise RuntimeError("qkv must be [B, T >= 1, (H + 2*Hkv)*D]")
     B, T, E3 = qkv.shape
     if T == 1:
-        return attention_decode_packed(qkv, heads, k_cache, v_cache, positions, scale)
+        return attention_decode_packed(qkv, heads, k_cache, v_cache, positions, scale, kv_heads=kv_heads)
     _forward_only(qkv, k_cache, v_cache)
-    D = E3 // (3 * heads)
+    D = E3 // (heads + 2 * hkv)
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     with torch.no_grad():
         if _decode_native(qkv, k_cache, v_cache):
             qkv = qkv if _rows_ok(qkv) else qkv.contiguous()
             C = native()
-            C.attn_kv_append(qkv, heads, k_cache, v_cache, positions)
-            q = qkv.view(B, T, 3, heads, D)[:, :, 0]
-            return C.attn_extend(q, k_cache, v_cache, positions, scale)
-        _check_cache(k_cache, v_cache, B, heads, D, positions, "positions")
-        _append_ref(k_cache, v_cache, qkv, heads, positions)
-        q = qkv.reshape(B, T, 3, heads, D)[:, :, 0]
+            C.attn_kv_append(qkv, heads, k_cache, v_cache, positions, hkv)
+            q = qkv[..., :heads * D].view(B, T, heads, D)
+            return C.attn_extend(q, k_cache, v_cache, positions, scale, None, hkv)
+        _check_cache(k_cache, v_cache, B, hkv, D, positions, "positions")
+        _append_ref(k_cache, v_cache, qkv, heads, positions, hkv)
+        q = qkv[..., :heads * D].reshape(B, T, heads, D)
         return _extend_ref(q, k_cache, v_cache, positions, scale).reshape(B, T, heads * D)
