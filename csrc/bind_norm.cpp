@@ -39,8 +39,9 @@ std::vector<Tensor> bn_forward(const Tensor& x_, const optional<Tensor>& weight,
   if (training) {
     TORCH_CHECK(M > 0, "bn_forward: empty batch in training mode");
     const int nblk = tbamd::bn_partial_blocks(M, C);
-    Tensor ws = at::empty({2, (int64_t)nblk, C}, fopt);
-    Tensor fws = at::empty({tbamd::colsum_workspace(nblk, C)}, x.options().dtype(at::kDouble));
+    const int prows = tbamd::bn_stats_rows(dt_code(x), nblk);  // f32 input: + the rounding-remainder rows
+    Tensor ws = at::empty({2, (int64_t)prows, C}, fopt);
+    Tensor fws = at::empty({tbamd::colsum_workspace(prows, C)}, x.options().dtype(at::kDouble));
     tbamd::bn_forward_train(dt_code(x), x.data_ptr(), M, C, g, b, fptr_mut(running_mean),
                             fptr_mut(running_var), nbt_ptr(num_batches_tracked), (float)momentum, (float)eps,
                             ws[0].data_ptr<float>(), ws[1].data_ptr<float>(), nblk, fws.data_ptr<double>(),
@@ -295,8 +296,9 @@ std::vector<Tensor> bn_stats(const Tensor& x_, const optional<Tensor>& stats, co
   } else {
     TORCH_CHECK(M > 0, "bn_stats: empty batch in training mode");
     const int nblk = tbamd::bn_partial_blocks(M, C);
-    Tensor ws = at::empty({2, (int64_t)nblk, C}, fopt);
-    Tensor fws = at::empty({tbamd::colsum_workspace(nblk, C)}, x.options().dtype(at::kDouble));
+    const int prows = tbamd::bn_stats_rows(dt_code(x), nblk);  // f32 input: + the rounding-remainder rows
+    Tensor ws = at::empty({2, (int64_t)prows, C}, fopt);
+    Tensor fws = at::empty({tbamd::colsum_workspace(prows, C)}, x.options().dtype(at::kDouble));
     tbamd::bn_forward_train(dt_code(x), x.data_ptr(), M, C, g, b, fptr_mut(running_mean), fptr_mut(running_var),
                             nbt_ptr(num_batches_tracked), (float)momentum, (float)eps, ws[0].data_ptr<float>(),
                             ws[1].data_ptr<float>(), nblk, fws.data_ptr<double>(), mean, invstd, scale, shift, st);
@@ -543,6 +545,17 @@ void register_norm(pybind11::module& m) {
         py::arg("residual"), py::arg("act"), py::arg("slope"), py::arg("num_batches_tracked") = py::none(),
         py::arg("want_mask") = false, py::arg("res_scale") = py::none(), py::arg("res_shift") = py::none());
   m.def("bn_stats", &bn_stats);
+  m.def(
+      "norm_partial_blocks",
+      [](int64_t M, int64_t C, int64_t S) {
+        TORCH_CHECK(M > 0 && C > 0 && S > 0, "norm_partial_blocks: M, C, S > 0");
+        return (int64_t)tbamd::norm_partial_blocks(M, (int)C, (int)S);
+      },
+      py::arg("M"), py::arg("C"), py::arg("S") = 1,
+      "Read-only: the number of partial-sum rows (row blocks, gridDim.x) the statistics and backward "
+      "reduction passes write for M rows of C channels per sample and S samples (S = 1: BatchNorm; "
+      "S = N: GroupNorm / InstanceNorm).  More than 32 rows puts the BatchNorm column-sum finalize "
+      "on its multi-slice ticket path.");
   m.def("bn_act_maxpool", &bn_act_maxpool);
   m.def("maxpool_backward", &maxpool_backward);
   m.def("bn_backward_pool", &bn_backward_pool, py::arg("dy"), py::arg("idx"), py::arg("x"), py::arg("N"),

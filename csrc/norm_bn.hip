@@ -9,13 +9,14 @@
 //
 // The activation tensor is viewed as [M, C] (M = N*H*W, channels innermost).
 // Every pass streams 16 B per lane (8 channels); per-channel reductions are
-// shifted sums in f32 per workgroup, merged in f64 by the finalize kernels,
-// so the result is deterministic (no float atomics).
+// shifted sums in f32 per workgroup (f64 for f32 I/O, bn_acc_t), merged in f64 by the
+// finalize kernels, so the result is deterministic (no float atomics).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
 #include <stdexcept>
+#include <type_traits>
 
 #include "common.h"
 #include "tbamd.h"
@@ -23,6 +24,12 @@
 namespace tbamd {
 
 constexpr int kBnThreads = 256;
+
+// Accumulator of the per-workgroup reductions: f32 for the 16-bit I/O types, f64 for f32 I/O, whose
+// outputs resolve the rounding of a 256-lane f32 accumulation (tests/test_gpu_norm_f64.py).  The
+// partial rows stay f32 either way.
+template <int DT>
+using bn_acc_t = std::conditional_t<DT == kF32, double, float>;
 constexpr int kGroupsPerTile = 64;  // channel groups (of VEC channels) per workgroup tile
 
 struct BnGeom {
@@ -42,10 +49,14 @@ __host__ __device__ inline BnGeom bn_geom(int C, int VEC) {
 // forward statistics: per workgroup shifted sums  S = Σ(x - s), Q = Σ(x - s)^2
 // shift s = x[0, c] keeps the f32 sums well conditioned when |mean| >> std.
 // grid = (nblk, ceil(G / 64)); partials laid out [nblk][C].
+// lo_rows (f32 I/O BatchNorm): nblk further rows hold what the f32 rounding of each partial dropped
+// (the f64 accumulator minus its f32 value).  The finalize sums every row in f64, so the partials
+// count to ~48 bits: one f32 rounding of Q costs the variance 2^-24 (1 + D^2 / var), D the distance
+// of row 0 from the mean, which reached invstd -- and through it y and dx -- at 5e-7.
 template <int DT, int VEC>
 __global__ __launch_bounds__(kBnThreads) void bn_stats_partial_k(
     const storage_t<DT>* __restrict__ x, int64_t M, int C, int64_t rows_per_blk,
-    float* __restrict__ psum, float* __restrict__ psq) {
+    float* __restrict__ psum, float* __restrict__ psq, int lo_rows) {
   const BnGeom g = bn_geom(C, VEC);
   // blockIdx.z = sample (GroupNorm / InstanceNorm statistics); BN uses one "sample"
   x += (int64_t)blockIdx.z * M * C;
@@ -55,11 +66,13 @@ __global__ __launch_bounds__(kBnThreads) void bn_stats_partial_k(
   const int gl = tid % g.GT, rl = tid / g.GT;
   const int grp = blockIdx.y * kGroupsPerTile + gl;
   const bool active = rl < g.rpp && gl < g.GT && grp < g.G;
-  __shared__ float sm_s[kBnThreads * VEC];
-  __shared__ float sm_q[kBnThreads * VEC];
-  float s[VEC], q[VEC], sh[VEC];
+  using acc_t = bn_acc_t<DT>;
+  __shared__ acc_t sm_s[kBnThreads * VEC];
+  __shared__ acc_t sm_q[kBnThreads * VEC];
+  acc_t s[VEC], q[VEC];
+  float sh[VEC];
 #pragma unroll
-  for (int i = 0; i < VEC; ++i) s[i] = q[i] = 0.f;
+  for (int i = 0; i < VEC; ++i) s[i] = q[i] = 0;
   if (active) {
     const int c0 = grp * VEC;
     load_vec<DT, VEC>(x + c0, sh);
@@ -76,7 +89,8 @@ __global__ __launch_bounds__(kBnThreads) void bn_stats_partial_k(
       load_vec<DT, VEC>(x + (r + 3 * g.rpp) * C + c0, v3);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
-        float d0 = v0[i] - sh[i], d1 = v1[i] - sh[i], d2 = v2[i] - sh[i], d3 = v3[i] - sh[i];
+        const acc_t a = sh[i];
+        acc_t d0 = v0[i] - a, d1 = v1[i] - a, d2 = v2[i] - a, d3 = v3[i] - a;
         s[i] += (d0 + d1) + (d2 + d3);
         q[i] += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
       }
@@ -86,7 +100,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_stats_partial_k(
       load_vec<DT, VEC>(x + r * C + c0, v);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
-        float d = v[i] - sh[i];
+        acc_t d = v[i] - (acc_t)sh[i];
         s[i] += d;
         q[i] += d * d;
       }
@@ -104,15 +118,21 @@ __global__ __launch_bounds__(kBnThreads) void bn_stats_partial_k(
     const int pg = p / VEC, pe = p % VEC;
     const int cgrp = blockIdx.y * kGroupsPerTile + pg;
     if (cgrp >= g.G) continue;
-    float ts = 0.f, tq = 0.f;
+    acc_t ts = 0, tq = 0;
     for (int rr = 0; rr < g.rpp; ++rr) {
       const int t = rr * g.GT + pg;
       ts += sm_s[t * VEC + pe];
       tq += sm_q[t * VEC + pe];
     }
     const int c = cgrp * VEC + pe;
-    psum[(int64_t)blockIdx.x * C + c] = ts;
-    psq[(int64_t)blockIdx.x * C + c] = tq;
+    psum[(int64_t)blockIdx.x * C + c] = (float)ts;
+    psq[(int64_t)blockIdx.x * C + c] = (float)tq;
+    if constexpr (DT == kF32) {
+      if (lo_rows) {
+        psum[(int64_t)(blockIdx.x + gridDim.x) * C + c] = (float)(ts - (double)(float)ts);
+        psq[(int64_t)(blockIdx.x + gridDim.x) * C + c] = (float)(tq - (double)(float)tq);
+      }
+    }
   }
 }
 
@@ -413,7 +433,11 @@ static void launch_colsum_fin(const float* pa, const float* pb, int64_t rs, int 
 // training statistics -> mean / invstd (saved for backward), fused affine
 // scale / shift, running stats (unbiased variance, torch semantics) and the
 // num_batches_tracked counter.  (s, q) are sums of (x - shift) and its square.
-template <int DT>
+// PRECISE (the f32 I/O statistics pass): scale and shift are formed in f64 and rounded once, the
+// shift from the ROUNDED scale, so y = fma(x, scale, shift) carries the scale's rounding only on
+// (x - mean) and stays within a few ulp of an f32 evaluation that subtracts the mean first
+// (tests/test_gpu_norm_f64.py).  The 16-bit and conv-epilogue paths keep the f32 products.
+template <int DT, bool PRECISE = false>
 struct StatsFin {
   int64_t M;
   const storage_t<DT>* shift_x;  // row 0 of x: per-channel shift of the partial sums (nullptr: raw sums)
@@ -434,9 +458,16 @@ struct StatsFin {
     invstd_out[c] = invstd;
     const float gm = gamma ? gamma[c] : 1.f;
     const float bt = beta ? beta[c] : 0.f;
-    const float sc = gm * invstd;
-    scale_out[c] = sc;
-    shift_out[c] = bt - mean * sc;
+    if constexpr (PRECISE) {
+      const double meand = (shift_x ? (double)Elem<DT>::ld(shift_x, c) : 0.0) + md;
+      const float sc = (float)((double)gm / sqrt(var + (double)eps));
+      scale_out[c] = sc;
+      shift_out[c] = (float)((double)bt - meand * (double)sc);
+    } else {
+      const float sc = gm * invstd;
+      scale_out[c] = sc;
+      shift_out[c] = bt - mean * sc;
+    }
     if (running_mean) {
       const double unb = M > 1 ? var * (double)M / (double)(M - 1) : var;
       running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
@@ -459,6 +490,21 @@ __global__ void bn_eval_coeffs_k(int C, const float* __restrict__ gamma, const f
   invstd_out[c] = invstd;
   scale_out[c] = gm * invstd;
   shift_out[c] = bt - rm[c] * gm * invstd;
+}
+
+// Activations of the streaming kernels below.  f32 I/O takes GELU from erfcf / expf: the shared
+// gelu_f / gelu_grad (common.h) approximate erf to 1.5e-7 absolute, below a bf16 or f16 rounding
+// but several f32 ulp of a channel whose outputs are small (tests/test_gpu_norm_f64.py).
+template <int DT, int ACT>
+__device__ __forceinline__ float nact_fwd(float z, float slope) {
+  if constexpr (DT == kF32 && ACT == kActGELU) return 0.5f * z * erfcf(-0.70710678118654752f * z);
+  else return act_fwd<ACT>(z, slope);
+}
+template <int DT, int ACT>
+__device__ __forceinline__ float nact_bwd(float z, float slope) {
+  if constexpr (DT == kF32 && ACT == kActGELU)
+    return 0.5f * erfcf(-0.70710678118654752f * z) + z * 0.3989422804014327f * expf(-0.5f * z * z);
+  else return act_bwd<ACT>(z, slope);
 }
 
 // ---------------------------------------------------------------------------
@@ -539,8 +585,8 @@ __global__ __launch_bounds__(kBnThreads) void bn_apply_k(const storage_t<DT>* __
         z0 += q0[i];
         z1 += q1[i];
       }
-      v0[i] = act_fwd<ACT>(z0, slope);
-      v1[i] = act_fwd<ACT>(z1, slope);
+      v0[i] = nact_fwd<DT, ACT>(z0, slope);
+      v1[i] = nact_fwd<DT, ACT>(z1, slope);
     }
     store_vec<DT, VEC>(y + o0, v0);
     store_vec<DT, VEC>(y + o1, v1);
@@ -568,7 +614,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_apply_k(const storage_t<DT>* __
     for (int i = 0; i < VEC; ++i) {
       float z0 = __builtin_fmaf(v0[i], sc[i], sf[i]);
       if constexpr (RES) z0 += q0[i];
-      v0[i] = act_fwd<ACT>(z0, slope);
+      v0[i] = nact_fwd<DT, ACT>(z0, slope);
     }
     store_vec<DT, VEC>(y + o0, v0);
     if constexpr (MASK) {
@@ -616,11 +662,12 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_partial_k(
   const int gl = tid % g.GT, rl = tid / g.GT;
   const int grp = blockIdx.y * kGroupsPerTile + gl;
   const bool active = rl < g.rpp && gl < g.GT && grp < g.G;
-  __shared__ float sm_a[kBnThreads * VEC];
-  __shared__ float sm_b[kBnThreads * VEC];
-  float sdb[VEC], sdg[VEC];
+  using acc_t = bn_acc_t<DT>;
+  __shared__ acc_t sm_a[kBnThreads * VEC];
+  __shared__ acc_t sm_b[kBnThreads * VEC];
+  acc_t sdb[VEC], sdg[VEC];
 #pragma unroll
-  for (int i = 0; i < VEC; ++i) sdb[i] = sdg[i] = 0.f;
+  for (int i = 0; i < VEC; ++i) sdb[i] = sdg[i] = 0;
   if (active) {
     const int c0 = grp * VEC;
     float mu[VEC], sc[VEC], sf[VEC];
@@ -661,14 +708,14 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_partial_k(
         for (int i = 0; i < VEC; ++i) {
           float z = __builtin_fmaf(vx[i], sc[i], sf[i]);
           if constexpr (RES) z += vr[i];
-          dz[i] = vdy[i] * act_bwd<ACT>(z, slope);
+          dz[i] = vdy[i] * nact_bwd<DT, ACT>(z, slope);
         }
       }
       if constexpr (RES && !MASKIN) store_vec<DT, VEC>(dres + off, dz);
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
         sdb[i] += dz[i];
-        sdg[i] += dz[i] * (vx[i] - mu[i]);
+        sdg[i] += (acc_t)dz[i] * ((acc_t)vx[i] - (acc_t)mu[i]);
       }
     }
   }
@@ -683,15 +730,15 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_partial_k(
     const int pg = p / VEC, pe = p % VEC;
     const int cgrp = blockIdx.y * kGroupsPerTile + pg;
     if (cgrp >= g.G) continue;
-    float ta = 0.f, tb = 0.f;
+    acc_t ta = 0, tb = 0;
     for (int rr = 0; rr < g.rpp; ++rr) {
       const int t = rr * g.GT + pg;
       ta += sm_a[t * VEC + pe];
       tb += sm_b[t * VEC + pe];
     }
     const int c = cgrp * VEC + pe;
-    pdb[(int64_t)blockIdx.x * C + c] = ta;
-    pdg[(int64_t)blockIdx.x * C + c] = tb;
+    pdb[(int64_t)blockIdx.x * C + c] = (float)ta;
+    pdg[(int64_t)blockIdx.x * C + c] = (float)tb;
   }
 }
 
@@ -799,7 +846,7 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_apply_k(
         for (int k = 0; k < VEC; ++k) {
           float z = __builtin_fmaf(vx[k], sc[k], sf[k]);
           if constexpr (RES) z += vr[k];
-          dz[k] = vdy[k] * act_bwd<ACT>(z, slope);
+          dz[k] = vdy[k] * nact_bwd<DT, ACT>(z, slope);
         }
       }
     }
@@ -929,15 +976,18 @@ __global__ __launch_bounds__(256) void gn_stats_finalize_k(
   const double mean = red[0][0] / cnt;
   double var = red[1][0] / cnt - mean * mean;
   if (var < 0.0) var = 0.0;
-  const float invstd = (float)(1.0 / sqrt(var + (double)eps));
+  const double invstdd = 1.0 / sqrt(var + (double)eps);
+  const float invstd = (float)invstdd;
   for (int cc = threadIdx.x; cc < Cg; cc += 256) {
     const int c = c0 + cc;
     const int64_t o = (int64_t)n * C + c;
     const float gm = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
     mean_out[o] = (float)mean;
     invstd_out[o] = invstd;
-    scale_out[o] = gm * invstd;
-    shift_out[o] = bt - (float)mean * gm * invstd;
+    // formed in f64, rounded once; the shift from the rounded scale (see StatsFin PRECISE)
+    const float sc = (float)((double)gm * invstdd);
+    scale_out[o] = sc;
+    shift_out[o] = (float)((double)bt - mean * (double)sc);
   }
 }
 
@@ -1024,6 +1074,9 @@ static int bn_nblk(int64_t M, int C, int VEC, int ytiles, int S) {
 
 int bn_partial_blocks(int64_t M, int C) { return norm_partial_blocks(M, C, 1); }
 
+// rows of each statistics partial array bn_forward_train writes for `nblk` row blocks
+int bn_stats_rows(int dt, int nblk) { return dt == kF32 ? 2 * nblk : nblk; }
+
 int norm_partial_blocks(int64_t M, int C, int S) {
   const int VEC = (C % 8 == 0) ? 8 : 1;
   const BnGeom g = bn_geom(C, VEC);
@@ -1079,16 +1132,16 @@ static int bn_dsp_blocks(int64_t M, int C, int ytiles) {
 
 template <int DT>
 static void launch_stats_partial(const void* x, int S, int64_t M, int C, int nblk, float* psum, float* psq,
-                                 hipStream_t st) {
+                                 hipStream_t st, int lo_rows = 0) {
   using T = storage_t<DT>;
   const bool vec = (C % 8 == 0);
   const BnGeom g = bn_geom(C, vec ? 8 : 1);
   dim3 grid(nblk, cdiv(g.G, kGroupsPerTile), S);
   const int64_t rpb = (M + nblk - 1) / nblk;
   if (vec)
-    bn_stats_partial_k<DT, 8><<<grid, kBnThreads, 0, st>>>((const T*)x, M, C, rpb, psum, psq);
+    bn_stats_partial_k<DT, 8><<<grid, kBnThreads, 0, st>>>((const T*)x, M, C, rpb, psum, psq, lo_rows);
   else
-    bn_stats_partial_k<DT, 1><<<grid, kBnThreads, 0, st>>>((const T*)x, M, C, rpb, psum, psq);
+    bn_stats_partial_k<DT, 1><<<grid, kBnThreads, 0, st>>>((const T*)x, M, C, rpb, psum, psq, lo_rows);
 }
 
 void bn_forward_train(int dt, const void* x, int64_t M, int C, const float* gamma, const float* beta,
@@ -1097,10 +1150,12 @@ void bn_forward_train(int dt, const void* x, int64_t M, int C, const float* gamm
                       float* shift, hipStream_t st) {
   TBAMD_DISPATCH_DT(dt, DT, {
     using T = storage_t<DT>;
-    launch_stats_partial<DT>(x, 1, M, C, nblk, psum, psq, st);
-    StatsFin<DT> fin{M, (const T*)x, gamma, beta, running_mean, running_var, nbt, momentum, eps,
-                     mean, invstd, scale, shift};
-    launch_colsum_fin(psum, psq, C, nblk, C, fin_ws, fin, st);
+    // f32 I/O: psum / psq hold 2 * nblk rows (bn_stats_rows), the second half the rounding remainders
+    constexpr int kLo = DT == kF32 ? 1 : 0;
+    launch_stats_partial<DT>(x, 1, M, C, nblk, psum, psq, st, kLo);
+    StatsFin<DT, DT == kF32> fin{M, (const T*)x, gamma, beta, running_mean, running_var, nbt, momentum, eps,
+                                 mean, invstd, scale, shift};
+    launch_colsum_fin(psum, psq, C, nblk * (1 + kLo), C, fin_ws, fin, st);
   });
 }
 
@@ -1249,6 +1304,22 @@ static void launch_bwd_apply(const void* dy, const void* y, const void* x, const
       tb_launch_ev(bn_bwd_apply_k<DT, 8, ACT, true, false, true>, agrid, dim3(kBnThreads), 0, st,
                    tdy, ty, tx, tres, nullptr, scale, shift, coef, M, C, rpb, slope, (T*)dx, maskin, (T*)dzout,
                    g_bn_rev);
+      return;
+    }
+  }
+  // dres holds dz rounded to the I/O type: exact in f32 and for ReLU / no activation (dz is dy or 0),
+  // a second rounding under dx for the other activations in bf16 / f16 -- those recompute dz from
+  // (dy, x, res) in f32 instead of reading it back
+  constexpr bool kDzExact = DT == kF32 || ACT == kActReLU || ACT == kActNone;
+  if constexpr (!kDzExact) {
+    if (dres && res) {
+      if (vec)
+        tb_launch_ev(bn_bwd_apply_k<DT, 8, ACT, true, false>, agrid, dim3(kBnThreads), 0, st,
+                     tdy, ty, tx, tres, nullptr, scale, shift, coef, M, C, rpb, slope, (T*)dx, nullptr, nullptr,
+                     g_bn_rev);
+      else
+        tb_launch_ev(bn_bwd_apply_k<DT, 1, ACT, true, false>, agrid, dim3(kBnThreads), 0, st,
+                     tdy, ty, tx, tres, nullptr, scale, shift, coef, M, C, rpb, slope, (T*)dx, nullptr, nullptr, 0);
       return;
     }
   }

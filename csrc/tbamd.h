@@ -45,6 +45,7 @@ void stream_wait_stop_event(hipStream_t st, int64_t id);
 
 // ---- BatchNorm (NHWC, [M, C]) ----
 int bn_partial_blocks(int64_t M, int C);
+int bn_stats_rows(int dt, int nblk);
 void bn_forward_train(int dt, const void* x, int64_t M, int C, const float* gamma, const float* beta,
                       float* running_mean, float* running_var, int64_t* nbt, float momentum, float eps,
                       float* psum, float* psq, int nblk, double* fin_ws, float* mean, float* invstd, float* scale,
