@@ -72,7 +72,7 @@ Tensor conv_any_wgrad(const Tensor& dy_, const Tensor& x_, int64_t R, int64_t S,
 // the taps that meet real dy pixels).  Zero padding without upsampling writes dX directly
 // (output grid H x W, padding R-1-pad); reflect / upsampled inputs go through the padded
 // virtual grid and the fold.  `wt`: the flipped transpose [C][R][S][K] when the caller
-// keeps one cached (ops/conv.py _flipped), else built here.
+// keeps one cached (ops/flipcache.py _flipped), else built here.
 Tensor conv_any_dgrad(const Tensor& dy_, const Tensor& w_, int64_t H, int64_t W, int64_t stride, int64_t pad,
                       int64_t up, bool reflect, const optional<Tensor>& wt_) {
   const at::DeviceGuard guard = on_device_of(dy_, "dy");

@@ -28,7 +28,7 @@
 //
 // Requirements (checked by the host): C % 64 == 0, K % BM == 0, bf16 data.
 // dgrad of a stride-1 conv is the same kernel on dY with flipped/transposed
-// weights (see ops/conv.py).
+// weights (see ops/conv.py, ops/flipcache.py).
 #include <cstdlib>
 #include <mutex>
 #include <stdexcept>

@@ -23,7 +23,7 @@
 //   D[k][pixel] = W[k][(r,s,c)] . Xcol[(r,s,c)][pixel]  (A = weights, B = activations)
 //
 // Requirements (host-checked): C % 64 == 0, K % BM == 0, bf16.  A stride-1 input gradient is the
-// same kernel on dY with flipped / transposed weights (ops/conv.py).
+// same kernel on dY with flipped / transposed weights (ops/conv.py, ops/flipcache.py).
 #include <cstdlib>
 #include <stdexcept>
 #include <string>

@@ -99,7 +99,7 @@ ONLY = [v for v in os.environ.get("VARIANTS", "").split(",") if v]  # subset (fp
 
 def variants(base, data):
     """(name, loss curve) of every variant on one set of batches."""
-    from torchbooster_amd.ops import conv as nconv
+    from torchbooster_amd.ops import conv_route as nconv  # (owns _NO_MIOPEN and _FORCE)
 
     res = {}
     if ONLY:

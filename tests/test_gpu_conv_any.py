@@ -200,6 +200,7 @@ def test_conv_narrow_is_routed_for_the_style_heads():
     """The autotuner offers the narrow kernel for the decoder RGB head and it wins (the shipped
     route table has no entry for this key, so it is timed here)."""
     from torchbooster_amd.ops import conv as CV
+    from torchbooster_amd.ops import conv_route
 
     x = torch.randn(8, 32, 128, 128, device="cuda").to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
     w = (torch.randn(3, 32, 9, 9, device="cuda") * 0.05).to(torch.bfloat16).contiguous(
@@ -208,7 +209,7 @@ def test_conv_narrow_is_routed_for_the_style_heads():
     ref = _ref(x.float(), w.float(), None, 1, 4, 1, True)
     assert ((y.float() - ref).abs().max() / ref.abs().max()).item() < 1e-2
     key = ("fwd", "any", tuple(x.shape), tuple(w.shape), str(x.dtype), 1, 4, 1, True, False)
-    if CV._AUTOTUNE and not CV._DISABLE:
+    if conv_route._AUTOTUNE and not conv_route._DISABLE:
         assert CV.autotune_table().get(key) == "narrow", CV.autotune_table().get(key)
 
 

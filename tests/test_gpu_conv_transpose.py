@@ -12,6 +12,7 @@ if not torch.cuda.is_available():  # pragma: no cover - CPU collection
 
 from torchbooster_amd.ops import _ext  # noqa: E402
 from torchbooster_amd.ops import conv as nconv  # noqa: E402
+from torchbooster_amd.ops import conv_route  # noqa: E402
 
 DEV = "cuda"
 
@@ -61,12 +62,25 @@ def test_dcgan_generator_native_matches_miopen(monkeypatch):
     torch.manual_seed(0)
     G = DCGANGenerator(128, 64).to(DEV).to(memory_format=torch.channels_last).to(torch.bfloat16)
     z = torch.randn(4, 128, device=DEV, dtype=torch.bfloat16)
+    gates = []  # per transposed conv called: does either native family take it?
+
+    def gate(m, args):
+        a = (args[0], m.weight, m.stride, m.padding, m.output_padding, m.dilation, m.groups)
+        gates.append(nconv.conv_transpose_supported(*a) or nconv.conv_transpose_any_supported(*a))
+
+    convts = [m for m in G.modules() if isinstance(m, nconv.ConvTranspose2d)]
+    hooks = [m.register_forward_pre_hook(gate) for m in convts]
     y = G(z)
+    assert len(gates) == len(convts) > 0 and all(gates)  # the native leg is native
     y.float().square().mean().backward()
     g_nat = [p.grad.clone() for p in G.parameters()]
     G.zero_grad(set_to_none=True)
-    monkeypatch.setattr(nconv, "_DISABLE", True)  # every ConvTranspose2d on MIOpen
+    monkeypatch.setattr(conv_route, "_DISABLE", True)  # every ConvTranspose2d on MIOpen
+    del gates[:]
     y2 = G(z)
+    assert len(gates) == len(convts) and not any(gates)  # ... and the MIOpen leg is not
+    for h in hooks:
+        h.remove()
     y2.float().square().mean().backward()
     assert _rel(y, y2) < 2e-2
     for a, b in zip(g_nat, [p.grad for p in G.parameters()]):

@@ -56,10 +56,10 @@ def test_strided_conv_directions_match_fp32(C, K, R, st, pad, H):
 
 def test_strided_convs_train_without_miopen():
     from torchbooster_amd.nativize import nativize
-    from torchbooster_amd.ops import conv as CV
+    from torchbooster_amd.ops import conv_route
     from torchbooster_amd.ops.optim import FusedAdamW
 
-    assert CV._NO_MIOPEN  # the default
+    assert conv_route._NO_MIOPEN  # the default
     torch.manual_seed(0)
     ref = _model().cuda().to(memory_format=torch.channels_last)
     stock16 = copy.deepcopy(ref).to(torch.bfloat16)

@@ -1,6 +1,6 @@
 """One routing decision for every rank of a job.
 
-The conv router (ops/conv.py ``_route``) and the GEMM tile tuner (ops/gemm.py ``_tuned``) pick a
+The conv router (ops/conv_route.py ``_route``) and the GEMM tile tuner (ops/gemm.py ``_tuned``) pick a
 kernel per shape by timing the candidates on the first call.  Timed on each rank separately, two
 ranks of one data-parallel job can pick different kernels for the same layer (box-to-box timing
 spread is up to 25 %, profiles/r02_convstudy): the job then runs at the pace of its slowest pick

@@ -171,7 +171,7 @@ def slot_alias(slot: torch.Tensor) -> torch.Tensor:
 
 # Parameters rewritten in place by a native kernel (the fused optimizers) keep their
 # autograd version counter; caches of values derived from parameters (the flipped
-# conv weights of ops/conv.py) key on this generation as well.
+# conv weights of ops/flipcache.py) key on this generation as well.
 _PARAM_GEN = [0]
 
 
@@ -184,7 +184,7 @@ def param_generation() -> int:
 
 
 # Work derived from parameters that is best done right after an optimizer update, on the compute
-# stream behind it (ops/conv.py: the flipped dgrad weights of every trainable conv), instead of at
+# stream behind it (ops/flipcache.py: the flipped dgrad weights of every trainable conv), instead of at
 # first use inside the next backward -- there the host-side refresh left the GPU idle (~0.17 ms
 # per ResNet-50 step between the first BN backward and the first dgrad, profiles/r04_open).
 _UPDATE_HOOKS: list = []

@@ -8,16 +8,19 @@ routed independently:
 
 * forward — csrc/conv.hip (implicit GEMM, BN statistics fused in the epilogue);
 * input grad — for stride 1 the same forward kernel on dY with the flipped,
-  transposed weights (``conv_flip_weight``) and padding R-1-pad; strided input
-  grads use MIOpen;
+  transposed weights (ops/flipcache.py) and padding R-1-pad; stride 2 / 3 as
+  stride^2 phase classes of stride-1 sub-convolutions on that kernel
+  (``conv_dgrad_s2``); any other geometry on the generic input gradient
+  (csrc/conv_any.hip);
 * weight grad — csrc/conv_wgrad.hip (split-reduction MFMA with transposing LDS
   reads and a deterministic partial-sum reduction).
 
-Routing is autotuned per (direction, shape) the first time a shape is seen
-(like ``cudnn.benchmark``: both candidates are timed with HIP events, the
-faster one is cached — see :func:`autotune_table`).  ``TBAMD_CONV_AUTOTUNE=0``
-always takes the native kernel; ``TBAMD_CONV_{FWD,DGRAD,WGRAD}=miopen|native``
-pins one direction; ``TBAMD_NATIVE_CONV=0`` disables the native path entirely.
+Each direction's candidates go through the per-shape autotuner of
+ops/conv_route.py (``_route``; the shipped table, the ``TBAMD_CONV_*`` switches
+and ``TBAMD_NATIVE_CONV=0`` live there).  MIOpen is a timed candidate only with
+``TBAMD_CONV_NO_MIOPEN=0``.  The generic family (``conv2d_any``, ``_ConvAnyFn``,
+``_ConvTAnyFn``) stays in this module: it shares the gates, the bias gradient
+and the flags below with the 64-channel path.
 
 ``passthrough=True`` additionally returns the input ``x`` as an alias whose
 gradient is folded into this conv's input gradient by the dgrad epilogue
@@ -33,9 +36,9 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, Dict, Optional, Tuple
 
-from torchbooster_amd.ops import _agree
+from torchbooster_amd.ops import conv_route as RT
 from torchbooster_amd.ops import convgemm as CG
 from torchbooster_amd.ops import streams
 
@@ -45,34 +48,22 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from torchbooster_amd.ops._ext import native, slot_alias, slot_in_use, take_slot, use_native
+# re-exported: this module stays the import point for the tuner's and the flip cache's names.  The
+# tuner's mutable flags (_DISABLE, _AUTOTUNE, _NO_MIOPEN) are NOT copied here: read them as RT.<flag>
+from torchbooster_amd.ops.conv_route import (_FORCE, _ROUTE_NAMES, _route, autotune_table,  # noqa: F401
+                                             load_routes, save_routes)
+from torchbooster_amd.ops.flipcache import _FLIP_CACHE, _FlipCache, _flipped, transposed_linear_weight  # noqa: F401
 
 __all__ = ["conv2d_any", "conv_any_supported", "PadConv2d", "conv2d", "conv2d_bn_stats", "conv_stem", "stem_supported", "native_supported", "conv2d_forward", "conv2d_wgrad", "autotune_table",
            "Conv2d", "ConvTranspose2d", "conv_transpose2d", "conv_transpose_supported"]
 
-_DISABLE = os.environ.get("TBAMD_NATIVE_CONV", "1") == "0"
 # DIAGNOSTIC ONLY (interference studies, never a benchmark number): skip the conv weight-gradient
 # kernels of the side-stream path, leaving the gradient slots unwritten
 _DIAG_SKIP_WGRAD = os.environ.get("TBAMD_DIAG_SKIP_WGRAD", "0") == "1"
 # transposed convs only (A/B against MIOpen's conv_transpose2d)
 _DISABLE_T = os.environ.get("TBAMD_NATIVE_CONVT", "1") == "0"
-_AUTOTUNE = os.environ.get("TBAMD_CONV_AUTOTUNE", "1") != "0"
-# one stderr line per autotune decision (long first steps then show progress)
-_TUNE_LOG = os.environ.get("TBAMD_TUNE_LOG", "0") == "1"
-_FORCE = {d: os.environ.get(f"TBAMD_CONV_{d.upper()}", "") for d in ("fwd", "dgrad", "wgrad")}
 # HBM bytes/s used to price the extra BN statistics pass a MIOpen forward needs
 _STATS_PASS_BW = 4.0e12
-
-_CHOICE: Dict[tuple, str] = {}
-
-
-def _tuplify(v):
-    return tuple(_tuplify(x) for x in v) if isinstance(v, list) else v
-
-
-# every route a table row may name (_route_choice candidates)
-_ROUTE_NAMES = ("native", "miopen", "gemm", "native64", "narrow", "tinyc", "im2col", "split32", "narrow32", "tiny32",
-                "tinyhalo", "splitk", "tinyin", "big256x256", "big256x128", "big128x256", "big128x128",
-                "big256x256m32", "big256x128m32", "big128x256m32", "big128x128m32")
 
 # big-tile candidates of the implicit-GEMM forward / stride-1 input gradient (csrc/conv_big.hip: 8
 # waves, one workgroup per CU, (channel x pixel) tiles below, 16x16x32 MFMA, 2-4 LDS stages).  The
@@ -88,11 +79,6 @@ _BIG_CFGS = (("big256x256", (256, 256, 16, 2)), ("big256x128", (256, 128, 16, 3)
 # (the 64-channel tiles 64x256 / MF 16 and 32 lose to the shipped route on every ResNet-50 shape by
 # 15-70 %, profiles/r06_m32/retime64_log.txt: not candidates)
 _BIG_CODES: Dict[str, int] = {}
-# tuning aid: TBAMD_CONV_RETIME=name,name,... re-times every decided route that has one of these
-# candidates against them (kept only where one is faster by 3 %); with TBAMD_CONV_SAVE it writes the
-# table to merge (scripts/merge_routes.py)
-_RETIME = tuple(n for n in os.environ.get("TBAMD_CONV_RETIME", "").split(",") if n)
-_RETIMED: set = set()
 
 
 def _big_cands(K: int, C: int, make: Callable[[int], Callable[[], object]]) -> list:
@@ -110,49 +96,6 @@ def _big_cands(K: int, C: int, make: Callable[[int], Callable[[], object]]) -> l
     return out
 
 
-def load_routes(path: Optional[str] = None) -> int:
-    """Seed the autotune table from a routes file (like a cuDNN/MIOpen find-db:
-    decisions measured once on this GPU model, so a fresh process does not pay
-    ~3 minutes of first-step timing — mostly MIOpen find of the losing
-    candidates).  ``TBAMD_CONV_ROUTES`` overrides the shipped gfx950 file;
-    ``TBAMD_CONV_ROUTES=none`` disables it.  Returns the number of routes."""
-    import json
-
-    path = path or os.environ.get("TBAMD_CONV_ROUTES") or os.path.join(os.path.dirname(__file__),
-                                                                        "conv_routes_gfx950.json")
-    if path == "none" or not os.path.exists(path):
-        return 0
-    with open(path) as f:
-        data = json.load(f)
-    n = 0
-    for key, name in data.get("routes", []):
-        if name in _ROUTE_NAMES:
-            _CHOICE.setdefault(_tuplify(key), name)
-            n += 1
-    return n
-
-
-def save_routes(path: str) -> None:
-    """Write the current autotune table in :func:`load_routes` format."""
-    import json
-
-    rows = [json.dumps([list(_listify(k)), v]) for k, v in sorted(_CHOICE.items(), key=str)]
-    with open(path, "w") as f:
-        f.write('{\n"device": "gfx950",\n"routes": [\n' + ",\n".join(rows) + "\n]}\n")
-
-
-def _listify(v):
-    return [_listify(x) for x in v] if isinstance(v, tuple) else v
-
-
-def autotune_table() -> Dict[tuple, str]:
-    """(direction, shapes...) -> "native" | "miopen" decided so far."""
-    return dict(_CHOICE)
-
-
-if _AUTOTUNE and not _DISABLE:
-    load_routes()
-
 def _apply_occupancy_env() -> None:
     """A/B knobs: TBAMD_CONV_OCC / TBAMD_WGRAD_OCC = workgroups per CU the single-stage forward /
     weight-gradient kernels are compiled for (2, 3, 4; defaults 4 / 3)."""
@@ -167,12 +110,6 @@ def _apply_occupancy_env() -> None:
 
 _apply_occupancy_env()
 
-if os.environ.get("TBAMD_CONV_SAVE"):
-    # collect this process's decisions for the shipped table (scripts/merge_routes.py)
-    import atexit
-
-    atexit.register(lambda: _CHOICE and save_routes(os.environ["TBAMD_CONV_SAVE"]))
-
 
 def _pair(v) -> int:
     if isinstance(v, (tuple, list)):
@@ -182,8 +119,13 @@ def _pair(v) -> int:
     return int(v)
 
 
+def _out_hw(h: int, w: int, R: int, S: int, stride: int, pad: int) -> Tuple[int, int]:
+    """Output height / width of an R x S conv on an h x w input."""
+    return (h + 2 * pad - R) // stride + 1, (w + 2 * pad - S) // stride + 1
+
+
 def native_supported(x: Tensor, w: Tensor, stride, padding, dilation=1, groups=1) -> bool:
-    if _DISABLE or not x.is_cuda or x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+    if RT._DISABLE or not x.is_cuda or x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
         return False
     if groups != 1 or _pair(dilation) != 1 or _pair(stride) < 1 or _pair(padding) < 0:
         return False
@@ -192,23 +134,6 @@ def native_supported(x: Tensor, w: Tensor, stride, padding, dilation=1, groups=1
     C, K = x.shape[1], w.shape[0]
     return C % 64 == 0 and K % 64 == 0
 
-
-def _time_ms(fn: Callable[[], object], reps: int = 3) -> float:
-    fn()  # warm (MIOpen runs its own find on first use)
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record()
-    for _ in range(reps):
-        fn()
-    e.record()
-    e.synchronize()
-    return s.elapsed_time(e) / reps
-
-
-# TBAMD_CONV_NO_MIOPEN (default 1): never route a conv direction to MIOpen -- every shape has a
-# native candidate (implicit GEMM, the phase-class strided input gradient, the generic / narrow /
-# tiny-channel families, im2col + GEMM), and no first-use MIOpen find is paid.  0: MIOpen is a
-# timed candidate again (taken only where it is clearly faster, _MIOPEN_MARGIN).
-_NO_MIOPEN = os.environ.get("TBAMD_CONV_NO_MIOPEN", "1") == "1"
 
 # fp32 convolutions: by default split-bf16 MFMA (three bf16 products, ~16 mantissa bits: finer than
 # the TF32 PyTorch's cuDNN path may use for fp32 convs by default).  IEEE fp32 when the process asks
@@ -233,93 +158,6 @@ def _sync_f32_mode() -> bool:
         native().conv_any_set_f32_split(not exact)
         _F32_SPLIT_STATE[0] = not exact
     return exact
-_MIOPEN_MARGIN = float(os.environ.get("TBAMD_CONV_MIOPEN_MARGIN", "0.05"))
-_MIOPEN_MARGIN_MS = float(os.environ.get("TBAMD_CONV_MIOPEN_MARGIN_MS", "0.005"))
-
-
-def _route(direction: str, key: tuple, cands: List[Tuple[str, Callable[[], object], float]]):
-    """Run the chosen candidate of ``cands`` [(name, fn, penalty_ms)]; the first
-    candidate is the default when autotuning is off or impossible."""
-    name = _route_choice(direction, key, cands)
-    for n, fn, _ in cands:
-        if n == name:
-            return fn()
-    raise RuntimeError(f"conv route {name} vanished")  # pragma: no cover
-
-
-def _route_choice(direction: str, key: tuple, cands: List[Tuple[str, Callable[[], object], float]]) -> str:
-    """The name of the candidate :func:`_route` runs (timing the candidates on first use)."""
-    forced = _FORCE[direction]
-    # deterministic mode (utils.seed / torch.use_deterministic_algorithms): MIOpen's split-K
-    # solvers accumulate with float atomics (bitwise run-to-run differences on the few-pixel
-    # shapes they win), every native route is fixed-order -- so native only
-    if (_NO_MIOPEN or torch.are_deterministic_algorithms_enabled()) and any(c[0] != "miopen" for c in cands):
-        cands = [c for c in cands if c[0] != "miopen"]
-    names = [c[0] for c in cands]
-    if forced in names:
-        return forced
-    if len(cands) == 1:
-        return names[0]
-    k = (direction,) + key
-    name = _CHOICE.get(k)
-    if name is not None and name not in names:  # a shipped / loaded route this process excludes
-        name = None
-    if (name is not None and _RETIME and k not in _RETIMED and not torch.cuda.is_current_stream_capturing()
-            and any(n in _RETIME for n in names)):
-        # tuning aid (_RETIME): the decided route against the named candidates only
-        _RETIMED.add(k)
-        times, cur = [], None
-        best_n, best_t = None, float("inf")
-        for n, fn, pen in cands:
-            if n != name and n not in _RETIME:
-                continue
-            try:
-                t = min(_time_ms(fn), _time_ms(fn)) + pen
-            except RuntimeError:
-                continue
-            times.append(f"{n}={t:.3f}ms")
-            if n == name:
-                cur = t
-            elif t < best_t:
-                best_n, best_t = n, t
-        if cur is not None and best_n is not None and best_t < cur * 0.97:
-            name = best_n
-            _CHOICE[k] = name
-        if _TUNE_LOG:
-            import sys
-
-            print(f"[conv-retime] {k} -> {name} ({', '.join(times)})", file=sys.stderr, flush=True)
-    if name is None:
-        if not _AUTOTUNE or torch.cuda.is_current_stream_capturing():
-            return names[0]
-        times = []
-        name = _agree.shared("conv", k)  # rank 0's decision (multi-rank jobs)
-        if name not in names:
-            best, name = float("inf"), names[0]
-            mio = float("inf")
-            for n, fn, pen in cands:
-                try:
-                    t = _time_ms(fn) + pen
-                except RuntimeError as e:  # a candidate that cannot run this shape (e.g. an ATen
-                    times.append(f"{n}=failed({str(e)[:60]})")  # 32-bit-index limit) drops out
-                    continue
-                times.append(f"{n}={t:.3f}ms")
-                if n == "miopen":
-                    mio = t
-                elif t < best:
-                    best, name = t, n
-            # native first: MIOpen only where it is clearly faster (relative + absolute margin)
-            if mio < best * (1.0 - _MIOPEN_MARGIN) - _MIOPEN_MARGIN_MS:
-                best, name = mio, "miopen"
-            _agree.publish("conv", k, name)
-        else:
-            times.append("rank 0's decision")
-        _CHOICE[k] = name
-        if _TUNE_LOG:
-            import sys
-
-            print(f"[conv-tune] {k} -> {name} ({', '.join(times)})", file=sys.stderr, flush=True)
-    return name
 
 
 def conv2d_forward(x: Tensor, w: Tensor, stride: int, pad: int, bias: Optional[Tensor] = None,
@@ -344,11 +182,9 @@ def _splitk_ok(x: Tensor, w: Tensor, stride: int, pad: int) -> bool:
     maps at batch 1): csrc/conv.hip conv_fwd_splitk_bf16 splits the reduction over workgroups."""
     if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 or x.shape[1] % 64 or w.shape[0] % 128:
         return False
-    n, _, h, wd = x.shape
-    p = (h + 2 * pad - w.shape[2]) // stride + 1
-    q = (wd + 2 * pad - w.shape[3]) // stride + 1
-    return p > 0 and q > 0 and native().conv_fwd_splitk_ksplit(n, x.shape[1], w.shape[0], w.shape[2], w.shape[3],
-                                                              p, q) > 1
+    p, q = _out_hw(x.shape[2], x.shape[3], w.shape[2], w.shape[3], stride, pad)
+    return p > 0 and q > 0 and native().conv_fwd_splitk_ksplit(x.shape[0], x.shape[1], w.shape[0], w.shape[2],
+                                                              w.shape[3], p, q) > 1
 
 
 def _fwd(x: Tensor, w: Tensor, bias: Optional[Tensor], stride: int, pad: int, want_stats: bool,
@@ -362,10 +198,8 @@ def _fwd(x: Tensor, w: Tensor, bias: Optional[Tensor], stride: int, pad: int, wa
 
     pen = 0.0
     if want_stats:  # a MIOpen forward leaves the BN statistics pass to the BN kernel
-        n, _, h, wd = x.shape
-        p = (h + 2 * pad - w.shape[2]) // stride + 1
-        q = (wd + 2 * pad - w.shape[3]) // stride + 1
-        pen = n * p * q * w.shape[0] * 2 / _STATS_PASS_BW * 1e3
+        p, q = _out_hw(x.shape[2], x.shape[3], w.shape[2], w.shape[3], stride, pad)
+        pen = x.shape[0] * p * q * w.shape[0] * 2 / _STATS_PASS_BW * 1e3
     key = (tuple(x.shape), tuple(w.shape), stride, pad, bias is not None, want_stats) + (("relu",) if relu else ())
     cands = [("native", nat, 0.0), ("miopen", mio, pen)]
     cands += _big_cands(w.shape[0], x.shape[1], lambda code: lambda: nat(code))
@@ -376,137 +210,19 @@ def _fwd(x: Tensor, w: Tensor, bias: Optional[Tensor], stride: int, pad: int, wa
     return _route("fwd", key, cands)
 
 
-class _FlipCache:
-    """Flipped/transposed copies of TRAINABLE conv weights, refreshed together.
+def _add_residual(dx: Optional[Tensor], addend: Optional[Tensor], amask: Optional[Tensor],
+                  inplace: bool = False) -> Optional[Tensor]:
+    """``dx + addend``, the addend masked by the ``amask`` bits when there are any (``dx`` None: the
+    masked addend alone); ``inplace`` adds into ``dx``."""
+    if addend is None:
+        return dx
+    if amask is not None:
+        from torchbooster_amd.ops.norm import unpack_mask
 
-    A weight changes once per optimizer step, and every conv's dgrad of the next
-    backward needs its flipped copy: instead of one small flip kernel per conv
-    per backward (52 launches per ResNet-50 step), the first dgrad after a
-    parameter update refreshes every registered stale copy in ONE multi-tensor
-    launch (csrc/conv.hip ``flip_transpose_mt_k``).  An entry is current while
-    its parameter's storage, autograd version and the fused-optimizer generation
-    (ops/_ext.py ``param_generation``: native optimizer kernels write parameters
-    without bumping the version counter) are unchanged."""
-
-    def __init__(self) -> None:
-        import weakref
-
-        self._weakref = weakref.ref
-        self.entries: Dict[int, list] = {}  # id(param) -> [ref, key, wt]
-        self._tables: Dict[tuple, tuple] = {}  # launch tables per set of stale entries
-
-    @staticmethod
-    def _key(p: Tensor):
-        from torchbooster_amd.ops._ext import param_generation
-
-        return (p.data_ptr(), p._version, param_generation(), tuple(p.shape))
-
-    @staticmethod
-    def _shape4(p: Tensor):
-        # a Linear weight [out, in] is the 1x1 conv weight [out, in, 1, 1]: its "flip" is its transpose
-        return tuple(p.shape) if p.dim() == 4 else (p.shape[0], p.shape[1], 1, 1)
-
-    def get(self, w: Tensor, owner: Tensor) -> Tensor:
-        e = self.entries.get(id(owner))
-        if e is not None and e[0]() is owner and e[1] == self._key(owner):
-            return e[2]
-        if e is None or e[0]() is not owner:
-            K, C, R, S = self._shape4(owner)
-            if owner.dim() == 2:
-                wt = torch.empty((C, K), dtype=owner.dtype, device=owner.device)
-            else:
-                wt = torch.empty((C, K, R, S), dtype=owner.dtype, device=owner.device,
-                                 memory_format=torch.channels_last)
-            e = self.entries[id(owner)] = [self._weakref(owner), None, wt]
-        self._refresh()
-        return e[2]
-
-    def _refresh(self) -> None:
-        import numpy as np
-
-        stale = []
-        for pid, (ref, key, wt) in list(self.entries.items()):
-            p = ref()
-            if p is None:
-                del self.entries[pid]
-                continue
-            if key != self._key(p):
-                stale.append((pid, p, wt))
-        if not stale:
-            return
-        # the shapes are part of the signature: a later parameter can reuse a dead one's id AND
-        # (caching allocator) both of its addresses -- a table built for another shape would flip
-        # past the end of the new copy
-        sig = tuple((pid, p.data_ptr(), wt.data_ptr(), tuple(p.shape), p.dtype) for pid, p, wt in stale)
-        tabs = self._tables.get(sig)
-        if tabs is None:
-            dev = stale[0][1].device
-            rows, chunks = [], []
-            for t, (_, p, wt) in enumerate(stale):
-                K, C, R, S = self._shape4(p)
-                rows.append([p.data_ptr(), wt.data_ptr(), K, R, S, C, 0, 0])
-                for tile in range((K // 64) * (R * S * C // 64)):  # 64 x 64 tiles of [K][RSC]
-                    chunks.append([t, tile, 0])
-            table = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev)
-            ck = np.asarray(chunks, dtype=np.int64)  # column 0 = (int32 tensor, int32 pad) little-endian
-            tabs = (torch.from_numpy(ck).to(dev), len(chunks), table)
-            if len(self._tables) > 64:
-                self._tables.clear()
-            self._tables[sig] = tabs
-        native().conv_flip_weights_mt(*tabs)  # (entries are channels_last: [K][R][S][C] in memory)
-        for pid, p, wt in stale:
-            self.entries[pid][1] = self._key(p)
-
-
-_FLIP_CACHE = _FlipCache()
-
-
-def transposed_linear_weight(w: Tensor, owner: Tensor) -> Optional[Tensor]:
-    """``owner``ᵀ ([in, out], contiguous) for a trainable bf16 Linear weight ``owner`` = ``w``'s storage,
-    from the flip cache: every registered copy is refreshed in ONE launch right after each optimizer
-    step (``_refresh_flipped_after_update``), so a Linear input gradient dX = dY W can run as the NT
-    product dY (Wᵀ)ᵀ on the faster row-read kernel (ops/gemm.py ``mm_nn``).  None where the cache
-    cannot hold it (shape not a multiple of 64, capture, frozen or non-bf16 weight)."""
-    if not (owner.requires_grad and owner.dim() == 2 and owner.dtype == torch.bfloat16 and w.dtype == owner.dtype
-            and owner.shape[0] % 64 == 0 and owner.shape[1] % 64 == 0 and owner.is_contiguous()
-            and w.data_ptr() == owner.data_ptr() and tuple(w.shape) == tuple(owner.shape) and w.is_contiguous()
-            and owner.is_cuda and not torch.cuda.is_current_stream_capturing()):
-        return None
-    return _FLIP_CACHE.get(w, owner)
-
-
-def _refresh_flipped_after_update() -> None:
-    if _FLIP_CACHE.entries:
-        _FLIP_CACHE._refresh()
-
-
-from torchbooster_amd.ops._ext import register_param_update_hook  # noqa: E402
-
-register_param_update_hook(_refresh_flipped_after_update)
-
-
-def _flipped(w: Tensor, owner: Optional[Tensor] = None) -> Tensor:
-    """Flipped/transposed weight for the dgrad-as-forward kernel.  Frozen weights
-    (a VGG feature extractor in the style-transfer examples) keep theirs cached
-    on the tensor, keyed by storage and version counter, instead of re-flipping
-    every backward; trainable ones go through :class:`_FlipCache` (one batched
-    refresh per optimizer step).  ``owner`` is the Parameter ``w`` was taken
-    from (``w`` itself may be a per-call saved-tensor object)."""
-    owner = w if owner is None else owner
-    if owner.requires_grad:
-        if (owner.dim() == 4 and owner.shape[0] % 64 == 0 and owner.shape[1] % 64 == 0
-                and w.data_ptr() == owner.data_ptr() and w.dtype == owner.dtype
-                and owner.is_contiguous(memory_format=torch.channels_last)
-                and not torch.cuda.is_current_stream_capturing()):
-            return _FLIP_CACHE.get(w, owner)
-        return native().conv_flip_weight(w)
-    key = (w.data_ptr(), owner._version, tuple(w.shape))
-    hit = getattr(owner, "_tb_flip", None)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    wt = native().conv_flip_weight(w)
-    owner._tb_flip = (key, wt)
-    return wt
+        addend = addend * unpack_mask(amask, addend)
+    if dx is None:
+        return addend
+    return dx.add_(addend) if inplace else dx + addend
 
 
 def _dgrad(dy: Tensor, x: Tensor, w: Tensor, stride: int, pad: int, addend: Optional[Tensor],
@@ -521,14 +237,7 @@ def _dgrad(dy: Tensor, x: Tensor, w: Tensor, stride: int, pad: int, addend: Opti
     use_bnb = bn_in is not None and bn_in.ready()
 
     def mio():
-        dx = _miopen_bwd(dy, x, w, stride, pad, 0)
-        if addend is None:
-            return dx
-        if amask is not None:
-            from torchbooster_amd.ops.norm import unpack_mask
-
-            return dx.add_(addend * unpack_mask(amask, addend))
-        return dx.add_(addend)
+        return _add_residual(_miopen_bwd(dy, x, w, stride, pad, 0), addend, amask, inplace=True)
 
     if stride in (2, 3) and amask is None and native().conv_dgrad_s2_supported(R, w.shape[3], stride):
         # stride 2 / 3: stride^2 output-phase classes of stride-1 sub-convolutions on the native
@@ -544,7 +253,7 @@ def _dgrad(dy: Tensor, x: Tensor, w: Tensor, stride: int, pad: int, addend: Opti
                 b.part, b.dx_ptr = part, dx.data_ptr()
                 return dx
             dx = native().conv2d_dgrad_s2(dy, wt, R, w.shape[3], pad, x.shape[2], x.shape[3], stride=stride)[0]
-            return dx if addend is None else dx.add_(addend)
+            return _add_residual(dx, addend, None, inplace=True)
 
         # a MIOpen dgrad leaves the BN backward its own partial pass over (dX, x)
         pen = 2 * x.numel() * x.element_size() / _STATS_PASS_BW * 1e3 if bnb_ok else 0.0
@@ -557,13 +266,7 @@ def _dgrad(dy: Tensor, x: Tensor, w: Tensor, stride: int, pad: int, addend: Opti
         # TBAMD_CONV_NO_MIOPEN=1)
         def gen():
             dx = native().conv_any_dgrad(dy, w, x.shape[2], x.shape[3], stride, pad, 1, False, _dgrad_weight(w, wparam))
-            if addend is None:
-                return dx
-            if amask is not None:
-                from torchbooster_amd.ops.norm import unpack_mask
-
-                return dx.add_(addend * unpack_mask(amask, addend))
-            return dx.add_(addend)
+            return _add_residual(dx, addend, amask, inplace=True)
 
         key = ("generic", tuple(x.shape), tuple(w.shape), stride, pad, addend is not None, amask is not None)
         return _route("dgrad", key, [("native", gen, 0.0), ("miopen", mio, 0.0)])
@@ -650,31 +353,88 @@ def _dgrad_gxf(gx, w: Tensor, wparam: Optional[Tensor], addend: Optional[Tensor]
     return dx, (dz if want_dz else None)
 
 
-def _wgrad_side(wparam: Tensor, dy: Tensor, w: Tensor, run: Callable[[Optional[Tensor]], Tensor], reads,
-                fresh: bool = False) -> Tensor:
-    """A weight gradient ``run(slot)`` into the parameter's zero-copy slot on the side stream (as
-    :class:`_ConvFn`'s backward); ``reads``: the tensors it reads (kept alive for the side stream);
-    ``fresh``: ``dy`` was produced by the kernel just issued on the compute stream."""
+def _cl_slot(wparam: Tensor, w: Tensor) -> Optional[Tensor]:
+    """The parameter's zero-copy gradient slot, if a channels_last weight gradient can be written into it."""
     slot = take_slot(wparam)
     if slot is not None and (slot.dtype != w.dtype or not slot.is_contiguous(memory_format=torch.channels_last)):
-        slot = None
+        return None
+    return slot
+
+
+def _wgrad_side(wparam: Tensor, w: Tensor, run: Callable[[Tensor, Optional[Tensor]], Tensor], reads,
+                after: Optional[Tensor]) -> Tensor:
+    """The weight gradient ``run(dy, slot)`` into the parameter's zero-copy slot, off the critical
+    path: on the side stream, concurrent with the dgrad and the layers below (ops/streams.py).
+    ``reads``: the tensors it reads, ``dy`` first (kept alive for the side stream).  ``after``: the
+    tensor given to ``streams.fork`` -- the incoming gradient itself where ``dy`` is that very
+    tensor (its producer may have recorded a stop event), None where ``dy`` is a copy or was just
+    produced on the compute stream."""
+    dy = reads[0]
+    slot = _cl_slot(wparam, w)
     if slot is not None and _DIAG_SKIP_WGRAD:
         return slot_alias(slot)  # diagnostic only: the weight gradient is NOT computed
     if slot is not None and streams.usable(dy):
-        side = streams.fork(dy.device, None if fresh else dy)
+        side = streams.fork(dy.device, after)
         with torch.cuda.stream(side):
-            dw = run(slot)
+            dw = run(dy, slot)
             if dw.data_ptr() != slot.data_ptr():
+                # a route that returned a fresh tensor (MIOpen): land it in the slot on the side
+                # stream too -- handed out as is, the DDP reducer's bind copy or AccumulateGrad
+                # would read it on the compute stream while it is still being written here
                 slot.copy_(dw)
                 dw.record_stream(side)
                 dw = slot_alias(slot)
         for t in reads:
             t.record_stream(side)
         return dw
-    dw = run(slot)
+    dw = run(dy, slot)
     if slot is None and slot_in_use(wparam) and streams.pending(dy.device):
+        # a second use of this weight in one backward (D(real) + D(fake), a gradient penalty,
+        # weight tying): autograd sums our fresh dw with the slot alias ON THIS STREAM, and the
+        # DDP bind copies that sum into the slot -- both must come after the side-stream kernel
+        # writing the slot
         torch.cuda.current_stream(dy.device).wait_stream(streams.side_stream(dy.device))
     return dw
+
+
+def _deferred_apply(ctx, dy: Tensor, x: Tensor, w: Tensor, stride: int, pad: int, ok: bool,
+                    addend: Optional[Tensor], amask: Optional[Tensor], want_dw: bool,
+                    wgrad: Callable[[Tensor, Optional[Tensor]], Tensor], reads: tuple):
+    """Take the BatchNorm backward apply that ``ctx.gx`` (ops.norm.BnGradXf of the BN consuming
+    this conv's output) deferred into this conv's input gradient.  Returns the finished
+    ``(dx, dw)`` when the 1x1 kernel took it (``ok``: the caller's own conditions hold), else the
+    gradient to continue with: ``dy`` itself, or the apply materialised by the BN's own kernel.
+    ``wgrad(dz, slot)`` / ``reads`` (after ``dz``): the weight gradient as :func:`_wgrad_side` runs it."""
+    gx, ctx.gx = ctx.gx, None
+    if gx is None:
+        return dy
+    if not gx.ready(dy):
+        return gx.materialize() if gx.mode else dy  # (another tensor arrived as the gradient; never expected)
+    b = ctx.bn_in if (ctx.bn_in is not None and ctx.bn_in.ready()) else None
+    add = 0 if addend is None else (2 if amask is not None else 1)
+    if not (ctx.needs_input_grad[0] and ok and _gxf_conv_ok(x, w, stride, pad)
+            and native().conv_dgrad_gxf_supported(gx.mode, add, b.mode if b is not None else 0)):
+        return gx.materialize()  # this conv cannot take the deferred apply: the BN's own kernel
+    dx, dz = _dgrad_gxf(gx, w, ctx.wparam, addend, amask, b, want_dz=want_dw)
+    # (dz was just produced on the compute stream: a plain fork)
+    dw = _wgrad_side(ctx.wparam, w, wgrad, (dz,) + reads, None) if want_dw else None
+    return dx, dw
+
+
+def _recompute_grads(ctx, has_bias: bool, dy: Tensor, conv: Callable) -> list:
+    """create_graph backward (e.g. a GAN gradient penalty): [dx, dw, db] of the differentiable
+    ATen recompute ``y = conv(x, w, b)`` from the saved inputs, None where not needed."""
+    needs = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2])
+    operands = (*ctx.saved_tensors[:2], ctx.bias_ref if has_bias else None)
+    ins = [t for t, need in zip(operands, needs) if need]
+    out = [None, None, None]
+    if ins:
+        y = conv(*operands)
+        got = list(torch.autograd.grad(y, ins, dy.to(y.dtype), create_graph=True, allow_unused=True))
+        for i, need in enumerate(needs):
+            if need:
+                out[i] = got.pop(0)
+    return out
 
 
 class _ConvFn(torch.autograd.Function):
@@ -717,32 +477,15 @@ class _ConvFn(torch.autograd.Function):
         """Guarded ATen fallback for double backward: rebuild y = conv(x, w) + b
         from the saved inputs and differentiate it with ``create_graph`` so the
         returned gradients carry their own graph (reference GP: gan.py:52-63)."""
-        x, w = ctx.saved_tensors[:2]
         stride, pad, has_bias = ctx.cfg
         if ctx.link is not None:
-            ldy, lmask = ctx.link.take()
-            if ldy is not None:
-                from torchbooster_amd.ops.norm import unpack_mask
-
-                m = ldy * unpack_mask(lmask, ldy)
-                dpass = m if dpass is None else dpass + m
-        grads = [None] * 12
-        if ctx.gx is not None:
-            ctx.gx = None  # (double backward: the BN backward ran differentiably, nothing deferred)
+            dpass = _add_residual(dpass, *ctx.link.take())
+        ctx.gx = None  # (double backward: the BN backward ran differentiably, nothing deferred)
+        grads = [None, None, None]
         if dy is not None:
-            b = ctx.bias_ref if has_bias else None
-            ins = [t for t, need in ((x, ctx.needs_input_grad[0]), (w, ctx.needs_input_grad[1]),
-                                     (b, has_bias and ctx.needs_input_grad[2])) if need]
-            if ins:
-                y = F.conv2d(x, w, b, stride, pad)
-                got = list(torch.autograd.grad(y, ins, dy.to(y.dtype), create_graph=True, allow_unused=True))
-                for i, need in enumerate((ctx.needs_input_grad[0], ctx.needs_input_grad[1],
-                                          has_bias and ctx.needs_input_grad[2])):
-                    if need:
-                        grads[i] = got.pop(0)
-        if dpass is not None:
-            grads[0] = dpass if grads[0] is None else grads[0] + dpass
-        return tuple(grads)
+            grads = _recompute_grads(ctx, has_bias, dy, lambda x, w, b: F.conv2d(x, w, b, stride, pad))
+        grads[0] = _add_residual(grads[0], dpass, None)
+        return (*grads, None, None, None, None, None, None, None, None)
 
     @staticmethod
     def _backward_native(ctx, dy, dpass):
@@ -751,70 +494,25 @@ class _ConvFn(torch.autograd.Function):
         amask = None
         if ctx.link is not None:
             ldy, lmask = ctx.link.take()
-            if ldy is not None:
-                if dpass is not None:  # both forms arrived: fold the masked one in
-                    from torchbooster_amd.ops.norm import unpack_mask
-
-                    dpass = dpass + ldy * unpack_mask(lmask, ldy)
-                else:
-                    dpass, amask = ldy, lmask
+            if ldy is not None and dpass is not None:  # both forms arrived: fold the masked one in
+                dpass = _add_residual(dpass, ldy, lmask)
+            elif ldy is not None:
+                dpass, amask = ldy, lmask
         if dy is None:  # only the passthrough alias was used downstream
-            if amask is not None:
-                from torchbooster_amd.ops.norm import unpack_mask
+            return _add_residual(None, dpass, amask), None, None, None, None, None, None, None, None, None, None
 
-                dpass = dpass * unpack_mask(amask, dpass)
-            return dpass, None, None, None, None, None, None, None, None, None, None
-        gx, ctx.gx = ctx.gx, None
-        if gx is not None and gx.ready(dy):
-            stride, pad, has_bias = ctx.cfg
-            b = ctx.bn_in if (ctx.bn_in is not None and ctx.bn_in.ready()) else None
-            add = 0 if dpass is None else (2 if amask is not None else 1)
-            if (ctx.needs_input_grad[0] and not has_bias and not ctx.relu and _gxf_conv_ok(x, w, stride, pad)
-                    and native().conv_dgrad_gxf_supported(gx.mode, add, b.mode if b is not None else 0)):
-                dx = _dgrad_gxf(gx, w, ctx.wparam, dpass, amask, b, want_dz=ctx.needs_input_grad[1])
-                dz = dx[1]
-                dw = None
-                if ctx.needs_input_grad[1]:
-                    dw = _wgrad_side(ctx.wparam, dz, w, lambda slot: _wgrad(dz, x, w, stride, pad, slot), (dz, x),
-                                     fresh=True)
-                return dx[0], dw, None, None, None, None, None, None, None, None, None
-            dy = gx.materialize()  # this conv cannot take the deferred apply: the BN's own kernel
-        elif gx is not None and gx.mode:
-            dy = gx.materialize()  # (another tensor arrived as the gradient; never expected)
+        def wgrad(g, slot):
+            return _wgrad(g, x, w, stride, pad, slot)
+
+        dy = _deferred_apply(ctx, dy, x, w, stride, pad, not has_bias and not ctx.relu, dpass, amask,
+                             ctx.needs_input_grad[1], wgrad, (x,))
+        if isinstance(dy, tuple):  # (dx, dw): the deferred BN apply ran inside this conv's input gradient
+            return (*dy, None, None, None, None, None, None, None, None, None)
         dy_in = dy
         dy = dy.contiguous(memory_format=torch.channels_last)
         dx = dw = db = None
         if ctx.needs_input_grad[1]:
-            slot = take_slot(ctx.wparam)
-            if slot is not None and (slot.dtype != w.dtype or not slot.is_contiguous(memory_format=torch.channels_last)):
-                slot = None
-            if slot is not None and _DIAG_SKIP_WGRAD:
-                dw = slot_alias(slot)  # diagnostic only: the weight gradient is NOT computed
-            elif slot is not None and streams.usable(dy):
-                # off the critical path: the weight gradient runs on the side stream, concurrent
-                # with this dgrad and the layers below (ops/streams.py)
-                main = torch.cuda.current_stream(dy.device)
-                side = streams.fork(dy.device, dy if dy is dy_in else None)
-                with torch.cuda.stream(side):
-                    dw = _wgrad(dy, x, w, stride, pad, slot)
-                    if dw.data_ptr() != slot.data_ptr():
-                        # a route that returned a fresh tensor (MIOpen): land it in the slot on
-                        # the side stream too -- handed out as is, the DDP reducer's bind copy or
-                        # AccumulateGrad would read it on the compute stream while it is still
-                        # being written here
-                        slot.copy_(dw)
-                        dw.record_stream(side)
-                        dw = slot_alias(slot)
-                dy.record_stream(side)
-                x.record_stream(side)
-            else:
-                dw = _wgrad(dy, x, w, stride, pad, slot)
-                if slot is None and slot_in_use(ctx.wparam) and streams.pending(dy.device):
-                    # a second use of this weight in one backward (D(real) + D(fake), a
-                    # gradient penalty, weight tying): autograd sums our fresh dw with the
-                    # slot alias ON THIS STREAM, and the DDP bind copies that sum into the
-                    # slot -- both must come after the side-stream kernel writing the slot
-                    torch.cuda.current_stream(dy.device).wait_stream(streams.side_stream(dy.device))
+            dw = _wgrad_side(ctx.wparam, w, wgrad, (dy, x), dy if dy is dy_in else None)
         if ctx.needs_input_grad[0]:
             dx = _dgrad(dy, x, w, stride, pad, dpass, amask, ctx.bn_in, ctx.wparam)
         if has_bias and ctx.needs_input_grad[2]:
@@ -850,51 +548,22 @@ class _ConvXfFn(torch.autograd.Function):
         y, scale, shift, w = ctx.saved_tensors
         stride, pad = ctx.cfg
         R = w.shape[2]
-        gx, ctx.gx = ctx.gx, None
-        if gx is not None and gx.ready(dy):
-            b = ctx.bn_in if (ctx.bn_in is not None and ctx.bn_in.ready()) else None
-            if (ctx.needs_input_grad[0] and _gxf_conv_ok(y, w, stride, pad)
-                    and native().conv_dgrad_gxf_supported(gx.mode, 0, b.mode if b is not None else 0)):
-                da, dz = _dgrad_gxf(gx, w, ctx.wparam, None, None, b, want_dz=ctx.needs_input_grad[4])
-                dw = None
-                if ctx.needs_input_grad[4]:
-                    def run(slot):
-                        if slot is not None:
-                            native().conv2d_wgrad_xf(dz, y, scale, shift, R, R, stride, pad, slot)
-                            return slot_alias(slot)
-                        return native().conv2d_wgrad_xf(dz, y, scale, shift, R, R, stride, pad)
 
-                    dw = _wgrad_side(ctx.wparam, dz, w, run, (dz, y, scale, shift), fresh=True)
-                return da, None, None, None, dw, None, None, None, None
-            dy = gx.materialize()
-        elif gx is not None and gx.mode:
-            dy = gx.materialize()
+        def wgrad(g, slot):
+            if slot is not None:
+                native().conv2d_wgrad_xf(g, y, scale, shift, R, R, stride, pad, slot)
+                return slot_alias(slot)
+            return native().conv2d_wgrad_xf(g, y, scale, shift, R, R, stride, pad)
+
+        dy = _deferred_apply(ctx, dy, y, w, stride, pad, True, None, None, ctx.needs_input_grad[4], wgrad,
+                             (y, scale, shift))
+        if isinstance(dy, tuple):  # (da, dw), as in _ConvFn
+            return dy[0], None, None, None, dy[1], None, None, None, None
         dy_in = dy
         dy = dy.contiguous(memory_format=torch.channels_last)
         da = dw = None
         if ctx.needs_input_grad[4]:
-            slot = take_slot(ctx.wparam)
-            if slot is not None and (slot.dtype != w.dtype or not slot.is_contiguous(memory_format=torch.channels_last)):
-                slot = None
-
-            def wgrad():
-                if slot is not None:
-                    native().conv2d_wgrad_xf(dy, y, scale, shift, R, R, stride, pad, slot)
-                    return slot_alias(slot)
-                return native().conv2d_wgrad_xf(dy, y, scale, shift, R, R, stride, pad)
-
-            if slot is not None and _DIAG_SKIP_WGRAD:
-                dw = slot_alias(slot)  # diagnostic only: the weight gradient is NOT computed
-            elif slot is not None and streams.usable(dy):
-                side = streams.fork(dy.device, dy if dy is dy_in else None)
-                with torch.cuda.stream(side):
-                    dw = wgrad()
-                for t in (dy, y, scale, shift):
-                    t.record_stream(side)
-            else:
-                dw = wgrad()
-                if slot is None and slot_in_use(ctx.wparam) and streams.pending(dy.device):
-                    torch.cuda.current_stream(dy.device).wait_stream(streams.side_stream(dy.device))
+            dw = _wgrad_side(ctx.wparam, w, wgrad, (dy, y, scale, shift), dy if dy is dy_in else None)
         if ctx.needs_input_grad[0]:
             # the dgrad needs only a's shape (and the BN link for its epilogue partials)
             da = _dgrad(dy, y, w, stride, pad, None, None, ctx.bn_in, ctx.wparam)
@@ -906,7 +575,7 @@ def xf_supported(y: Tensor, w: Tensor, stride, padding) -> bool:
     groups 1, the single-stage forward addressing (any stride / zero padding)."""
     return (y.is_cuda and y.dim() == 4 and y.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
             and y.shape[1] % 64 == 0 and y.shape[1] <= 512 and w.shape[0] % 64 == 0 and w.shape[1] == y.shape[1]
-            and w.shape[2] == w.shape[3] and _pair(stride) >= 1 and _pair(padding) >= 0 and not _DISABLE
+            and w.shape[2] == w.shape[3] and _pair(stride) >= 1 and _pair(padding) >= 0 and not RT._DISABLE
             and use_native(y))
 
 
@@ -935,7 +604,7 @@ def stem_supported(x: Tensor, w: Tensor, stride, padding, dilation=1, groups=1) 
     return (x.is_cuda and x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.bfloat16
             and w.dtype == torch.bfloat16 and tuple(w.shape[1:]) == (3, 7, 7) and w.shape[0] % 64 == 0
             and _pair(stride) == 2 and _pair(padding) == 3 and _pair(dilation) == 1 and groups == 1
-            and not _DISABLE and use_native(x))
+            and not RT._DISABLE and use_native(x))
 
 
 def _pack_stem_w(w: Tensor) -> Tensor:
@@ -967,8 +636,8 @@ class _StemConvFn(torch.autograd.Function):
 
         pen = 0.0
         if want_stats:
-            n = x.shape[0]
-            pen = n * ((H - 1) // 2 + 1) * ((W - 1) // 2 + 1) * w.shape[0] * 2 / _STATS_PASS_BW * 1e3
+            p, q = _out_hw(H, W, 7, 7, 2, 3)
+            pen = x.shape[0] * p * q * w.shape[0] * 2 / _STATS_PASS_BW * 1e3
         y, stats = _route("fwd", ("stem", tuple(x.shape), tuple(w.shape), want_stats),
                           [("native", nat, 0.0), ("miopen", mio, pen)])
         ctx.set_materialize_grads(False)
@@ -1029,7 +698,7 @@ def conv2d_bn_stats(x: Tensor, w: Tensor, stride: int, padding: int, passthrough
 def conv_any_supported(x: Tensor, w: Tensor, stride, padding, dilation=1, groups=1) -> bool:
     """csrc/conv_any.hip: any channel counts, square taps / stride / padding, bf16 or
     fp32 (reference precision), groups 1, no dilation."""
-    if _DISABLE or not x.is_cuda or x.dim() != 4 or x.dtype not in (torch.bfloat16, torch.float32):
+    if RT._DISABLE or not x.is_cuda or x.dim() != 4 or x.dtype not in (torch.bfloat16, torch.float32):
         return False
     if w.dtype != x.dtype or groups != 1 or _pair(dilation) != 1 or w.shape[2] != w.shape[3]:
         return False
@@ -1050,7 +719,7 @@ def _bias_grad(dy: Tensor, dtype: torch.dtype) -> Tensor:
     (csrc/colsum.hip); C % 8 != 0 sums G rows at once as one row of G*C columns."""
     C = dy.shape[1]
     rows = dy.permute(0, 2, 3, 1)
-    if dy.is_cuda and rows.is_contiguous() and dy.dtype in (torch.bfloat16, torch.float32) and not _DISABLE:
+    if dy.is_cuda and rows.is_contiguous() and dy.dtype in (torch.bfloat16, torch.float32) and not RT._DISABLE:
         G = 8 // math.gcd(C, 8)
         M = rows.numel() // C
         if M % G == 0 and M > 0:
@@ -1228,18 +897,9 @@ class _ConvAnyFn(torch.autograd.Function):
         x, w = ctx.saved_tensors
         stride, pad, up, reflect, has_bias = ctx.cfg
         if torch.is_grad_enabled():  # create_graph: differentiable ATen recompute
-            ins = [t for t, need in ((x, ctx.needs_input_grad[0]), (w, ctx.needs_input_grad[1])) if need]
-            b = ctx.bias_ref if has_bias else None
-            if b is not None and ctx.needs_input_grad[2]:
-                ins.append(b)
-            y = F.conv2d(_virtual(x, pad, up, reflect), w, b, stride)
-            got = list(torch.autograd.grad(y, ins, dy, create_graph=True, allow_unused=True)) if ins else []
-            out = [None] * 7
-            for i, need in enumerate((ctx.needs_input_grad[0], ctx.needs_input_grad[1],
-                                      has_bias and ctx.needs_input_grad[2])):
-                if need:
-                    out[i] = got.pop(0)
-            return tuple(out)
+            grads = _recompute_grads(ctx, has_bias, dy,
+                                     lambda x, w, b: F.conv2d(_virtual(x, pad, up, reflect), w, b, stride))
+            return (*grads, None, None, None, None)
         with torch.no_grad():
             dy = dy.contiguous(memory_format=torch.channels_last)
             exact = x.dtype == torch.float32 and _sync_f32_mode()
@@ -1310,15 +970,12 @@ class _ConvAnyFn(torch.autograd.Function):
                 if _virt_wgrad_ok(x, w, stride, up):
                     cands.insert(0, ("native64", lambda: native().conv2d_wgrad_virtual(
                         dy, x, w.shape[2], w.shape[3], stride, pad, up, reflect), 0.0))
-                Cn, Kn, Rn, Sn = x.shape[1], w.shape[0], w.shape[2], w.shape[3]
-                if (not exact and x.dtype == torch.float32 and dy.dtype == torch.float32 and Cn in (32, 64)
-                        and 1 <= Kn <= 16
-                        and Rn <= 9 and Sn <= 9 and stride == 1 and up in (1, 2, 4)
-                        and (not reflect or (pad < x.shape[2] * up and pad < x.shape[3] * up))
-                        and x.numel() % 4 == 0 and dy.numel() % 4 == 0):
+                # (the forward's gate: w.dtype == x.dtype by conv_any_supported, and for fp32 x `exact` is f32_exact())
+                if (_narrow32_ok(x, w, stride, pad, up, reflect) and dy.dtype == torch.float32
+                        and dy.numel() % 4 == 0):
                     # fp32 RGB heads (9x9, <= 16 outputs): split-bf16 runs of the halo-tile kernel
                     cands.insert(0, ("narrow32", lambda: native().conv_narrow_wgrad_split32(
-                        dy, x, Rn, Sn, pad, up, reflect).contiguous(memory_format=torch.channels_last), 0.0))
+                        dy, x, w.shape[2], w.shape[3], pad, up, reflect).contiguous(memory_format=torch.channels_last), 0.0))
                 if (not exact and x.dtype == torch.float32 and dy.dtype == torch.float32 and x.shape[1] % 64 == 0
                         and w.shape[0] % 64 == 0 and up in (1, 2, 4) and x.numel() % 4 == 0):
                     # fp32 (the reference precision): split-bf16 passes of the 64-channel MFMA kernel
@@ -1437,7 +1094,7 @@ class PadConv2d(torch.nn.Module):
 def conv_transpose_supported(x: Tensor, w: Tensor, stride, padding, output_padding=0, dilation=1, groups=1) -> bool:
     """ConvTranspose2d on the native kernels: x [N, Ci, H, W], w [Ci, Co, R, R] bf16 with
     Ci, Co multiples of 64 (the conv it is the input-gradient of has K = Ci, C = Co)."""
-    if _DISABLE or _DISABLE_T or not x.is_cuda or x.dim() != 4 or x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+    if RT._DISABLE or _DISABLE_T or not x.is_cuda or x.dim() != 4 or x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
         return False
     if groups != 1 or _pair(dilation) != 1 or _pair(output_padding) != 0 or w.shape[2] != w.shape[3]:
         return False
@@ -1480,10 +1137,7 @@ class _ConvTFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = _fwd(dy, w, None, stride, pad, False)[0]
         if ctx.needs_input_grad[1]:
-            slot = take_slot(ctx.wparam)
-            if slot is not None and (slot.dtype != w.dtype or not slot.is_contiguous(memory_format=torch.channels_last)):
-                slot = None
-            dw = _wgrad(x, dy, w, stride, pad, slot)
+            dw = _wgrad(x, dy, w, stride, pad, _cl_slot(ctx.wparam, w))
         if has_bias and ctx.needs_input_grad[2]:
             db = _bias_grad(dy, w.dtype)
         return dx, dw, db, None, None
@@ -1509,7 +1163,7 @@ def _tinyin_ok(t: Tensor, g: Tensor, w: Tensor, stride: int, pad: int) -> bool:
 def conv_transpose_any_supported(x: Tensor, w: Tensor, stride, padding, output_padding=0, dilation=1,
                                  groups=1) -> bool:
     """Transposed convs the generic family takes (any channel counts, bf16 / fp32)."""
-    if _DISABLE or _DISABLE_T or not x.is_cuda or x.dim() != 4 or x.dtype not in (torch.bfloat16, torch.float32):
+    if RT._DISABLE or _DISABLE_T or not x.is_cuda or x.dim() != 4 or x.dtype not in (torch.bfloat16, torch.float32):
         return False
     if w.dtype != x.dtype or groups != 1 or _pair(dilation) != 1 or _pair(output_padding) != 0:
         return False

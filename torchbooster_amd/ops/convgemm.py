@@ -5,7 +5,7 @@ layers with 9x9 / 4x4 windows (StyleNet input, reference online.py:57; DCGAN
 discriminator input / generator output) and 512-channel convs over a few hundred
 pixels (VGG-19 at batch 1, offline.py:104) -- the routing tables used to keep
 MIOpen.  These functions give every such direction a native candidate
-(csrc/im2col.hip + csrc/gemm.hip / gemm8.hip); ``ops.conv._route`` times it
+(csrc/im2col.hip + csrc/gemm.hip / gemm8.hip); ``ops.conv_route._route`` times it
 against the others, and ``TBAMD_CONV_NO_MIOPEN=1`` removes MIOpen from the
 candidates altogether.
 

@@ -249,7 +249,7 @@ TRANS = 100
 
 def mm_nn(dy: Tensor, w: Tensor, out: Optional[Tensor] = None, owner: Optional[Tensor] = None) -> Tensor:
     """dy w  (dy [..., out], w [out, in]) -> [..., in].  ``owner``: the Parameter ``w`` is (the storage
-    of): its cached transpose (ops/conv.py ``transposed_linear_weight``, refreshed once per optimizer
+    of): its cached transpose (ops/flipcache.py ``transposed_linear_weight``, refreshed once per optimizer
     step) lets the product run as NT on the row-read 8-phase kernel -- a timed candidate (tiles
     TRANS + 16 .. 18) beside the NN tiles, which read W through the transposing LDS path."""
     K, Q = dy.shape[-1], w.shape[1]
@@ -261,7 +261,7 @@ def mm_nn(dy: Tensor, w: Tensor, out: Optional[Tensor] = None, owner: Optional[T
     C = native()
     wt = None
     if owner is not None and Kp == K and Qp == Q:
-        from torchbooster_amd.ops.conv import transposed_linear_weight
+        from torchbooster_amd.ops.flipcache import transposed_linear_weight
 
         wt = transposed_linear_weight(w, owner)
 

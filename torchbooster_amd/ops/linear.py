@@ -99,13 +99,13 @@ def _wgrad(dy2: Tensor, x2: Tensor, wp: Tensor) -> Tensor:
             return slot_alias(s)
         return native().conv2d_wgrad(dy4, x4, 1, 1, 1, 0).view(K, C)
 
-    from torchbooster_amd.ops.conv import _route
+    from torchbooster_amd.ops.conv_route import _route
 
     return _route("wgrad", ("linear", M, K, C), [("hipblaslt", blas, 0.0), ("native", nat, 0.0)])
 
 
 # the fused GELU-backward product on the cached transposed weight (row-read NT kernel) instead of the
-# NN kernel's transposing reads (ops/conv.py transposed_linear_weight); TBAMD_GELU_BWD_NT=0: NN (A/B)
+# NN kernel's transposing reads (ops/flipcache.py transposed_linear_weight); TBAMD_GELU_BWD_NT=0: NN (A/B)
 _GELU_BWD_NT = os.environ.get("TBAMD_GELU_BWD_NT", "1") == "1"
 
 
@@ -125,7 +125,7 @@ def _gelu_fused_dx(dy2: Tensor, w: Tensor, link: Optional[GeluLink], x_shape,
         sb = None
     wt = None
     if _GELU_BWD_NT and owner is not None:
-        from torchbooster_amd.ops.conv import transposed_linear_weight
+        from torchbooster_amd.ops.flipcache import transposed_linear_weight
 
         wt = transposed_linear_weight(w, owner)
     dz, db = native().gemm_nn_gelu_bwd(dy2, w, z2, sb, wt)
