@@ -1,5 +1,5 @@
-// Bindings of the attention kernels (attention.hip, attention_decode.hip, attention_extend.hip) and
-// of the few-row decode products (rows_gemm.hip).
+// Bindings of the attention kernels (attention.hip, attention_decode.hip, attention_extend.hip), of
+// the rotary position embedding (rope.hip) and of the few-row decode products (rows_gemm.hip).
 #include "bind_common.h"
 
 namespace {
@@ -299,36 +299,82 @@ Tensor rows_linear(const Tensor& x, const Tensor& weight, const optional<Tensor>
 
 // tokens int64 [B, T] (any strides); tok_weight [vocab, D], pos_weight [max_len, D] bf16 contiguous; positions
 // int32 [B] or none -> [B, T, D].  Token ids and positions are clamped into range by the kernel.
-Tensor embed_rows(const Tensor& tokens, const Tensor& tok_weight, const Tensor& pos_weight,
+// pos_weight none: the clamped token rows alone.
+Tensor embed_rows(const Tensor& tokens, const Tensor& tok_weight, const optional<Tensor>& pos_weight,
                   const optional<Tensor>& positions) {
   const at::DeviceGuard guard = on_device_of(tok_weight, "tok_weight");
   check_cuda(tokens, "tokens");
-  check_cuda(pos_weight, "pos_weight");
   TORCH_CHECK(tokens.scalar_type() == at::kLong && tokens.dim() == 2 && tokens.device() == tok_weight.device(),
               "embed_rows: tokens must be int64 [B, T] on the device of the weights");
-  TORCH_CHECK(tok_weight.scalar_type() == at::kBFloat16 && pos_weight.scalar_type() == at::kBFloat16 &&
-                  tok_weight.dim() == 2 && pos_weight.dim() == 2 && tok_weight.is_contiguous() &&
-                  pos_weight.is_contiguous() && pos_weight.size(1) == tok_weight.size(1) &&
-                  pos_weight.device() == tok_weight.device(),
+  TORCH_CHECK(tok_weight.scalar_type() == at::kBFloat16 && tok_weight.dim() == 2 && tok_weight.is_contiguous(),
               "embed_rows: weights must be contiguous bf16 [vocab, D] and [max_len, D]");
   const int64_t B = tokens.size(0), T = tokens.size(1), D = tok_weight.size(1);
-  TORCH_CHECK(D % 8 == 0 && D >= 8 && tok_weight.size(0) >= 1 && pos_weight.size(0) >= 1 &&
-                  tok_weight.size(0) < (int64_t)INT32_MAX && pos_weight.size(0) < (int64_t)INT32_MAX &&
+  TORCH_CHECK(D % 8 == 0 && D >= 8 && tok_weight.size(0) >= 1 && tok_weight.size(0) < (int64_t)INT32_MAX &&
                   D < (int64_t)INT32_MAX && B * T < (int64_t)INT32_MAX,
               "embed_rows: D % 8 == 0; bad size");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(tok_weight.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(pos_weight.data_ptr()) % 16 == 0,
-              "embed_rows: weights not 16-B aligned");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(tok_weight.data_ptr()) % 16 == 0, "embed_rows: weights not 16-B aligned");
   tbamd::EmbedRowsArgs a{};
+  a.max_len = 1;
+  if (given(pos_weight)) {
+    const Tensor& pw = *pos_weight;
+    check_cuda(pw, "pos_weight");
+    TORCH_CHECK(pw.scalar_type() == at::kBFloat16 && pw.dim() == 2 && pw.is_contiguous() && pw.size(1) == D &&
+                    pw.device() == tok_weight.device(),
+                "embed_rows: weights must be contiguous bf16 [vocab, D] and [max_len, D]");
+    TORCH_CHECK(pw.size(0) >= 1 && pw.size(0) < (int64_t)INT32_MAX, "embed_rows: D % 8 == 0; bad size");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(pw.data_ptr()) % 16 == 0, "embed_rows: weights not 16-B aligned");
+    a.pos_w = reinterpret_cast<const uint16_t*>(pw.data_ptr());
+    a.max_len = (int)pw.size(0);
+  }
   if (given(positions)) a.pos = decode_lengths(*positions, "positions", tok_weight, B);
   Tensor y = at::empty({B, T, D}, tok_weight.options());
   a.tokens = tokens.data_ptr<int64_t>();
   a.stok[0] = tokens.stride(0), a.stok[1] = tokens.stride(1);
   a.tok_w = reinterpret_cast<const uint16_t*>(tok_weight.data_ptr());
-  a.pos_w = reinterpret_cast<const uint16_t*>(pos_weight.data_ptr());
   a.y = reinterpret_cast<uint16_t*>(y.data_ptr());
-  a.B = (int)B, a.T = (int)T, a.D = (int)D, a.vocab = (int)tok_weight.size(0), a.max_len = (int)pos_weight.size(0);
+  a.B = (int)B, a.T = (int)T, a.D = (int)D, a.vocab = (int)tok_weight.size(0);
   tbamd::embed_rows(a, cur_stream());
+  return y;
+}
+
+// ---- rotary position embedding (csrc/rope.hip).  qkv: packed [B, T, (H + 2*Hkv)*64] bf16 (checked as
+// the decode kernels' qkv); table: f32 [max_len, 2, 32] contiguous on the same device; positions: int32
+// [B] or none, read by the kernel.  out none -> a new contiguous tensor, value part copied; out given
+// -> it must BE qkv (in place: the value part is not touched).  Returns the output.
+Tensor rope_packed(const Tensor& qkv, int64_t heads, const Tensor& table, const optional<Tensor>& positions,
+                   int64_t kv_heads, bool inverse, const optional<Tensor>& out) {
+  const at::DeviceGuard guard = on_device_of(qkv, "qkv");
+  const int64_t Hkv = kv_heads_of(heads, kv_heads, "rope");
+  TORCH_CHECK(qkv.dim() == 3, "rope: qkv must be bf16 [B, T, (H + 2*Hkv)*64]");
+  const int64_t B = qkv.size(0), T = qkv.size(1), H = heads;
+  TORCH_CHECK(B * T * (H + 2 * Hkv) < (int64_t)1 << 34 && B < (int64_t)INT32_MAX && T < (int64_t)INT32_MAX &&
+                  H + 2 * Hkv < (int64_t)1 << 20,
+              "rope: bad size");
+  check_cuda(table, "table");
+  TORCH_CHECK(table.scalar_type() == at::kFloat && table.dim() == 3 && table.size(1) == 2 && table.size(2) == 32 &&
+                  table.is_contiguous() && table.size(0) >= 1 && table.size(0) < (int64_t)INT32_MAX / 64 &&
+                  table.device() == qkv.device(),
+              "rope: table must be contiguous f32 [max_len, 2, 32] on the device of qkv");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(table.data_ptr()) % 16 == 0, "rope: table not 16-B aligned");
+  tbamd::RopeArgs a{};
+  a.x = packed_qkv(qkv, B, H, Hkv, qkv, a.sx);
+  Tensor y;
+  if (given(out)) {
+    TORCH_CHECK(out->is_same(qkv), "rope: out must be qkv itself (in place)");
+    y = *out;
+    a.sy[0] = a.sx[0], a.sy[1] = a.sx[1];
+    a.copy_v = 0;
+  } else {
+    y = at::empty({B, T, qkv.size(2)}, qkv.options().memory_format(at::MemoryFormat::Contiguous));
+    a.sy[0] = T * qkv.size(2), a.sy[1] = qkv.size(2);
+    a.copy_v = 1;
+  }
+  a.y = reinterpret_cast<uint16_t*>(y.data_ptr());
+  a.tab = table.data_ptr<float>();
+  if (given(positions)) a.pos = decode_lengths(*positions, "positions", qkv, B);
+  a.B = (int)B, a.T = (int)T, a.H = (int)H, a.Hkv = (int)Hkv, a.max_len = (int)table.size(0);
+  a.inverse = inverse ? 1 : 0;
+  tbamd::rope_packed(a, cur_stream());
   return y;
 }
 
@@ -393,8 +439,11 @@ void register_attn(pybind11::module& m) {
   m.def("rows_linear", &rows_linear, py::arg("x"), py::arg("weight"), py::arg("bias") = py::none(),
         py::arg("gamma") = py::none(), py::arg("beta") = py::none(), py::arg("eps") = 0.0, py::arg("epi") = 0,
         py::arg("residual") = py::none(), py::arg("out") = py::none());
-  m.def("embed_rows", &embed_rows, py::arg("tokens"), py::arg("tok_weight"), py::arg("pos_weight"),
+  m.def("embed_rows", &embed_rows, py::arg("tokens"), py::arg("tok_weight"), py::arg("pos_weight") = py::none(),
         py::arg("positions") = py::none());
+  m.def("rope_packed", &rope_packed, py::arg("qkv"), py::arg("heads"), py::arg("table"),
+        py::arg("positions") = py::none(), py::arg("kv_heads") = 0, py::arg("inverse") = false,
+        py::arg("out") = py::none());
   m.def("attn_extend", &attn_extend, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("positions"),
         py::arg("scale"), py::arg("workspace") = py::none(), py::arg("kv_heads") = 0);
   // knobs and workspace sizes

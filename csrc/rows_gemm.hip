@@ -30,6 +30,7 @@
 //
 //   embed_rows_k    x[b, t] = tok[clamp(id)] + pos[clamp(positions[b] + t)], f32 sum, one rounding.
 //                   A token id outside [0, vocab) is clamped: it never becomes an address.
+//                   Without a position table (pos_w null) it is the clamped token row alone.
 #include "common.h"
 #include "tbamd.h"
 
@@ -218,13 +219,18 @@ __global__ __launch_bounds__(256) void embed_rows_k(EmbedRowsArgs a) {
   tk = tk < 0 ? 0 : (tk >= a.vocab ? (int64_t)a.vocab - 1 : tk);  // never an address out of range
   int64_t p = (a.pos ? (int64_t)a.pos[b] : 0) + t;
   p = p < 0 ? 0 : (p >= a.max_len ? (int64_t)a.max_len - 1 : p);
+  const uint4 tw = *reinterpret_cast<const uint4*>(a.tok_w + tk * a.D + v * 8);
+  const bool ok = TB_BOUNDS_OK(row * a.D + v * 8 + 8 <= (int64_t)a.B * a.T * a.D, kBndGemmDst);
+  if (!a.pos_w) {  // no learned positions (kernel-uniform): the clamped token row, bit for bit
+    if (ok) *reinterpret_cast<uint4*>(a.y + row * a.D + v * 8) = tw;
+    return;
+  }
   float e[8], q[8];
-  rows_unpack8(*reinterpret_cast<const uint4*>(a.tok_w + tk * a.D + v * 8), e);
+  rows_unpack8(tw, e);
   rows_unpack8(*reinterpret_cast<const uint4*>(a.pos_w + p * a.D + v * 8), q);
 #pragma unroll
   for (int k = 0; k < 8; ++k) e[k] += q[k];
-  if (TB_BOUNDS_OK(row * a.D + v * 8 + 8 <= (int64_t)a.B * a.T * a.D, kBndGemmDst))
-    *reinterpret_cast<uint4*>(a.y + row * a.D + v * 8) = rows_pack8(e);
+  if (ok) *reinterpret_cast<uint4*>(a.y + row * a.D + v * 8) = rows_pack8(e);
 }
 
 template <int MB, int CW>

@@ -351,7 +351,7 @@ int rows_linear_cols_per_wave(int Q);
 void rows_linear(const RowsLinearArgs& a, hipStream_t st);
 // y[b][t][:] = tok_w[clamp(tokens[b][t], 0, vocab - 1)] + pos_w[clamp(pos[b] + t, 0, max_len - 1)]
 // (f32 sum, one rounding); tokens int64 [B][T] with strides stok (elements), pos int32 [B] or null
-// (0), D % 8 == 0.
+// (0), D % 8 == 0.  pos_w null (a model without learned positions): the clamped token row alone.
 struct EmbedRowsArgs {
   const int64_t* tokens;
   const uint16_t* tok_w;
@@ -362,6 +362,23 @@ struct EmbedRowsArgs {
   int B, T, D, vocab, max_len;
 };
 void embed_rows(const EmbedRowsArgs& a, hipStream_t st);
+
+// ---- rotary position embedding of a packed projection (csrc/rope.hip; head dim 64, bf16) ----
+// x, y: packed [B][T][(H + 2*Hkv)*64] rows (q | k | v), strides in elements over (batch, token), unit
+// last stride, 16-B aligned rows; y may be x.  The H query heads and the Hkv key heads of token t of
+// batch b are rotated (rotate-half layout) by the angles of table row p = clamp(pos[b] + t, 0,
+// max_len - 1); tab: f32 [max_len][2][32], cosines then sines; pos: [B] int32 in device memory, read
+// by the kernel, or null (0).  inverse: the transposed rotation (-sin).  copy_v: the same launch
+// copies the value part of x to y bit for bit (out of place); 0 leaves it untouched (in place).
+struct RopeArgs {
+  const uint16_t* x;
+  uint16_t* y;
+  const float* tab;
+  const int* pos;
+  int B, T, H, Hkv, max_len, inverse, copy_v;
+  int64_t sx[2], sy[2];
+};
+void rope_packed(const RopeArgs& a, hipStream_t st);
 
 // ---- KV-cache extend attention (csrc/attention_extend.hip; head dim 64, bf16) ----
 // T new queries per (batch, head) against the cache AFTER their own k / v rows were appended at

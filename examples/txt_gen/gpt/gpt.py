@@ -44,6 +44,7 @@ class Config(BaseConfig):
     env: EnvironementConfig
     optim: OptimizerConfig
     scheduler: SchedulerConfig
+    pos: str = "learned"  # "rope": rotary position embeddings (models/gpt.py)
 
 
 def load_bytes(path: str) -> torch.Tensor:
@@ -58,7 +59,7 @@ def main(conf: Config) -> None:
     data = conf.env.make(load_bytes(conf.text))
     if data.numel() <= conf.seq_len:
         raise ValueError(f"{conf.text or 'README.md'}: {data.numel()} bytes, need more than seq_len = {conf.seq_len}")
-    model = prepare_model(getattr(gpt, conf.arch)(vocab=256, max_len=conf.seq_len), conf, channels_last=False)
+    model = prepare_model(getattr(gpt, conf.arch)(vocab=256, max_len=conf.seq_len, pos=conf.pos), conf, channels_last=False)
     net = getattr(model, "module", model)
     optim = conf.optim.make(model.parameters())
     sched = conf.scheduler.make(optim)

@@ -36,6 +36,17 @@ attention), so a :class:`KVCache` layer is ``[B, Hkv, capacity, hd]`` -- ``heads
 and as many times fewer bytes per decode step, which the decode kernel reads once for the heads that
 share them (ops/attention.py).  Everything above works unchanged in meaning, including a
 ``generate(draft=)`` whose two models differ in ``kv_heads``.  ``kv_heads=None`` is ``heads``.
+
+Rotary position embeddings (``TransformerLM(..., pos="rope", rope_base=10000.0)``): there is no learned
+position table -- no ``pos`` parameter -- the token embedding alone feeds the first block, and every
+layer rotates the q and k parts of its packed projection by the token's position (rotate-half layout,
+``ops.attention.rope_packed``, csrc/rope.hip) before any attention path reads it.  A token is at position
+``t`` in ``features`` / ``forward`` / ``loss`` / ``prefill``, at ``cache.positions[b]`` in ``decode_step``
+and at ``cache.positions[b] + t`` in ``extend``, on the default and on the fused path, hence under
+``generate`` with ``graph=True``, ``cache=`` and ``draft=`` (whose two models may differ in ``pos``).  A
+:class:`KVCache` is unchanged and holds rotated keys; ``max_len`` stays the capacity limit and is the
+length of the angle table, which one :class:`~torchbooster_amd.models.vit.Rope` per model owns outside
+the parameters and buffers.  ``pos="learned"`` (the default) is everything above unchanged.
 """
 from __future__ import annotations
 
@@ -44,7 +55,7 @@ from typing import List, Optional, Tuple
 import torch
 from torch import Tensor, nn
 
-from torchbooster_amd.models.vit import Block
+from torchbooster_amd.models.vit import Block, Rope
 from torchbooster_amd.ops.linear import Linear, embed_rows, linear_rows
 from torchbooster_amd.ops.loss import linear_cross_entropy
 from torchbooster_amd.ops.norm import LayerNorm
@@ -94,17 +105,23 @@ def _sample(logits: Tensor, temperature: float, top_k: Optional[int], generator)
 
 class TransformerLM(nn.Module):
     def __init__(self, vocab: int, dim: int, depth: int, heads: int, max_len: int, mlp_ratio: float = 4.0,
-                 kv_heads: Optional[int] = None) -> None:
+                 kv_heads: Optional[int] = None, *, pos: str = "learned", rope_base: float = 10000.0) -> None:
         super().__init__()
+        if pos not in ("learned", "rope"):
+            raise ValueError(f"pos must be 'learned' or 'rope', not {pos!r}")
         self.max_len = max_len
         self.tok = nn.Embedding(vocab, dim)
-        self.pos = nn.Parameter(torch.zeros(1, max_len, dim))
-        self.blocks = nn.ModuleList([Block(dim, heads, mlp_ratio, causal=True, kv_heads=kv_heads)
+        # learned: a [1, max_len, dim] table added to the token embedding; rope: none, the layers rotate q / k
+        self.rope = Rope(max_len, dim // heads, rope_base) if pos == "rope" else None
+        self.pos = nn.Parameter(torch.zeros(1, max_len, dim)) if self.rope is None else None
+        kw = {} if self.rope is None else {"rope": self.rope}  # learned: the calls it always made
+        self.blocks = nn.ModuleList([Block(dim, heads, mlp_ratio, causal=True, kv_heads=kv_heads, **kw)
                                      for _ in range(depth)])
         self.norm = LayerNorm(dim, eps=1e-6)
         self.head = Linear(dim, vocab, bias=False)
         nn.init.normal_(self.tok.weight, std=0.02)
-        nn.init.normal_(self.pos, std=0.02)
+        if self.pos is not None:
+            nn.init.normal_(self.pos, std=0.02)
         for m in self.modules():
             if isinstance(m, nn.Linear):
                 nn.init.normal_(m.weight, std=0.02)
@@ -116,7 +133,9 @@ class TransformerLM(nn.Module):
         B, N = tokens.shape
         if N > self.max_len:
             raise ValueError(f"sequence length {N} exceeds max_len {self.max_len}")
-        x = self.tok(tokens) + self.pos[:, :N].to(self.tok.weight.dtype)
+        x = self.tok(tokens)
+        if self.pos is not None:
+            x = x + self.pos[:, :N].to(self.tok.weight.dtype)
         pending = None
         for blk in self.blocks:
             x, pending = blk(x, pending, lengths)
@@ -164,7 +183,9 @@ class TransformerLM(nn.Module):
             if N > cache.capacity:
                 raise ValueError(f"prompt length {N} exceeds the cache capacity {cache.capacity}")
             cache.positions.zero_()
-            x = self.tok(tokens) + self.pos[:, :N].to(self.tok.weight.dtype)
+            x = self.tok(tokens)
+            if self.pos is not None:
+                x = x + self.pos[:, :N].to(self.tok.weight.dtype)
             pending = None
             for blk, kv in zip(self.blocks, cache.layers):
                 x, pending = blk(x, pending, lengths, cache=kv, positions=cache.positions)
@@ -181,21 +202,28 @@ class TransformerLM(nn.Module):
     def _norm_ln(self):
         return self.norm.weight, self.norm.bias, self.norm.eps
 
+    def _pos_rows(self) -> Optional[Tensor]:
+        """``embed_rows``' position table: ``[max_len, dim]``, or None with rotary positions."""
+        return None if self.pos is None else self.pos[0]
+
     def decode_step(self, token: Tensor, cache: KVCache, *, fused: bool = False) -> Tensor:
         """One new token per sequence, ``token`` ``[B]``, at ``cache.positions`` -> logits ``[B, vocab]``;
         ``cache.positions`` advance by one in place.  No device value is read on the host.
         ``fused=True``: the few-row kernels (module docstring); same result to rounding."""
         if fused:
             with torch.no_grad():
-                x = embed_rows(token[:, None], self.tok.weight, self.pos[0], cache.positions)
+                x = embed_rows(token[:, None], self.tok.weight, self._pos_rows(), cache.positions)
                 for blk, kv in zip(self.blocks, cache.layers):
                     x = blk.forward_rows(x, cache=kv, positions=cache.positions)
                 logits = linear_rows(x[:, 0], self.head.weight, self.head.bias, ln=self._norm_ln())
                 cache.positions.add_(1)
                 return logits
         with torch.no_grad():
-            at = cache.positions.to(torch.int64).clamp(0, self.max_len - 1)
-            x = (self.tok(token) + self.pos[0].index_select(0, at).to(self.tok.weight.dtype))[:, None]
+            if self.pos is None:
+                x = self.tok(token)[:, None]
+            else:
+                at = cache.positions.to(torch.int64).clamp(0, self.max_len - 1)
+                x = (self.tok(token) + self.pos[0].index_select(0, at).to(self.tok.weight.dtype))[:, None]
             pending = None
             for blk, kv in zip(self.blocks, cache.layers):
                 x, pending = blk(x, pending, cache=kv, positions=cache.positions)
@@ -224,7 +252,7 @@ class TransformerLM(nn.Module):
             raise ValueError(f"{T} new tokens exceed the cache capacity {cache.capacity}")
         if fused:
             with torch.no_grad():
-                x = embed_rows(tokens, self.tok.weight, self.pos[0], cache.positions)
+                x = embed_rows(tokens, self.tok.weight, self._pos_rows(), cache.positions)
                 for blk, kv in zip(self.blocks, cache.layers):
                     x = blk.forward_rows(x, cache=kv, positions=cache.positions, extend=True)
                 adv = None if lengths is None else lengths.clamp(1, T).to(torch.int32)
@@ -238,8 +266,11 @@ class TransformerLM(nn.Module):
                 cache.positions.add_(T if adv is None else adv)
                 return logits
         with torch.no_grad():
-            at = cache.positions.to(torch.int64)[:, None] + torch.arange(T, device=tokens.device)[None, :]
-            x = self.tok(tokens) + self.pos[0][at.clamp(0, self.max_len - 1)].to(self.tok.weight.dtype)
+            if self.pos is None:
+                x = self.tok(tokens)
+            else:
+                at = cache.positions.to(torch.int64)[:, None] + torch.arange(T, device=tokens.device)[None, :]
+                x = self.tok(tokens) + self.pos[0][at.clamp(0, self.max_len - 1)].to(self.tok.weight.dtype)
             pending = None
             for blk, kv in zip(self.blocks, cache.layers):
                 x, pending = blk(x, pending, cache=kv, positions=cache.positions, extend=True)
@@ -417,9 +448,9 @@ class TransformerLM(nn.Module):
             return out, out_lengths
 
 
-def gpt_tiny(vocab: int = 256, max_len: int = 128) -> TransformerLM:
-    return TransformerLM(vocab, 128, 2, 2, max_len)
+def gpt_tiny(vocab: int = 256, max_len: int = 128, pos: str = "learned") -> TransformerLM:
+    return TransformerLM(vocab, 128, 2, 2, max_len, pos=pos)
 
 
-def gpt2_small(vocab: int = 50257, max_len: int = 1024) -> TransformerLM:
-    return TransformerLM(vocab, 768, 12, 12, max_len)
+def gpt2_small(vocab: int = 50257, max_len: int = 1024, pos: str = "learned") -> TransformerLM:
+    return TransformerLM(vocab, 768, 12, 12, max_len, pos=pos)

@@ -20,13 +20,51 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from torchbooster_amd.ops.attention import (attention_decode_packed, attention_extend_packed, attention_packed,
-                                            kv_cache_append)
+                                            kv_cache_append, rope_packed, rope_table)
 from torchbooster_amd.ops.conv import Conv2d
 
 from torchbooster_amd.ops.norm import LayerNorm
 from torchbooster_amd.ops.linear import GeluLink, Linear, LinearGELU, linear, linear_rows
 
-__all__ = ["ViT", "vit_b_16", "vit_s_16", "vit_tiny", "Attention", "Block"]
+__all__ = ["ViT", "vit_b_16", "vit_s_16", "vit_tiny", "Attention", "Block", "Rope"]
+
+
+class Rope:
+    """The rotary position embedding of one model: ``(max_len, head_dim, base)`` and the table of
+    ``ops.attention.rope_table`` per (device, dtype), built on first use and shared by every
+    :class:`Attention` that holds this object.
+
+    Neither a parameter nor a buffer: ``model.to(torch.bfloat16)`` does not round it and ``.cuda()`` does
+    not have to move it -- ``table(like)`` follows the device of ``like`` and is float32, or float64 for
+    float64 activations.  A copy (``copy.deepcopy``, pickling) carries the three numbers and rebuilds its
+    tables.  The device copy is a host-built tensor, so its first use must lie outside a graph capture
+    (``TransformerLM.prefill`` and the eager step ahead of ``generate(graph=True)`` both see to that)."""
+
+    def __init__(self, max_len: int, head_dim: int, base: float = 10000.0) -> None:
+        if head_dim < 2 or head_dim % 2:
+            raise ValueError(f"rotary embeddings need an even head dim, not {head_dim}")
+        self.max_len, self.head_dim, self.base = int(max_len), int(head_dim), float(base)
+        self._tables = {}
+
+    def table(self, like: Tensor) -> Tensor:
+        """``[max_len, 2, head_dim // 2]`` on the device of ``like``."""
+        dtype = torch.float64 if like.dtype == torch.float64 else torch.float32
+        key = (like.device, dtype)
+        t = self._tables.get(key)
+        if t is None:
+            if like.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the rotary table must exist before a graph capture begins: run one eager "
+                                   "step first")
+            t = self._tables[key] = rope_table(self.max_len, self.head_dim, self.base, device=like.device,
+                                               dtype=dtype)
+        return t
+
+    def __getstate__(self):
+        return {"max_len": self.max_len, "head_dim": self.head_dim, "base": self.base}
+
+    def __setstate__(self, state) -> None:
+        self.__dict__.update(state)
+        self._tables = {}
 
 
 class Attention(nn.Module):
@@ -45,9 +83,15 @@ class Attention(nn.Module):
     ``kv_heads`` (grouped-query attention, ops/attention.py): ``heads`` query heads share ``kv_heads``
     key / value heads, query head ``h`` reading kv head ``h // (heads // kv_heads)``.  The projection is
     ``Linear(dim, (heads + 2 * kv_heads) * hd)`` and a cache ``[B, kv_heads, cap, hd]``.  ``None`` is
-    ``heads``: plain multi-head attention, the same parameters and the same calls as without it."""
+    ``heads``: plain multi-head attention, the same parameters and the same calls as without it.
 
-    def __init__(self, dim: int, heads: int, causal: bool = False, kv_heads: Optional[int] = None) -> None:
+    ``rope`` (a :class:`Rope`; ``None``: nothing changes): the q and k parts of the packed projection are
+    rotated right behind ``self.qkv`` (``ops.attention.rope_packed``), so every path below reads rotated
+    q / k and a cache holds rotated keys.  Token ``t`` is at position ``t`` without a cache and in a
+    prefill, at ``positions[b] + t`` in a decode step and an extend; the cached paths rotate in place."""
+
+    def __init__(self, dim: int, heads: int, causal: bool = False, kv_heads: Optional[int] = None,
+                 rope: Optional[Rope] = None) -> None:
         super().__init__()
         if kv_heads is not None and (kv_heads < 1 or heads % kv_heads):
             raise ValueError(f"kv_heads {kv_heads} must divide heads {heads}")
@@ -55,15 +99,24 @@ class Attention(nn.Module):
         self.kv_heads = heads if kv_heads is None else int(kv_heads)
         self.hd = dim // heads
         self.causal = causal
+        if rope is not None and rope.head_dim != self.hd:
+            raise ValueError(f"rope is for head dim {rope.head_dim}, this layer has {self.hd}")
+        self.rope = rope
         self.qkv = Linear(dim, 3 * dim if kv_heads is None else (heads + 2 * self.kv_heads) * self.hd)
         self.proj = Linear(dim, dim)
+
+    def rotate(self, qkv: Tensor, positions: Optional[Tensor] = None, inplace: bool = False) -> Tensor:
+        """The packed projection with q and k rotated; ``qkv`` itself without ``rope``."""
+        if self.rope is None:
+            return qkv
+        return rope_packed(qkv, self.heads, self.rope.table(qkv), positions, kv_heads=self.kv_heads, inplace=inplace)
 
     def forward(self, x: Tensor, key_lengths: Optional[Tensor] = None, *, cache=None,
                 positions: Optional[Tensor] = None, extend: bool = False) -> Tensor:
         scale = 1.0 / math.sqrt(self.hd)
         kw = {} if self.kv_heads == self.heads else {"kv_heads": self.kv_heads}  # MHA: the calls it always made
         if cache is None:
-            return self.proj(attention_packed(self.qkv(x), self.heads, scale, causal=self.causal,
+            return self.proj(attention_packed(self.rotate(self.qkv(x)), self.heads, scale, causal=self.causal,
                                               key_lengths=key_lengths, **kw))
         if not self.causal:
             raise ValueError("a KV cache needs causal attention")
@@ -71,6 +124,8 @@ class Attention(nn.Module):
             raise ValueError("a KV cache needs positions")
         k_cache, v_cache = cache
         qkv = self.qkv(x)
+        if self.rope is not None:  # a prefill's tokens are at 0 .. N - 1 whatever row they are appended at
+            qkv = self.rotate(qkv, positions if extend or x.shape[1] == 1 else None, inplace=True)
         if extend:
             return self.proj(attention_extend_packed(qkv, self.heads, k_cache, v_cache, positions, scale, **kw))
         if x.shape[1] == 1:
@@ -94,10 +149,10 @@ class MLP(nn.Module):
 
 class Block(nn.Module):
     def __init__(self, dim: int, heads: int, mlp_ratio: float = 4.0, causal: bool = False,
-                 kv_heads: Optional[int] = None) -> None:
+                 kv_heads: Optional[int] = None, rope: Optional[Rope] = None) -> None:
         super().__init__()
         self.ln1 = LayerNorm(dim, eps=1e-6)
-        self.attn = Attention(dim, heads, causal, kv_heads)
+        self.attn = Attention(dim, heads, causal, kv_heads, rope)
         self.ln2 = LayerNorm(dim, eps=1e-6)
         self.mlp = MLP(dim, int(dim * mlp_ratio))
 
@@ -120,7 +175,8 @@ class Block(nn.Module):
         ``x`` ``[B, T, dim]`` is the residual stream itself -- there is no ``pending`` -- and so is the
         result.  Both LayerNorms run as prologues of the product behind them, bias / GELU / residual as
         epilogues, and with ``T == 1`` the cache append is folded into the decode attention
-        (``attention_decode_packed(fused=True)``): 5 launches with a single-chunk cache, 6 otherwise.
+        (``attention_decode_packed(fused=True)``): 5 launches with a single-chunk cache, 6 otherwise (one
+        more with rotary positions: the rotation of ``qkv``).
         ``T > 1`` needs ``extend=True`` and uses ``attention_extend_packed``.  Computes what ``forward``
         computes with ``cache`` / ``positions`` / ``extend``, to rounding."""
         at = self.attn
@@ -132,6 +188,8 @@ class Block(nn.Module):
         scale = 1.0 / math.sqrt(at.hd)
         kw = {} if at.kv_heads == at.heads else {"kv_heads": at.kv_heads}
         qkv = linear_rows(x, at.qkv.weight, at.qkv.bias, ln=(self.ln1.weight, self.ln1.bias, self.ln1.eps))
+        if at.rope is not None:  # one more launch per layer
+            qkv = at.rotate(qkv, positions, inplace=True)
         if x.shape[1] == 1:
             a = attention_decode_packed(qkv, at.heads, k_cache, v_cache, positions, scale, fused=True, **kw)
         else:

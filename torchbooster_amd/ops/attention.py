@@ -85,6 +85,13 @@ query heads of a group, and the decode / extend results have the bits of the sam
 expanded to ``H`` heads.  Training and prefill (:func:`attention`, :func:`attention_packed` with
 ``Hkv < H``) expand k / v to ``H`` heads -- one materialised copy -- and run the existing kernels under
 autograd, which sums dK / dV over each group; a group-aware training kernel is not part of this.
+
+Rotary position embeddings (csrc/rope.hip): :func:`rope_packed` rotates the q and k parts of a packed
+projection by the angles :func:`rope_table` holds, before any of the functions above reads it -- so the
+training path, the prefill, the append, the decode and the extend all see rotated q / k, a cache holds
+rotated keys, and none of the attention kernels knows.  Positions follow the clamp rule of
+``embed_rows`` and are read on the device.  Differentiable out of place (the gradient is the inverse
+rotation), forward-only in place.
 """
 from __future__ import annotations
 
@@ -99,7 +106,8 @@ from torch.autograd.function import once_differentiable
 from torchbooster_amd.ops._ext import native, use_native
 
 __all__ = ["attention", "attention_packed", "attention_ref", "native_supported", "kv_cache_append",
-           "attention_decode", "attention_decode_packed", "attention_extend", "attention_extend_packed"]
+           "attention_decode", "attention_decode_packed", "attention_extend", "attention_extend_packed",
+           "rope_table", "rope_packed"]
 
 
 def _visible(N: int, device, causal: bool, key_lengths: Optional[Tensor]) -> Optional[Tensor]:
@@ -476,3 +484,128 @@ def attention_extend_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: T
         _append_ref(k_cache, v_cache, qkv, heads, positions, hkv)
         q = qkv[..., :heads * D].reshape(B, T, heads, D)
         return _extend_ref(q, k_cache, v_cache, positions, scale).reshape(B, T, heads * D)
+
+
+# ---------------------------------------------------------------- rotary position embedding
+def rope_table(max_len: int, head_dim: int, base: float = 10000.0, *, device=None,
+               dtype: torch.dtype = torch.float32) -> Tensor:
+    """The angles of :func:`rope_packed`: ``[max_len, 2, head_dim // 2]``, row ``p`` holding
+    ``cos(p * theta_i)`` and then ``sin(p * theta_i)`` with ``theta_i = base ** (-2 * i / head_dim)``.
+    Built in float64 on the host and rounded once to ``dtype`` (float32 or float64), so the native
+    kernel and the PyTorch path use the same numbers and no device math library's range reduction enters
+    at large positions.  Another frequency schedule is another table of this shape."""
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"rope_table: dtype must be float32 or float64, not {dtype}")
+    max_len, head_dim = int(max_len), int(head_dim)
+    if max_len < 1 or head_dim < 2 or head_dim % 2:
+        raise ValueError(f"rope_table: max_len {max_len} must be >= 1 and head_dim {head_dim} even and >= 2")
+    i = torch.arange(head_dim // 2, dtype=torch.float64)
+    theta = torch.pow(torch.tensor(float(base), dtype=torch.float64), -2.0 * i / head_dim)
+    ang = torch.arange(max_len, dtype=torch.float64)[:, None] * theta[None, :]
+    return torch.stack((ang.cos(), ang.sin()), dim=1).to(dtype).to(device)
+
+
+def _rope_ref(qkv: Tensor, heads: int, hkv: int, table: Tensor, positions: Optional[Tensor], inverse: bool,
+              inplace: bool) -> Tensor:
+    """The PyTorch path of :func:`rope_packed`: the two formulas in fp32 (fp64 for fp64 inputs), one
+    rounding, the kernel's clamp, no host sync."""
+    B, T, E = qkv.shape
+    hr = heads + hkv
+    D = E // (hr + hkv)
+    at = torch.arange(T, device=qkv.device)[None, :]
+    if positions is not None:
+        at = positions.to(torch.int64)[:, None] + at
+    cs = table[at.clamp(0, table.shape[0] - 1)]  # [B | 1, T, 2, D / 2]
+    ct = torch.float64 if qkv.dtype == torch.float64 else torch.float32
+    c, s = cs[:, :, 0, None, :].to(ct), cs[:, :, 1, None, :].to(ct)
+    if inverse:
+        s = -s
+    x = qkv[..., :hr * D].reshape(B, T, hr, D).to(ct)
+    x1, x2 = x[..., :D // 2], x[..., D // 2:]
+    y = torch.cat((x1 * c - x2 * s, x2 * c + x1 * s), dim=-1).to(qkv.dtype).reshape(B, T, hr * D)
+    if inplace:
+        qkv[..., :hr * D].copy_(y)
+        return qkv
+    return torch.cat((y, qkv[..., hr * D:]), dim=-1)
+
+
+def _rope_apply(qkv: Tensor, heads: int, hkv: int, table: Tensor, positions: Optional[Tensor], inverse: bool,
+                inplace: bool) -> Tensor:
+    D = qkv.shape[2] // (heads + 2 * hkv)
+    if (qkv.is_cuda and qkv.dtype == torch.bfloat16 and D == 64 and table.dtype == torch.float32
+            and use_native(qkv)):
+        table = table.contiguous()
+        pos = None if positions is None else positions.contiguous()
+        if _rows_ok(qkv):
+            return native().rope_packed(qkv, heads, table, pos, hkv, inverse, qkv if inplace else None)
+        y = native().rope_packed(qkv.contiguous(), heads, table, pos, hkv, inverse, None)
+        if inplace:  # the rotated part alone goes back: the value part is not touched
+            w = (heads + hkv) * D
+            qkv[..., :w].copy_(y[..., :w])
+            return qkv
+        return y
+    return _rope_ref(qkv, heads, hkv, table, positions, inverse, inplace)
+
+
+class _RopeFn(torch.autograd.Function):
+    """The rotation is orthogonal: its gradient is the inverse rotation of the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, hkv, table, positions, inverse):
+        ctx.save_for_backward(table, positions)
+        ctx.cfg = (heads, hkv, inverse)
+        return _rope_apply(qkv, heads, hkv, table, positions, inverse, False)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        table, positions = ctx.saved_tensors
+        heads, hkv, inverse = ctx.cfg
+        return _rope_apply(g, heads, hkv, table, positions, not inverse, False), None, None, None, None, None
+
+
+def rope_packed(qkv: Tensor, heads: int, table: Tensor, positions: Optional[Tensor] = None, *,
+                kv_heads: Optional[int] = None, inverse: bool = False, inplace: bool = False) -> Tensor:
+    """Rotary position embedding of a packed projection: ``qkv`` ``[B, T, (H + 2*Hkv)*D]`` -> the same shape,
+    the ``H`` query heads and the ``Hkv`` key heads rotated, the value part copied bit for bit (with
+    ``inplace=True`` the result is ``qkv`` itself and the value part is not touched at all).
+
+    Rotate-half (GPT-NeoX / Llama) layout: for a head vector ``x`` of even length ``D`` at position ``p``,
+    with ``c`` / ``s`` row ``p`` of ``table`` (``[max_len, 2, D // 2]``, :func:`rope_table`),
+    ``y[i] = x[i] * c - x[i + D/2] * s`` and ``y[i + D/2] = x[i + D/2] * c + x[i] * s``; ``inverse=True``
+    uses ``-s``, the transpose of the rotation and therefore its gradient.  Token ``t`` of batch ``b`` is at
+    position ``clamp((positions[b] if given else 0) + t, 0, max_len - 1)`` -- the rule of
+    ``ops.linear.embed_rows``: a bad position never becomes an address.  ``positions`` is an int32 ``[B]``
+    tensor on the device of ``qkv``, read on the device: no host sync, safe inside a graph capture, a
+    replay follows in-place changes.  ``kv_heads``: ``Hkv`` of grouped-query attention; ``None`` is ``H``.
+
+    Native path (csrc/rope.hip, one launch): CUDA bf16, ``D == 64``, a float32 table on the same device; a
+    view that is not 16-B aligned with row strides in multiples of 8 goes through ``.contiguous()``.
+    Everything else -- CPU, other dtypes, another even ``D``, ``TBAMD_FORCE_REFERENCE=1`` -- is the PyTorch
+    path: the same formulas in fp32 (fp64 for fp64 inputs) and the same clamp.
+
+    Out of place it is differentiable w.r.t. ``qkv``: the gradient is ``rope_packed(grad, ...,
+    inverse=not inverse)``, a new tensor; the table and the positions get none.  ``inplace=True`` is
+    forward-only and raises if ``qkv`` requires grad in grad mode."""
+    hkv = _kv_heads(heads, kv_heads)
+    if qkv.dim() != 3 or qkv.shape[2] % (heads + 2 * hkv) or (qkv.shape[2] // (heads + 2 * hkv)) % 2:
+        raise RuntimeError("qkv must be [B, T, (H + 2*Hkv)*D] with an even D")
+    B, T, E = qkv.shape
+    D = E // (heads + 2 * hkv)
+    if table.dim() != 3 or table.shape[1] != 2 or table.shape[2] != D // 2 or table.shape[0] < 1:
+        raise RuntimeError(f"table must be [max_len, 2, D // 2 = {D // 2}], not {tuple(table.shape)}")
+    if table.device != qkv.device:
+        raise RuntimeError("table must be on the device of qkv")
+    if positions is not None and (positions.dtype != torch.int32 or positions.shape != (B,)
+                                  or positions.device != qkv.device):
+        raise RuntimeError("positions must be an int32 tensor of shape [B] on the device of qkv")
+    if inplace:
+        if torch.is_grad_enabled() and qkv.requires_grad:
+            raise RuntimeError("rope_packed(inplace=True) is forward-only: call it under torch.no_grad() or "
+                               "detach the input")
+        with torch.no_grad():
+            return _rope_apply(qkv, heads, hkv, table, positions, bool(inverse), True)
+    if torch.is_grad_enabled() and qkv.requires_grad:
+        return _RopeFn.apply(qkv, heads, hkv, table, positions, bool(inverse))
+    with torch.no_grad():
+        return _rope_apply(qkv, heads, hkv, table, positions, bool(inverse), False)

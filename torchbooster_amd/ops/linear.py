@@ -342,11 +342,13 @@ def linear_rows(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, ln=
         return y
 
 
-def embed_rows(tokens: Tensor, tok_weight: Tensor, pos_weight: Tensor, positions: Optional[Tensor] = None) -> Tensor:
+def embed_rows(tokens: Tensor, tok_weight: Tensor, pos_weight: Optional[Tensor] = None,
+               positions: Optional[Tensor] = None) -> Tensor:
     """Token plus learned position embedding of ``tokens`` ``[B, T]`` in one kernel -> ``[B, T, dim]`` in the
     dtype of ``tok_weight`` ``[vocab, dim]``: ``tok_weight[id] + pos_weight[clamp(positions[b] + t, 0,
     max_len - 1)]`` with ``pos_weight`` ``[max_len, dim]`` and ``positions`` int ``[B]`` (zeros when None),
-    summed in f32 and rounded once.
+    summed in f32 and rounded once.  ``pos_weight=None`` (a model without learned positions): the clamped
+    token row alone, bit for bit.
 
     The one difference from ``nn.Embedding``: a token id outside ``[0, vocab)`` is CLAMPED into range, on
     every path, instead of raising (CPU) or tripping a device-side assert (GPU) -- a bad id never becomes
@@ -359,12 +361,16 @@ def embed_rows(tokens: Tensor, tok_weight: Tensor, pos_weight: Tensor, positions
         raise RuntimeError("positions must have shape [B]")
     with torch.no_grad():
         bf = torch.bfloat16
-        if (use_native(tok_weight) and tokens.is_cuda and tok_weight.dtype == bf and pos_weight.dtype == bf
-                and pos_weight.is_cuda and tok_weight.shape[1] % 8 == 0 and B * T > 0
+        if (use_native(tok_weight) and tokens.is_cuda and tok_weight.dtype == bf
+                and (pos_weight is None or (pos_weight.dtype == bf and pos_weight.is_cuda))
+                and tok_weight.shape[1] % 8 == 0 and B * T > 0
                 and (positions is None or (positions.is_cuda and positions.dtype == torch.int32))):
             return native().embed_rows(tokens.to(torch.int64), tok_weight.contiguous(),
-                                       pos_weight.contiguous(), None if positions is None else positions.contiguous())
+                                       None if pos_weight is None else pos_weight.contiguous(),
+                                       None if positions is None else positions.contiguous())
         ids = tokens.to(torch.int64).clamp(0, tok_weight.shape[0] - 1)
+        if pos_weight is None:
+            return F.embedding(ids, tok_weight)
         at = torch.arange(T, device=tokens.device)[None, :].expand(B, T)
         if positions is not None:
             at = positions.to(torch.int64)[:, None] + at
