@@ -153,43 +153,53 @@ void attn_kv_append(const Tensor& qkv, int64_t heads, const Tensor& k_cache, con
   tbamd::attn_kv_append(a, cur_stream());
 }
 
+// What attn_decode and attn_decode_append share of AttnDecodeArgs: the cache views, the size checks, the
+// lengths and the output o [B, H*64], which is returned.  qkv: the packed [B, 1, (H + 2*Hkv)*64] whose q
+// part is read in place (a.sq[0] is its batch stride); null leaves a.q / a.sq to the caller.  a.ws too.
+Tensor decode_args(tbamd::AttnDecodeArgs& a, const Tensor* qkv, int64_t H, int64_t Hkv, const Tensor& k_cache,
+                   const Tensor& v_cache, const Tensor& lengths, const char* lengths_name, int64_t add, double scale) {
+  check_kv_cache(k_cache, Hkv, "attention decode");
+  const int64_t B = k_cache.size(0), cap = k_cache.size(2);
+  TORCH_CHECK(B >= 1 && cap >= 1 && cap < (int64_t)INT32_MAX / 2 && add >= -cap && add <= cap,
+              "attention decode: bad size");
+  TORCH_CHECK(B * H * (int64_t)tbamd::attn_decode_chunks((int)cap) < (int64_t)INT32_MAX / 64,
+              "attention decode: bad size");
+  if (qkv != nullptr) {
+    TORCH_CHECK(qkv->dim() == 3 && qkv->size(1) == 1, "attention decode: qkv must be bf16 [B, 1, (H + 2*Hkv)*64]");
+    a.q = packed_qkv(*qkv, B, H, Hkv, k_cache, a.sq);
+    a.sq[1] = 64;  // from head to head, not packed_qkv's token stride
+  }
+  attn_view(k_cache, "k_cache", B, Hkv, cap, &a.k, a.sk);
+  attn_view(v_cache, "v_cache", B, Hkv, cap, &a.v, a.sv);
+  TORCH_CHECK(v_cache.device() == k_cache.device(), "attention decode: caches on different devices");
+  a.klen = decode_lengths(lengths, lengths_name, k_cache, B);
+  Tensor o = at::empty({B, H * 64}, k_cache.options());
+  a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
+  a.so[0] = H * 64, a.so[1] = 64;
+  a.B = (int)B, a.H = (int)H, a.Hkv = (int)Hkv, a.cap = (int)cap, a.add = (int)add, a.scale = (float)scale;
+  return o;
+}
+
 // q: [B, H, 64] (any batch / head strides) or the packed [B, 1, (H + 2*Hkv)*64] whose q part is read in
 // place -> o [B, H*64].  len = clamp(lengths[b] + add, 1, cap).  workspace (optional, tests): f32,
 // at least attn_decode_workspace floats; by default it comes from the caching allocator.
 Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const Tensor& v_cache, const Tensor& lengths,
                    int64_t add, double scale, const optional<Tensor>& workspace, int64_t kv_heads) {
   const at::DeviceGuard guard(k_cache.device());
-  const int64_t Hkv = kv_heads_of(heads, kv_heads, "attention decode");
-  check_kv_cache(k_cache, Hkv, "attention decode");
-  const int64_t B = k_cache.size(0), H = heads, cap = k_cache.size(2);
-  TORCH_CHECK(B >= 1 && cap >= 1 && cap < (int64_t)INT32_MAX / 2 && add >= -cap && add <= cap,
-              "attention decode: bad size");
-  TORCH_CHECK(B * H * (int64_t)tbamd::attn_decode_chunks((int)cap) < (int64_t)INT32_MAX / 64,
-              "attention decode: bad size");
+  const int64_t H = heads, Hkv = kv_heads_of(heads, kv_heads, "attention decode");
+  const bool packed = q.dim() == 3 && q.size(1) == 1 && q.size(2) == packed_qkv_width(H, Hkv);
   tbamd::AttnDecodeArgs a{};
-  if (q.dim() == 3 && q.size(1) == 1 && q.size(2) == packed_qkv_width(H, Hkv)) {
-    int64_t s[2];
-    a.q = packed_qkv(q, B, H, Hkv, k_cache, s);
-    a.sq[0] = s[0], a.sq[1] = 64;
-  } else {
+  Tensor o = decode_args(a, packed ? &q : nullptr, H, Hkv, k_cache, v_cache, lengths, "lengths", add, scale);
+  if (!packed) {
     check_cuda(q, "q");
-    TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.dim() == 3 && q.size(0) == B && q.size(1) == H &&
+    TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.dim() == 3 && q.size(0) == a.B && q.size(1) == H &&
                     q.size(2) == 64 && q.stride(2) == 1,
                 "attention decode: q must be bf16 [B, H, 64] with a unit head-dim stride (or packed [B, 1, (H + 2*Hkv)*64])");
     TORCH_CHECK(q.device() == k_cache.device(), "attention decode: q must be on the device of the cache");
     a.q = aligned_rows(q, 2, a.sq, "attention decode", "q");
   }
-  attn_view(k_cache, "k_cache", B, Hkv, cap, &a.k, a.sk);
-  attn_view(v_cache, "v_cache", B, Hkv, cap, &a.v, a.sv);
-  TORCH_CHECK(v_cache.device() == k_cache.device(), "attention decode: caches on different devices");
-  a.klen = decode_lengths(lengths, "lengths", k_cache, B);
-  const int64_t need = tbamd::attn_decode_workspace((int)B, (int)H, (int)cap);
-  Tensor ws = workspace_or_new(workspace, need, k_cache, "attention decode");
-  Tensor o = at::empty({B, H * 64}, k_cache.options());
-  a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
-  a.so[0] = H * 64, a.so[1] = 64;
+  Tensor ws = workspace_or_new(workspace, tbamd::attn_decode_workspace(a.B, a.H, a.cap), k_cache, "attention decode");
   a.ws = ws.data_ptr<float>();
-  a.B = (int)B, a.H = (int)H, a.Hkv = (int)Hkv, a.cap = (int)cap, a.add = (int)add, a.scale = (float)scale;
   tbamd::attn_decode(a, cur_stream());
   return o;
 }
@@ -200,30 +210,15 @@ Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const 
 Tensor attn_decode_append(const Tensor& qkv, int64_t heads, const Tensor& k_cache, const Tensor& v_cache,
                           const Tensor& positions, double scale, int64_t kv_heads) {
   const at::DeviceGuard guard(k_cache.device());
-  const int64_t Hkv = kv_heads_of(heads, kv_heads, "attention decode");
-  check_kv_cache(k_cache, Hkv, "attention decode");
-  const int64_t B = k_cache.size(0), H = heads, cap = k_cache.size(2);
-  TORCH_CHECK(B >= 1 && cap >= 1 && cap < (int64_t)INT32_MAX / 2, "attention decode: bad size");
-  TORCH_CHECK(B * H * (int64_t)tbamd::attn_decode_chunks((int)cap) < (int64_t)INT32_MAX / 64,
-              "attention decode: bad size");
-  TORCH_CHECK(qkv.dim() == 3 && qkv.size(1) == 1, "attention decode: qkv must be bf16 [B, 1, (H + 2*Hkv)*64]");
+  const int64_t H = heads, Hkv = kv_heads_of(heads, kv_heads, "attention decode");
   tbamd::AttnDecodeArgs a{};
-  int64_t s[2];
-  a.q = packed_qkv(qkv, B, H, Hkv, k_cache, s);
-  a.sq[0] = s[0], a.sq[1] = 64;
-  attn_view(k_cache, "k_cache", B, Hkv, cap, &a.k, a.sk);
-  attn_view(v_cache, "v_cache", B, Hkv, cap, &a.v, a.sv);
-  TORCH_CHECK(v_cache.device() == k_cache.device(), "attention decode: caches on different devices");
-  a.klen = decode_lengths(positions, "positions", k_cache, B);
-  const int64_t need = tbamd::attn_decode_chunks((int)cap) > 1 ? tbamd::attn_decode_workspace((int)B, (int)H, (int)cap) : 0;
-  Tensor ws;
-  if (need > 0) ws = at::empty({need}, k_cache.options().dtype(at::kFloat));
-  Tensor o = at::empty({B, H * 64}, k_cache.options());
-  a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
-  a.so[0] = H * 64, a.so[1] = 64;
-  a.ws = need > 0 ? ws.data_ptr<float>() : nullptr;
-  a.B = (int)B, a.H = (int)H, a.Hkv = (int)Hkv, a.cap = (int)cap, a.add = 1, a.scale = (float)scale;
-  tbamd::attn_decode_append(a, a.q + H * 64, a.q + (H + Hkv) * 64, s[0], cur_stream());
+  Tensor o = decode_args(a, &qkv, H, Hkv, k_cache, v_cache, positions, "positions", 1, scale);
+  Tensor ws;  // a single chunk is normalised in the split kernel: no partials
+  if (tbamd::attn_decode_chunks(a.cap) > 1) {
+    ws = at::empty({tbamd::attn_decode_workspace(a.B, a.H, a.cap)}, k_cache.options().dtype(at::kFloat));
+    a.ws = ws.data_ptr<float>();
+  }
+  tbamd::attn_decode_append(a, a.q + H * 64, a.q + (H + Hkv) * 64, a.sq[0], cur_stream());
   return o;
 }
 

@@ -15,14 +15,14 @@ through the fused head (ops/loss.py ``linear_cross_entropy``), which masks the p
 and never stores the logits.
 
 Generation (forward only, ``torch.no_grad()``): :class:`KVCache` holds the keys and values of every
-layer, ``prefill`` runs the prompt once and fills it, ``decode_step`` runs ONE new token per sequence
-against it (the split-KV decode kernels of csrc/attention_decode.hip) and ``generate`` ties the two to
-greedy / temperature / top-k sampling.  Nothing in a decode step reads a device value on the host --
-positions and lengths live in device memory -- so a step can be captured into a graph and replayed
-(``generate(graph=True)``).  ``extend`` runs T >= 1 new tokens per sequence on top of what a cache holds
-(csrc/attention_extend.hip): ``generate(cache=...)`` continues a conversation with it, and
-``generate(draft=...)`` is greedy speculative decoding, the target scoring a draft's proposals in one
-``extend`` per round.
+layer and ``prefill`` runs the prompt once and fills it.  Every step after that is ONE body, ``_step``:
+``extend`` runs T >= 1 new tokens per sequence on top of what the cache holds (csrc/attention_extend.hip;
+one token: the split-KV decode kernels of csrc/attention_decode.hip), and ``decode_step(token, cache)`` is
+``extend(token[:, None], cache, last_only=True)`` bit for bit.  Nothing in a step reads a device value on
+the host -- positions and lengths live in device memory -- so a step can be captured into a graph and
+replayed.  ``generate`` ties prefill and steps to greedy / temperature / top-k sampling
+(``graph=True``: replayed steps), continues a conversation (``cache=...``) and decodes speculatively
+(``draft=...``: the target scores a draft's proposals in one ``extend`` per round).
 
 Fused decoding (``fused=True`` on ``decode_step`` / ``extend`` / ``generate``, off by default): the same
 step on the few-row kernels -- ``embed_rows``, then per layer ``Block.forward_rows`` (LayerNorm, bias,
@@ -41,8 +41,8 @@ Rotary position embeddings (``TransformerLM(..., pos="rope", rope_base=10000.0)`
 position table -- no ``pos`` parameter -- the token embedding alone feeds the first block, and every
 layer rotates the q and k parts of its packed projection by the token's position (rotate-half layout,
 ``ops.attention.rope_packed``, csrc/rope.hip) before any attention path reads it.  A token is at position
-``t`` in ``features`` / ``forward`` / ``loss`` / ``prefill``, at ``cache.positions[b]`` in ``decode_step``
-and at ``cache.positions[b] + t`` in ``extend``, on the default and on the fused path, hence under
+``t`` in ``features`` / ``forward`` / ``loss`` / ``prefill`` and at ``cache.positions[b] + t`` in a step
+(``decode_step`` / ``extend``), on the default and on the fused path, hence under
 ``generate`` with ``graph=True``, ``cache=`` and ``draft=`` (whose two models may differ in ``pos``).  A
 :class:`KVCache` is unchanged and holds rotated keys; ``max_len`` stays the capacity limit and is the
 length of the angle table, which one :class:`~torchbooster_amd.models.vit.Rope` per model owns outside
@@ -55,7 +55,7 @@ from typing import List, Optional, Tuple
 import torch
 from torch import Tensor, nn
 
-from torchbooster_amd.models.vit import Block, Rope
+from torchbooster_amd.models.vit import Block, Rope, ln_args
 from torchbooster_amd.ops.linear import Linear, embed_rows, linear_rows
 from torchbooster_amd.ops.loss import linear_cross_entropy
 from torchbooster_amd.ops.norm import LayerNorm
@@ -133,10 +133,7 @@ class TransformerLM(nn.Module):
         B, N = tokens.shape
         if N > self.max_len:
             raise ValueError(f"sequence length {N} exceeds max_len {self.max_len}")
-        x = self.tok(tokens)
-        if self.pos is not None:
-            x = x + self.pos[:, :N].to(self.tok.weight.dtype)
-        pending = None
+        x, pending = self._embed(tokens), None
         for blk in self.blocks:
             x, pending = blk(x, pending, lengths)
         h, _ = self.norm(x, pending)
@@ -183,54 +180,81 @@ class TransformerLM(nn.Module):
             if N > cache.capacity:
                 raise ValueError(f"prompt length {N} exceeds the cache capacity {cache.capacity}")
             cache.positions.zero_()
-            x = self.tok(tokens)
-            if self.pos is not None:
-                x = x + self.pos[:, :N].to(self.tok.weight.dtype)
-            pending = None
-            for blk, kv in zip(self.blocks, cache.layers):
+            x, pending = self._embed(tokens), None
+            for blk, kv in zip(self.blocks, cache.layers):  # the masked self-attention plus one append
                 x, pending = blk(x, pending, lengths, cache=kv, positions=cache.positions)
             if lengths is None:
                 cache.positions.fill_(N)
-                x, pending = x[:, N - 1:], pending[:, N - 1:]
             else:
                 cache.positions.copy_(lengths.clamp(1, N))
-                last = (cache.positions.to(torch.int64) - 1)[:, None, None].expand(B, 1, x.shape[-1])
-                x, pending = x.gather(1, last), pending.gather(1, last)
-            h, _ = self.norm(x.contiguous(), pending.contiguous())
-            return self.head(h[:, 0]), cache
+            x, pending = self._last_rows(x, pending, None if lengths is None else cache.positions, N)
+            return self._logits(x, pending)[:, 0], cache
 
-    def _norm_ln(self):
-        return self.norm.weight, self.norm.bias, self.norm.eps
+    def _embed(self, tokens: Tensor, positions: Optional[Tensor] = None) -> Tensor:
+        """Token rows ``[B, T, dim]`` plus, with ``pos="learned"``, the learned position rows: ``0 .. T - 1``,
+        or ``clamp(positions[b] + t, 0, max_len - 1)`` with ``positions`` (int32 ``[B]``)."""
+        if self.pos is None:
+            return self.tok(tokens)
+        T, dtype = tokens.shape[1], self.tok.weight.dtype
+        if positions is None:
+            return self.tok(tokens) + self.pos[:, :T].to(dtype)
+        at = positions.to(torch.int64)
+        if T == 1:  # a decode step: one index_select, no arange and no advanced index
+            at = at.clamp(0, self.max_len - 1)
+            return self.tok(tokens) + self.pos[0].index_select(0, at).to(dtype)[:, None]
+        at = at[:, None] + torch.arange(T, device=tokens.device)[None, :]
+        return self.tok(tokens) + self.pos[0][at.clamp(0, self.max_len - 1)].to(dtype)
 
-    def _pos_rows(self) -> Optional[Tensor]:
-        """``embed_rows``' position table: ``[max_len, dim]``, or None with rotary positions."""
-        return None if self.pos is None else self.pos[0]
+    @staticmethod
+    def _last_rows(x: Tensor, pending: Optional[Tensor], valid: Optional[Tensor], T: int):
+        """Each sequence's last valid row of ``x`` and of ``pending`` (when there is one), ``[B, T, dim]`` ->
+        ``[B, 1, dim]``: row ``valid[b] - 1`` (``valid`` int32 ``[B]`` in ``[1, T]``), or ``T - 1`` without.
+        With a ``pending`` the rows are contiguous, as the LayerNorm behind them reads them."""
+        if valid is not None:
+            last = (valid.to(torch.int64) - 1)[:, None, None].expand(x.shape[0], 1, x.shape[-1])
+            return x.gather(1, last), None if pending is None else pending.gather(1, last)
+        if T == 1:
+            return x, pending
+        if pending is None:
+            return x[:, T - 1:], None
+        return x[:, T - 1:].contiguous(), pending[:, T - 1:].contiguous()
+
+    def _logits(self, x: Tensor, pending: Optional[Tensor], fused: bool = False) -> Tensor:
+        """The final LayerNorm and the head on ``[B, T, dim]`` -> ``[B, T, vocab]``.  Default: ``x`` and its
+        ``pending`` add; ``fused``: the residual stream alone, the LayerNorm as the product's prologue."""
+        if fused:
+            return linear_rows(x, self.head.weight, self.head.bias, ln=ln_args(self.norm))
+        h, _ = self.norm(x, pending)
+        return self.head(h)
+
+    def _step(self, tokens: Tensor, cache: KVCache, lengths: Optional[Tensor], last_only: bool,
+              fused: bool) -> Tensor:
+        """``decode_step`` and ``extend``: ``tokens`` ``[B, T]`` at ``cache.positions[b] + t``, on the few-row
+        kernels when ``fused``.  ``[B, T, vocab]``, or ``[B, vocab]`` with ``last_only``."""
+        T = tokens.shape[1]
+        with torch.no_grad():
+            if fused:
+                x = embed_rows(tokens, self.tok.weight, None if self.pos is None else self.pos[0], cache.positions)
+            else:
+                x = self._embed(tokens, cache.positions)
+            pending = None
+            for blk, kv in zip(self.blocks, cache.layers):
+                if fused:
+                    x = blk.forward_rows(x, cache=kv, positions=cache.positions, extend=True)
+                else:
+                    x, pending = blk(x, pending, cache=kv, positions=cache.positions, extend=True)
+            adv = None if lengths is None else lengths.clamp(1, T).to(torch.int32)
+            if last_only:
+                x, pending = self._last_rows(x, pending, adv, T)
+            logits = self._logits(x, pending, fused)
+            cache.positions.add_(T if adv is None else adv)
+            return logits[:, 0] if last_only else logits
 
     def decode_step(self, token: Tensor, cache: KVCache, *, fused: bool = False) -> Tensor:
         """One new token per sequence, ``token`` ``[B]``, at ``cache.positions`` -> logits ``[B, vocab]``;
         ``cache.positions`` advance by one in place.  No device value is read on the host.
         ``fused=True``: the few-row kernels (module docstring); same result to rounding."""
-        if fused:
-            with torch.no_grad():
-                x = embed_rows(token[:, None], self.tok.weight, self._pos_rows(), cache.positions)
-                for blk, kv in zip(self.blocks, cache.layers):
-                    x = blk.forward_rows(x, cache=kv, positions=cache.positions)
-                logits = linear_rows(x[:, 0], self.head.weight, self.head.bias, ln=self._norm_ln())
-                cache.positions.add_(1)
-                return logits
-        with torch.no_grad():
-            if self.pos is None:
-                x = self.tok(token)[:, None]
-            else:
-                at = cache.positions.to(torch.int64).clamp(0, self.max_len - 1)
-                x = (self.tok(token) + self.pos[0].index_select(0, at).to(self.tok.weight.dtype))[:, None]
-            pending = None
-            for blk, kv in zip(self.blocks, cache.layers):
-                x, pending = blk(x, pending, cache=kv, positions=cache.positions)
-            h, _ = self.norm(x, pending)
-            logits = self.head(h[:, 0])
-            cache.positions.add_(1)
-            return logits
+        return self._step(token[:, None], cache, None, True, fused)
 
     def extend(self, tokens: Tensor, cache: KVCache, lengths: Optional[Tensor] = None, *,
                last_only: bool = False, fused: bool = False) -> Tensor:
@@ -250,44 +274,7 @@ class TransformerLM(nn.Module):
             raise ValueError("extend needs at least one token per sequence")
         if T > cache.capacity:
             raise ValueError(f"{T} new tokens exceed the cache capacity {cache.capacity}")
-        if fused:
-            with torch.no_grad():
-                x = embed_rows(tokens, self.tok.weight, self._pos_rows(), cache.positions)
-                for blk, kv in zip(self.blocks, cache.layers):
-                    x = blk.forward_rows(x, cache=kv, positions=cache.positions, extend=True)
-                adv = None if lengths is None else lengths.clamp(1, T).to(torch.int32)
-                if last_only:
-                    if adv is None:
-                        x = x[:, T - 1]
-                    else:
-                        last = (adv.to(torch.int64) - 1)[:, None, None].expand(B, 1, x.shape[-1])
-                        x = x.gather(1, last)[:, 0]
-                logits = linear_rows(x, self.head.weight, self.head.bias, ln=self._norm_ln())
-                cache.positions.add_(T if adv is None else adv)
-                return logits
-        with torch.no_grad():
-            if self.pos is None:
-                x = self.tok(tokens)
-            else:
-                at = cache.positions.to(torch.int64)[:, None] + torch.arange(T, device=tokens.device)[None, :]
-                x = self.tok(tokens) + self.pos[0][at.clamp(0, self.max_len - 1)].to(self.tok.weight.dtype)
-            pending = None
-            for blk, kv in zip(self.blocks, cache.layers):
-                x, pending = blk(x, pending, cache=kv, positions=cache.positions, extend=True)
-            adv = None if lengths is None else lengths.clamp(1, T).to(torch.int32)
-            if last_only:
-                if adv is None:
-                    x, pending = x[:, T - 1:], pending[:, T - 1:]
-                else:
-                    last = (adv.to(torch.int64) - 1)[:, None, None].expand(B, 1, x.shape[-1])
-                    x, pending = x.gather(1, last), pending.gather(1, last)
-                h, _ = self.norm(x.contiguous(), pending.contiguous())
-                logits = self.head(h[:, 0])
-            else:
-                h, _ = self.norm(x, pending)
-                logits = self.head(h)
-            cache.positions.add_(T if adv is None else adv)
-            return logits
+        return self._step(tokens, cache, lengths, last_only, fused)
 
     def _speculative(self, tokens: Tensor, max_new_tokens: int, lengths: Optional[Tensor], eos: Optional[int],
                      draft: "TransformerLM", gamma: int, fused: bool = False) -> Tuple[Tensor, Tensor]:

@@ -67,11 +67,16 @@ class Rope:
         self._tables = {}
 
 
+def ln_args(norm: LayerNorm):
+    """The ``ln=(weight, bias, eps)`` prologue of ``ops.linear.linear_rows`` for a LayerNorm module."""
+    return norm.weight, norm.bias, norm.eps
+
+
 class Attention(nn.Module):
     """``causal``: query i attends to keys j <= i; ``key_lengths`` (int32 [B], clamped into [1, N]):
     the keys of batch b at or past its length are hidden (ops/attention.py).
 
-    Incremental decoding (causal only, forward only): with ``cache=(k_cache, v_cache)``, each
+    Incremental decoding (causal only, forward only; ``cached`` holds all of it): with ``cache=(k_cache, v_cache)``, each
     ``[B, H, cap, hd]``, and ``positions`` (int32 [B], the row each sequence writes next), an ``x`` of
     ``[B, 1, dim]`` is one decode step -- its k / v are appended at ``positions`` and the query attends to
     the cache rows ``j <= positions[b]`` -- and an ``x`` of ``[B, N > 1, dim]`` is a prefill: the masked
@@ -113,25 +118,36 @@ class Attention(nn.Module):
 
     def forward(self, x: Tensor, key_lengths: Optional[Tensor] = None, *, cache=None,
                 positions: Optional[Tensor] = None, extend: bool = False) -> Tensor:
-        scale = 1.0 / math.sqrt(self.hd)
+        if cache is not None:
+            return self.proj(self.cached(self.qkv(x), cache, positions, key_lengths, extend=extend))
         kw = {} if self.kv_heads == self.heads else {"kv_heads": self.kv_heads}  # MHA: the calls it always made
-        if cache is None:
-            return self.proj(attention_packed(self.rotate(self.qkv(x)), self.heads, scale, causal=self.causal,
-                                              key_lengths=key_lengths, **kw))
+        return self.proj(attention_packed(self.rotate(self.qkv(x)), self.heads, 1.0 / math.sqrt(self.hd),
+                                          causal=self.causal, key_lengths=key_lengths, **kw))
+
+    def cached(self, qkv: Tensor, cache, positions: Optional[Tensor], key_lengths: Optional[Tensor] = None, *,
+               extend: bool = False, fused: bool = False) -> Tensor:
+        """The cached paths of the class docstring on the packed projection ``qkv`` ``[B, T, (H + 2*Hkv)*hd]``
+        (rotated here, in place) -> ``[B, T, H*hd]``, the input of ``proj``.  ``forward`` and
+        ``Block.forward_rows`` both end here; ``fused`` folds the append of a decode step into its attention
+        (``attention_decode_packed(fused=True)``)."""
         if not self.causal:
             raise ValueError("a KV cache needs causal attention")
         if positions is None:
             raise ValueError("a KV cache needs positions")
         k_cache, v_cache = cache
-        qkv = self.qkv(x)
-        if self.rope is not None:  # a prefill's tokens are at 0 .. N - 1 whatever row they are appended at
-            qkv = self.rotate(qkv, positions if extend or x.shape[1] == 1 else None, inplace=True)
+        scale = 1.0 / math.sqrt(self.hd)
+        kw = {} if self.kv_heads == self.heads else {"kv_heads": self.kv_heads}  # MHA: the calls it always made
+        one = qkv.shape[1] == 1
+        # a prefill's tokens sit at 0 .. N - 1 whatever row they are appended at, a step's at positions[b] + t
+        qkv = self.rotate(qkv, positions if extend or one else None, inplace=True)
+        if one:  # attention_extend_packed would make this very call
+            if fused:
+                return attention_decode_packed(qkv, self.heads, k_cache, v_cache, positions, scale, fused=True, **kw)
+            return attention_decode_packed(qkv, self.heads, k_cache, v_cache, positions, scale, **kw)
         if extend:
-            return self.proj(attention_extend_packed(qkv, self.heads, k_cache, v_cache, positions, scale, **kw))
-        if x.shape[1] == 1:
-            return self.proj(attention_decode_packed(qkv, self.heads, k_cache, v_cache, positions, scale, **kw))
+            return attention_extend_packed(qkv, self.heads, k_cache, v_cache, positions, scale, **kw)
         kv_cache_append(k_cache, v_cache, qkv, self.heads, positions, **kw)
-        return self.proj(attention_packed(qkv, self.heads, scale, causal=True, key_lengths=key_lengths, **kw))
+        return attention_packed(qkv, self.heads, scale, causal=True, key_lengths=key_lengths, **kw)
 
 
 class MLP(nn.Module):
@@ -174,29 +190,17 @@ class Block(nn.Module):
         """The decoding layer on the few-row kernels (ops/linear.py ``linear_rows``; causal, forward only):
         ``x`` ``[B, T, dim]`` is the residual stream itself -- there is no ``pending`` -- and so is the
         result.  Both LayerNorms run as prologues of the product behind them, bias / GELU / residual as
-        epilogues, and with ``T == 1`` the cache append is folded into the decode attention
-        (``attention_decode_packed(fused=True)``): 5 launches with a single-chunk cache, 6 otherwise (one
-        more with rotary positions: the rotation of ``qkv``).
-        ``T > 1`` needs ``extend=True`` and uses ``attention_extend_packed``.  Computes what ``forward``
-        computes with ``cache`` / ``positions`` / ``extend``, to rounding."""
+        epilogues, and the attention is ``Attention.cached(fused=True)``: with ``T == 1`` 5 launches with a
+        single-chunk cache, 6 otherwise (one more with rotary positions: the rotation of ``qkv``).
+        ``T > 1`` needs ``extend=True``.  Computes what ``forward`` computes with ``cache`` / ``positions`` /
+        ``extend``, to rounding."""
         at = self.attn
-        if not at.causal:
-            raise ValueError("a KV cache needs causal attention")
         if x.shape[1] != 1 and not extend:
             raise ValueError("forward_rows: more than one token per sequence needs extend=True")
-        k_cache, v_cache = cache
-        scale = 1.0 / math.sqrt(at.hd)
-        kw = {} if at.kv_heads == at.heads else {"kv_heads": at.kv_heads}
-        qkv = linear_rows(x, at.qkv.weight, at.qkv.bias, ln=(self.ln1.weight, self.ln1.bias, self.ln1.eps))
-        if at.rope is not None:  # one more launch per layer
-            qkv = at.rotate(qkv, positions, inplace=True)
-        if x.shape[1] == 1:
-            a = attention_decode_packed(qkv, at.heads, k_cache, v_cache, positions, scale, fused=True, **kw)
-        else:
-            a = attention_extend_packed(qkv, at.heads, k_cache, v_cache, positions, scale, **kw)
+        qkv = linear_rows(x, at.qkv.weight, at.qkv.bias, ln=ln_args(self.ln1))
+        a = at.cached(qkv, cache, positions, extend=extend, fused=True)
         x = linear_rows(a, at.proj.weight, at.proj.bias, residual=x)
-        h = linear_rows(x, self.mlp.fc1.weight, self.mlp.fc1.bias, ln=(self.ln2.weight, self.ln2.bias, self.ln2.eps),
-                        act="gelu")
+        h = linear_rows(x, self.mlp.fc1.weight, self.mlp.fc1.bias, ln=ln_args(self.ln2), act="gelu")
         return linear_rows(h, self.mlp.fc2.weight, self.mlp.fc2.bias, residual=x)
 
 

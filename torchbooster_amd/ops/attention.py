@@ -227,6 +227,11 @@ def _rows_ok(t: Tensor) -> bool:
     return t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:-1]) and t.data_ptr() % 16 == 0
 
 
+def _rows(t: Tensor) -> Tensor:
+    """``t`` as the native kernels read it: 16-B aligned rows of unit stride, through a copy if need be."""
+    return t if _rows_ok(t) else t.contiguous()
+
+
 def attention(q: Tensor, k: Tensor, v: Tensor, scale: Optional[float] = None, *, causal: bool = False,
               key_lengths: Optional[Tensor] = None) -> Tensor:
     """[B, H, N, D] -> [B, H, N, D].  ``causal`` / ``key_lengths``: the masks of the module docstring
@@ -243,7 +248,7 @@ def attention(q: Tensor, k: Tensor, v: Tensor, scale: Optional[float] = None, *,
         raise ValueError("attention masks need [B, H, N, D] self-attention inputs of one shape")
     _check_lengths(key_lengths, q.shape[0], q)
     if native_supported(q) and q.dim() == 4 and q.shape == k.shape == v.shape:
-        q, k, v = (x if _rows_ok(x) else x.contiguous() for x in (q, k, v))
+        q, k, v = _rows(q), _rows(k), _rows(v)
         return _AttnFn.apply(q, k, v, scale, bool(causal), key_lengths).permute(0, 2, 1, 3)
     return _sdpa(q, k, v, scale, causal, key_lengths)
 
@@ -282,6 +287,20 @@ def attention_packed(qkv: Tensor, heads: int, scale: Optional[float] = None, *, 
 def _forward_only(*tensors: Tensor) -> None:
     if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
         raise RuntimeError("KV-cache decoding is forward-only: call it under torch.no_grad() or detach the inputs")
+
+
+def _packed_dims(qkv: Tensor, heads: int, kv_heads: Optional[int], scale: Optional[float] = None, *,
+                 T: str = "T", even: bool = False):
+    """Validate a packed ``[B, T, (H + 2*Hkv)*D]`` projection -- ``T``: ``"T"`` (any), ``"1"`` or ``"T >= 1"`` --
+    -> ``(hkv, B, T, D, scale)``, ``scale`` defaulting to ``1 / sqrt(D)``."""
+    hkv = _kv_heads(heads, kv_heads)
+    w = heads + 2 * hkv
+    if qkv.dim() == 3:
+        B, n, E = qkv.shape
+        D = E // w
+        if E == D * w and (T == "T" or n == 1 or (n > 1 and T != "1")) and not (even and D % 2):
+            return hkv, B, n, D, 1.0 / math.sqrt(max(D, 1)) if scale is None else float(scale)
+    raise RuntimeError(f"qkv must be [B, {T}, (H + 2*Hkv)*D]" + (" with an even D" if even else ""))
 
 
 def _check_cache(k_cache: Tensor, v_cache: Tensor, B: int, H: int, D: int, pos: Tensor, name: str) -> None:
@@ -342,16 +361,12 @@ def kv_cache_append(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, p
     ``[B, Hkv, cap, D]`` at rows ``positions[b] + t`` (int32 ``[B]``); rows outside ``[0, cap)`` are dropped.
     ``kv_heads``: ``Hkv`` of grouped-query attention (module docstring); ``None`` is ``H``."""
     _forward_only(qkv, k_cache, v_cache)
-    hkv = _kv_heads(heads, kv_heads)
-    if qkv.dim() != 3 or qkv.shape[2] % (heads + 2 * hkv):
-        raise RuntimeError("qkv must be [B, T, (H + 2*Hkv)*D]")
-    B, T, E3 = qkv.shape
+    hkv, B, _, D, _ = _packed_dims(qkv, heads, kv_heads)
     with torch.no_grad():
         if _decode_native(qkv, k_cache, v_cache):
-            qkv = qkv if _rows_ok(qkv) else qkv.contiguous()
-            native().attn_kv_append(qkv, heads, k_cache, v_cache, positions, hkv)
+            native().attn_kv_append(_rows(qkv), heads, k_cache, v_cache, positions, hkv)
             return
-        _check_cache(k_cache, v_cache, B, hkv, E3 // (heads + 2 * hkv), positions, "positions")
+        _check_cache(k_cache, v_cache, B, hkv, D, positions, "positions")
         _append_ref(k_cache, v_cache, qkv, heads, positions, hkv)
 
 
@@ -368,8 +383,7 @@ def attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tenso
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     with torch.no_grad():
         if _decode_native(q, k_cache, v_cache):
-            q = q if _rows_ok(q) else q.contiguous()
-            return native().attn_decode(q, H, k_cache, v_cache, lengths, 0, scale, None, hkv).view(B, H, D)
+            return native().attn_decode(_rows(q), H, k_cache, v_cache, lengths, 0, scale, None, hkv).view(B, H, D)
         _check_cache(k_cache, v_cache, B, hkv, D, lengths, "lengths")
         return _decode_ref(q, k_cache, v_cache, lengths, scale)
 
@@ -386,16 +400,10 @@ def attention_decode_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: T
     chunk is normalised there too, so a step is one or two launches instead of three.  Output and caches
     have the bits of ``fused=False``."""
     _forward_only(qkv, k_cache, v_cache)
-    hkv = _kv_heads(heads, kv_heads)
-    if qkv.dim() != 3 or qkv.shape[1] != 1 or qkv.shape[2] % (heads + 2 * hkv):
-        raise RuntimeError("qkv must be [B, 1, (H + 2*Hkv)*D]")
-    B, _, E3 = qkv.shape
-    D = E3 // (heads + 2 * hkv)
-    scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
+    hkv, B, _, D, scale = _packed_dims(qkv, heads, kv_heads, scale, T="1")
     with torch.no_grad():
         if _decode_native(qkv, k_cache, v_cache):
-            qkv = qkv if _rows_ok(qkv) else qkv.contiguous()
-            C = native()
+            qkv, C = _rows(qkv), native()
             if fused:
                 return C.attn_decode_append(qkv, heads, k_cache, v_cache, positions, scale,
                                             hkv).view(B, 1, heads * D)
@@ -451,8 +459,7 @@ def attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Ten
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     with torch.no_grad():
         if _decode_native(q, k_cache, v_cache):
-            q = q if _rows_ok(q) else q.contiguous()
-            return native().attn_extend(q, k_cache, v_cache, positions, scale, None, hkv).view(B, T, H, D)
+            return native().attn_extend(_rows(q), k_cache, v_cache, positions, scale, None, hkv).view(B, T, H, D)
         _check_cache(k_cache, v_cache, B, hkv, D, positions, "positions")
         return _extend_ref(q, k_cache, v_cache, positions, scale)
 
@@ -464,19 +471,14 @@ def attention_extend_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: T
     ``j < clamp(positions[b] + t + 1, 1, cap)`` -> ``[B, T, H*D]``.  ``T == 1`` is
     :func:`attention_decode_packed`.  What may enter arithmetic: see :func:`attention_extend`.
     ``kv_heads``: ``Hkv`` of grouped-query attention (module docstring); ``None`` is ``H``."""
-    hkv = _kv_heads(heads, kv_heads)
-    if qkv.dim() != 3 or qkv.shape[1] < 1 or qkv.shape[2] % (heads + 2 * hkv):
-        raise RuntimeError("qkv must be [B, T >= 1, (H + 2*Hkv)*D]")
-    B, T, E3 = qkv.shape
-    if T == 1:
+    dims = _packed_dims(qkv, heads, kv_heads, scale, T="T >= 1")
+    if dims[2] == 1:
         return attention_decode_packed(qkv, heads, k_cache, v_cache, positions, scale, kv_heads=kv_heads)
     _forward_only(qkv, k_cache, v_cache)
-    D = E3 // (heads + 2 * hkv)
-    scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
+    hkv, B, T, D, scale = dims
     with torch.no_grad():
         if _decode_native(qkv, k_cache, v_cache):
-            qkv = qkv if _rows_ok(qkv) else qkv.contiguous()
-            C = native()
+            qkv, C = _rows(qkv), native()
             C.attn_kv_append(qkv, heads, k_cache, v_cache, positions, hkv)
             q = qkv[..., :heads * D].view(B, T, heads, D)
             return C.attn_extend(q, k_cache, v_cache, positions, scale, None, hkv)
@@ -587,11 +589,7 @@ def rope_packed(qkv: Tensor, heads: int, table: Tensor, positions: Optional[Tens
     Out of place it is differentiable w.r.t. ``qkv``: the gradient is ``rope_packed(grad, ...,
     inverse=not inverse)``, a new tensor; the table and the positions get none.  ``inplace=True`` is
     forward-only and raises if ``qkv`` requires grad in grad mode."""
-    hkv = _kv_heads(heads, kv_heads)
-    if qkv.dim() != 3 or qkv.shape[2] % (heads + 2 * hkv) or (qkv.shape[2] // (heads + 2 * hkv)) % 2:
-        raise RuntimeError("qkv must be [B, T, (H + 2*Hkv)*D] with an even D")
-    B, T, E = qkv.shape
-    D = E // (heads + 2 * hkv)
+    hkv, B, _, D, _ = _packed_dims(qkv, heads, kv_heads, even=True)
     if table.dim() != 3 or table.shape[1] != 2 or table.shape[2] != D // 2 or table.shape[0] < 1:
         raise RuntimeError(f"table must be [max_len, 2, D // 2 = {D // 2}], not {tuple(table.shape)}")
     if table.device != qkv.device:
