@@ -224,17 +224,21 @@ Tensor attn_decode_append(const Tensor& qkv, int64_t heads, const Tensor& k_cach
 
 // ------------------------------------------------------------ few-row products (csrc/rows_gemm.hip)
 // x [M, K] bf16 (1 <= M <= 16, unit column stride, row stride a multiple of 8) . weight [Q, K]^T ->
-// [M, Q].  gamma / beta: f32 [K] LayerNorm prologue (both or neither); epi: 0 none, 1 GELU, 2
-// + residual [M, Q].  out (optional, tests): contiguous bf16 [M, Q] written instead of a fresh tensor.
+// [M, Q].  gamma / beta: f32 [K] LayerNorm prologue (both or neither); rms: gamma alone, the RMSNorm
+// prologue; epi: 0 none, 1 GELU, 2 + residual [M, Q], 3 SwiGLU (weight [2Q, K] gate | up rows, bias
+// [2Q], result [M, Q]).  out (optional, tests): contiguous bf16 [M, Q] written instead of a fresh tensor.
 Tensor rows_linear(const Tensor& x, const Tensor& weight, const optional<Tensor>& bias, const optional<Tensor>& gamma,
                    const optional<Tensor>& beta, double eps, int64_t epi, const optional<Tensor>& residual,
-                   const optional<Tensor>& out) {
+                   const optional<Tensor>& out, bool rms) {
   const at::DeviceGuard guard = on_device_of(x, "x");
   check_cuda(weight, "weight");
   TORCH_CHECK(x.scalar_type() == at::kBFloat16 && weight.scalar_type() == at::kBFloat16, "rows_linear: bf16 only");
   TORCH_CHECK(x.dim() == 2 && weight.dim() == 2 && weight.is_contiguous() && weight.device() == x.device(),
               "rows_linear: x [M, K], weight [Q, K] contiguous, on one device");
-  const int64_t M = x.size(0), K = x.size(1), Q = weight.size(0);
+  TORCH_CHECK(epi >= 0 && epi <= 3, "rows_linear: epilogue 0 (none), 1 (gelu), 2 (residual) or 3 (swiglu)");
+  const bool glu = epi == tbamd::kRowsSwiglu;
+  TORCH_CHECK(!glu || weight.size(0) % 2 == 0, "rows_linear: the swiglu epilogue needs weight [2F, K]");
+  const int64_t M = x.size(0), K = x.size(1), WQ = weight.size(0), Q = glu ? WQ / 2 : WQ;
   TORCH_CHECK(M >= 1 && M <= 16 && K % 8 == 0 && K >= 8 && K <= 4096 && weight.size(1) == K && Q >= 1 &&
                   Q < (int64_t)INT32_MAX / 16,
               "rows_linear: 1 <= M <= 16, K % 8 == 0, K <= 4096");
@@ -242,21 +246,29 @@ Tensor rows_linear(const Tensor& x, const Tensor& weight, const optional<Tensor>
                   reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
                   reinterpret_cast<uintptr_t>(weight.data_ptr()) % 16 == 0,
               "rows_linear: rows must be 16-B aligned with a unit column stride");
-  TORCH_CHECK(epi >= 0 && epi <= 2, "rows_linear: epilogue 0 (none), 1 (gelu) or 2 (residual)");
   tbamd::RowsLinearArgs a{};
   a.x = reinterpret_cast<const uint16_t*>(x.data_ptr());
   a.w = reinterpret_cast<const uint16_t*>(weight.data_ptr());
   a.sx = M == 1 ? 0 : x.stride(0);
   if (given(bias)) {
     check_cuda(*bias, "bias");
-    TORCH_CHECK(bias->scalar_type() == at::kBFloat16 && bias->dim() == 1 && bias->size(0) == Q &&
+    TORCH_CHECK(bias->scalar_type() == at::kBFloat16 && bias->dim() == 1 && bias->size(0) == WQ &&
                     bias->is_contiguous() && bias->device() == x.device(),
-                "rows_linear: bias must be contiguous bf16 [Q]");
+                "rows_linear: bias must be contiguous bf16 [Q] ([2F] under swiglu)");
     a.bias = reinterpret_cast<const uint16_t*>(bias->data_ptr());
   }
   const bool ln = given(gamma);
-  TORCH_CHECK(ln == given(beta), "rows_linear: gamma and beta come together");
-  if (ln) {
+  TORCH_CHECK(rms ? (ln && !given(beta)) : ln == given(beta),
+              "rows_linear: gamma and beta come together (LayerNorm), or gamma alone with rms");
+  if (rms) {
+    const Tensor* t = &*gamma;
+    check_cuda(*t, "gamma");
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->dim() == 1 && t->size(0) == K && t->is_contiguous() &&
+                    t->device() == x.device() && reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "rows_linear: gamma must be contiguous, 16-B aligned f32 [K]");
+    a.gamma = gamma->data_ptr<float>();
+    a.rms = 1;
+  } else if (ln) {
     for (const Tensor* t : {&*gamma, &*beta}) {
       check_cuda(*t, "gamma / beta");
       TORCH_CHECK(t->scalar_type() == at::kFloat && t->dim() == 1 && t->size(0) == K && t->is_contiguous() &&
@@ -276,6 +288,7 @@ Tensor rows_linear(const Tensor& x, const Tensor& weight, const optional<Tensor>
   } else {
     y = at::empty({M, Q}, x.options());
   }
+  TORCH_CHECK(!glu || !given(residual), "rows_linear: the swiglu epilogue takes no residual");
   if (epi == 2) {
     TORCH_CHECK(given(residual), "rows_linear: the residual epilogue needs a residual");
     const Tensor& r = *residual;
@@ -433,7 +446,12 @@ void register_attn(pybind11::module& m) {
         py::arg("v_cache"), py::arg("positions"), py::arg("scale"), py::arg("kv_heads") = 0);
   m.def("rows_linear", &rows_linear, py::arg("x"), py::arg("weight"), py::arg("bias") = py::none(),
         py::arg("gamma") = py::none(), py::arg("beta") = py::none(), py::arg("eps") = 0.0, py::arg("epi") = 0,
-        py::arg("residual") = py::none(), py::arg("out") = py::none());
+        py::arg("residual") = py::none(), py::arg("out") = py::none(), py::arg("rms") = false);
+  // test helper (tests/test_gpu_llama_block.py checks that its shapes reach every launcher setting)
+  m.def("rows_swiglu_cols_per_wave", [](int64_t F) {
+    TORCH_CHECK(F >= 1 && F < (int64_t)INT32_MAX / 32, "rows_swiglu_cols_per_wave: bad F");
+    return (int64_t)tbamd::rows_swiglu_cols_per_wave((int)F);
+  });
   m.def("embed_rows", &embed_rows, py::arg("tokens"), py::arg("tok_weight"), py::arg("pos_weight") = py::none(),
         py::arg("positions") = py::none());
   m.def("rope_packed", &rope_packed, py::arg("qkv"), py::arg("heads"), py::arg("table"),

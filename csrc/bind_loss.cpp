@@ -147,6 +147,44 @@ Tensor act_bwd(const Tensor& x_, const Tensor& dy_, int64_t act, double slope) {
   return dx;
 }
 
+// ---- SwiGLU gate (csrc/swiglu.hip).  gu: [M, 2F] packed gate | up rows, bf16 or f32, unit column
+// stride, 16-B aligned rows (any row stride that keeps them so), F % 8 == 0 -> y [M, F] contiguous.
+static int64_t swiglu_rows(const Tensor& gu, const char* what) {
+  check_cuda(gu, "gu");
+  TORCH_CHECK(gu.scalar_type() == at::kBFloat16 || gu.scalar_type() == at::kFloat, what, ": bf16 or f32 only");
+  TORCH_CHECK(gu.dim() == 2 && gu.size(1) % 16 == 0 && gu.size(1) >= 16 && gu.size(1) < (int64_t)INT32_MAX,
+              what, ": gu must be [M, 2F] with F % 8 == 0");
+  const int64_t es = gu.element_size();
+  TORCH_CHECK(gu.stride(1) == 1 && (gu.size(0) <= 1 || (gu.stride(0) >= gu.size(1) && gu.stride(0) * es % 16 == 0)) &&
+                  reinterpret_cast<uintptr_t>(gu.data_ptr()) % 16 == 0,
+              what, ": rows must be 16-B aligned with a unit column stride");
+  return gu.size(0) <= 1 ? gu.size(1) : gu.stride(0);
+}
+
+Tensor swiglu_fwd(const Tensor& gu) {
+  const at::DeviceGuard guard = on_device_of(gu, "gu");
+  const int64_t sgu = swiglu_rows(gu, "swiglu_fwd");
+  const int64_t M = gu.size(0), F = gu.size(1) / 2;
+  Tensor y = at::empty({M, F}, gu.options().memory_format(at::MemoryFormat::Contiguous));
+  tbamd::swiglu_forward(dt_code(gu), gu.data_ptr(), sgu, M, (int)F, y.data_ptr(), cur_stream());
+  return y;
+}
+
+// dy [M, F] contiguous, the dtype of gu -> dgu [M, 2F] contiguous (dgate | dup), recomputed from gu
+Tensor swiglu_bwd(const Tensor& gu, const Tensor& dy) {
+  const at::DeviceGuard guard = on_device_of(gu, "gu");
+  const int64_t sgu = swiglu_rows(gu, "swiglu_bwd");
+  const int64_t M = gu.size(0), F = gu.size(1) / 2;
+  check_cuda(dy, "dy");
+  TORCH_CHECK(dy.scalar_type() == gu.scalar_type() && dy.dim() == 2 && dy.size(0) == M && dy.size(1) == F &&
+                  dy.is_contiguous() && dy.device() == gu.device() &&
+                  reinterpret_cast<uintptr_t>(dy.data_ptr()) % 16 == 0,
+              "swiglu_bwd: dy must be contiguous, 16-B aligned [M, F] in the dtype and on the device of gu");
+  Tensor dgu = at::empty({M, 2 * F}, gu.options().memory_format(at::MemoryFormat::Contiguous));
+  tbamd::swiglu_backward(dt_code(gu), gu.data_ptr(), sgu, dy.data_ptr(), M, (int)F, dgu.data_ptr(), cur_stream());
+  return dgu;
+}
+
 Tensor hinge_forward(const Tensor& x_, double margin, double sign) {
   const at::DeviceGuard guard = on_device_of(x_, "x");
   Tensor x = x_.contiguous();
@@ -335,6 +373,8 @@ void register_loss(pybind11::module& m) {
   m.def("tv_backward", &tv_backward);
   m.def("act_fwd", &act_fwd, py::arg("x"), py::arg("act"), py::arg("slope") = 0.01);
   m.def("act_bwd", &act_bwd, py::arg("x"), py::arg("dy"), py::arg("act"), py::arg("slope") = 0.01);
+  m.def("swiglu_fwd", &swiglu_fwd, py::arg("gu"));
+  m.def("swiglu_bwd", &swiglu_bwd, py::arg("gu"), py::arg("dy"));
   m.def("hinge_forward", &hinge_forward);
   m.def("hinge_backward", &hinge_backward);
   m.def("bce_logits_forward", &bce_logits_forward);

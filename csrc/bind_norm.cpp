@@ -494,6 +494,67 @@ std::vector<Tensor> ln_backward(const Tensor& dy_, const Tensor& x_, const optio
   return {dx, dg, db};
 }
 
+// --------------------------------------------------------------- RMSNorm (csrc/layernorm.hip, RMS = true)
+// returns {y, xsum (x + residual, or undefined), rstd}
+std::vector<Tensor> rms_forward(const Tensor& x_, const optional<Tensor>& residual, const optional<Tensor>& weight,
+                                double eps) {
+  const at::DeviceGuard guard = on_device_of(x_, "x");
+  Tensor x = as_rows(x_);
+  TORCH_CHECK(x.dim() == 2, "rms_forward: x must be [M, C]");
+  const int64_t M = x.size(0);
+  const int C = (int)x.size(1);
+  TORCH_CHECK(C % 8 == 0 && C >= 8 && C <= 4096, "rms_forward: C % 8 == 0 and C <= 4096");
+  Tensor res, xsum;
+  if (given(residual)) {
+    res = as_rows(residual->to(x.scalar_type()));
+    TORCH_CHECK(res.dim() == 2 && res.size(0) == M && res.size(1) == C, "rms_forward: residual shape");
+    xsum = at::empty_like(x);
+  }
+  Tensor wf = f32_or_undef(weight);
+  TORCH_CHECK(!wf.defined() || wf.numel() == C, "rms_forward: weight must be [C]");
+  Tensor rstd = at::empty({M}, x.options().dtype(at::kFloat));
+  Tensor y = at::empty_like(x);
+  if (M > 0)
+    tbamd::rms_forward(dt_code(x), x.data_ptr(), ptr_or_null(res), f32_or_null(wf), M, C, (float)eps, y.data_ptr(),
+                       ptr_or_null(xsum), rstd.data_ptr<float>(), cur_stream());
+  return {y, xsum, rstd};
+}
+
+// dadd (optional, same shape as x): added to dx in the kernel (residual-stream gradient)
+std::vector<Tensor> rms_backward(const Tensor& dy_, const Tensor& x_, const optional<Tensor>& weight,
+                                 const Tensor& rstd, const optional<Tensor>& dadd_,
+                                 const optional<Tensor>& dgamma_out) {
+  const at::DeviceGuard guard = on_device_of(dy_, "dy");
+  Tensor x = as_rows(x_);
+  Tensor dy = as_rows(dy_.to(x.scalar_type()));
+  TORCH_CHECK(x.dim() == 2 && dy.sizes() == x.sizes(), "rms_backward: dy must match x [M, C]");
+  const int64_t M = x.size(0);
+  const int C = (int)x.size(1);
+  TORCH_CHECK(C % 8 == 0 && C >= 8 && C <= 4096, "rms_backward: C % 8 == 0 and C <= 4096");
+  check_cuda(rstd, "rstd");
+  TORCH_CHECK(rstd.scalar_type() == at::kFloat && rstd.numel() == M && rstd.is_contiguous(),
+              "rms_backward: rstd must be contiguous f32 [M]");
+  Tensor wf = f32_or_undef(weight);
+  TORCH_CHECK(!wf.defined() || wf.numel() == C, "rms_backward: weight must be [C]");
+  auto fopt = x.options().dtype(at::kFloat);
+  const int nblk = tbamd::ln_bwd_blocks(M);
+  Tensor ws = at::empty({(int64_t)nblk, C}, fopt);
+  Tensor dg = slot_or_new(dgamma_out, C, fopt, "rms_backward");
+  Tensor dx = at::empty_like(x);
+  Tensor dadd;
+  if (given(dadd_)) {
+    dadd = as_rows(dadd_->to(x.scalar_type()));
+    TORCH_CHECK(dadd.dim() == 2 && dadd.size(0) == M && dadd.size(1) == C, "rms_backward: dadd shape");
+  }
+  if (M > 0)
+    tbamd::rms_backward(dt_code(x), dy.data_ptr(), x.data_ptr(), ptr_or_null(dadd), f32_or_null(wf),
+                        rstd.data_ptr<float>(), M, C, dx.data_ptr(), ws.data_ptr<float>(), nblk,
+                        dg.data_ptr<float>(), cur_stream());
+  else
+    dg.zero_();
+  return {dx, dg};
+}
+
 // ---------------------------------------------------------------- global average pool (K7)
 // x [N, C, H, W] channels_last (C % 8 == 0) -> [N, C]
 Tensor global_avgpool(const Tensor& x_) {
@@ -571,6 +632,9 @@ void register_norm(pybind11::module& m) {
   m.def("ln_backward", &ln_backward, py::arg("dy"), py::arg("x"), py::arg("weight"), py::arg("mean"),
         py::arg("rstd"), py::arg("dadd") = py::none(), py::arg("dgamma_out") = py::none(),
         py::arg("dbeta_out") = py::none());
+  m.def("rms_forward", &rms_forward, py::arg("x"), py::arg("residual"), py::arg("weight"), py::arg("eps"));
+  m.def("rms_backward", &rms_backward, py::arg("dy"), py::arg("x"), py::arg("weight"), py::arg("rstd"),
+        py::arg("dadd") = py::none(), py::arg("dgamma_out") = py::none());
   m.def("global_avgpool", &global_avgpool);
   m.def("global_avgpool_backward", &global_avgpool_backward);
 }

@@ -3,6 +3,10 @@
 // variance), 16-B vector loads; backward reduces dgamma/dbeta per workgroup
 // into [nblk][C] partials merged by a second kernel (deterministic).
 //
+// RMSNorm (y = x * rsqrt(mean(x^2) + eps) * gamma, no beta) is the RMS = true instantiation of the
+// same two kernels: the same row-group layout, one pass over the registers for the statistic, rstd
+// the only thing saved.  The RMS = false instantiations are the LayerNorm arithmetic unchanged.
+//
 // Needed by the ViT-B/16 north-star config (BASELINE.json config 5); the
 // reference has no transformer.
 #include "common.h"
@@ -90,7 +94,8 @@ template <> struct Raw8<kF32> {
 };
 
 // RM: rows per group fixed at compile time (1/2/4/8), or 0 = runtime R <= kLnMaxR
-template <int DT, int NCH, int RM>
+// RMS: RMSNorm (beta and mean_out are not touched)
+template <int DT, int NCH, int RM, bool RMS>
 __global__ __launch_bounds__(64 * kLnWaves) void ln_fwd_k(const storage_t<DT>* __restrict__ x,
                                                           const storage_t<DT>* __restrict__ res,
                                                           const float* __restrict__ gamma,
@@ -117,7 +122,8 @@ __global__ __launch_bounds__(64 * kLnWaves) void ln_fwd_k(const storage_t<DT>* _
         b[i][k] = 0.f;
       }
       if (sl[i].on && gamma) load8f(gamma + sl[i].vi * 8, g[i]);
-      if (sl[i].on && beta) load8f(beta + sl[i].vi * 8, b[i]);
+      if constexpr (!RMS)
+        if (sl[i].on && beta) load8f(beta + sl[i].vi * 8, b[i]);
     }
   }
   const int64_t ngroups = (M + R - 1) / R;
@@ -162,23 +168,28 @@ __global__ __launch_bounds__(64 * kLnWaves) void ln_fwd_k(const storage_t<DT>* _
           Vec8<DT>::store(xsum + off, v[i]);
         }
 #pragma unroll
-        for (int k = 0; k < 8; ++k) part[i] += v[i][k];
+        for (int k = 0; k < 8; ++k) part[i] += RMS ? v[i][k] * v[i][k] : v[i][k];
       }
     }
     float mean[RB], rstd[RB];
-    ln_row_sums<NCH, RB>(part, sl, R, mean);
-#pragma unroll
-    for (int rr = 0; rr < RB; ++rr) mean[rr] *= 1.f / (float)C;
     float mu[NCH];
+    if constexpr (RMS) {  // the row is in registers: one pass, sum of squares
 #pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      mu[i] = ln_pick<RB>(mean, sl[i].r);
-      part[i] = 0.f;
-      if (ok[i]) {
+      for (int i = 0; i < NCH; ++i) mu[i] = 0.f;
+    } else {
+      ln_row_sums<NCH, RB>(part, sl, R, mean);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const float d = v[i][k] - mu[i];
-          part[i] += d * d;
+      for (int rr = 0; rr < RB; ++rr) mean[rr] *= 1.f / (float)C;
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) {
+        mu[i] = ln_pick<RB>(mean, sl[i].r);
+        part[i] = 0.f;
+        if (ok[i]) {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            const float d = v[i][k] - mu[i];
+            part[i] += d * d;
+          }
         }
       }
     }
@@ -186,7 +197,7 @@ __global__ __launch_bounds__(64 * kLnWaves) void ln_fwd_k(const storage_t<DT>* _
 #pragma unroll
     for (int rr = 0; rr < RB; ++rr) rstd[rr] = rsqrtf(rstd[rr] * (1.f / (float)C) + eps);
     if (lane < R && r0 + lane < M) {
-      mean_out[r0 + lane] = ln_pick<RB>(mean, lane);
+      if constexpr (!RMS) mean_out[r0 + lane] = ln_pick<RB>(mean, lane);
       rstd_out[r0 + lane] = ln_pick<RB>(rstd, lane);
     }
 #pragma unroll
@@ -207,11 +218,15 @@ __global__ __launch_bounds__(64 * kLnWaves) void ln_fwd_k(const storage_t<DT>* _
             bb[k] = 0.f;
           }
           if (gamma) load8f(gamma + sl[i].vi * 8, gg);
-          if (beta) load8f(beta + sl[i].vi * 8, bb);
+          if constexpr (!RMS)
+            if (beta) load8f(beta + sl[i].vi * 8, bb);
         }
         float o[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = (v[i][k] - mu[i]) * rs * gg[k] + bb[k];
+        for (int k = 0; k < 8; ++k) {
+          if constexpr (RMS) o[k] = v[i][k] * rs * gg[k];
+          else o[k] = (v[i][k] - mu[i]) * rs * gg[k] + bb[k];
+        }
         Vec8<DT>::store(y + (r0 + sl[i].r) * C + sl[i].vi * 8, o);
       }
     }
@@ -228,7 +243,9 @@ __global__ __launch_bounds__(64 * kLnWaves) void ln_fwd_k(const storage_t<DT>* _
 // dx = rstd * (g*dy - mean(g*dy) - xhat * mean(g*dy*xhat)) [+ dadd]; per-workgroup
 // column partials of dgamma = sum dy*xhat and dbeta = sum dy, merged into
 // [blk][C] in a fixed order (waves in turn, row slots in turn): deterministic.
-template <int DT, int NCH, int RM>
+// RMS: dx = rstd * (g*dy - xhat * mean(g*dy*xhat)) [+ dadd] with xhat = x * rstd, and dgamma alone
+// (mean_in and pdb are not touched).
+template <int DT, int NCH, int RM, bool RMS>
 __global__ __launch_bounds__(64 * kLnWaves) void ln_bwd_k(const storage_t<DT>* __restrict__ dy,
                                                           const storage_t<DT>* __restrict__ x,
                                                           const storage_t<DT>* __restrict__ dadd,
@@ -294,7 +311,8 @@ __global__ __launch_bounds__(64 * kLnWaves) void ln_bwd_k(const storage_t<DT>* _
 #pragma unroll
     for (int rr = 0; rr < RB; ++rr) {
       const bool in = rr < R && r0 + rr < M;
-      mrow[rr] = in ? mean_in[r0 + rr] : 0.f;
+      if constexpr (RMS) mrow[rr] = 0.f;
+      else mrow[rr] = in ? mean_in[r0 + rr] : 0.f;
       rrow[rr] = in ? rstd_in[r0 + rr] : 0.f;
     }
 #pragma unroll
@@ -318,17 +336,23 @@ __global__ __launch_bounds__(64 * kLnWaves) void ln_bwd_k(const storage_t<DT>* _
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           const float dv = dvv[k];
-          xh[i][k] = (xv[k] - mu) * rs;
+          if constexpr (RMS) xh[i][k] = xv[k] * rs;
+          else xh[i][k] = (xv[k] - mu) * rs;
           gd[i][k] = dv * gg[k];
-          p1[i] += gd[i][k];
+          if constexpr (!RMS) p1[i] += gd[i][k];
           p2[i] += gd[i][k] * xh[i][k];
           ag[i][k] += dv * xh[i][k];
-          ab[i][k] += dv;
+          if constexpr (!RMS) ab[i][k] += dv;
         }
       }
     }
     float s1[RB], s2[RB];
-    ln_row_sums<NCH, RB>(p1, sl, R, s1);
+    if constexpr (RMS) {
+#pragma unroll
+      for (int rr = 0; rr < RB; ++rr) s1[rr] = 0.f;
+    } else {
+      ln_row_sums<NCH, RB>(p1, sl, R, s1);
+    }
     ln_row_sums<NCH, RB>(p2, sl, R, s2);
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
@@ -339,7 +363,10 @@ __global__ __launch_bounds__(64 * kLnWaves) void ln_bwd_k(const storage_t<DT>* _
         const float rs = ln_pick<RB>(rrow, sl[i].r);
         float o[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = rs * (gd[i][k] - a1 - xh[i][k] * a2);
+        for (int k = 0; k < 8; ++k) {
+          if constexpr (RMS) o[k] = rs * (gd[i][k] - xh[i][k] * a2);
+          else o[k] = rs * (gd[i][k] - a1 - xh[i][k] * a2);
+        }
         if (dadd) {
           float av[8];
           ac[i].unpack(av);
@@ -370,7 +397,7 @@ __global__ __launch_bounds__(64 * kLnWaves) void ln_bwd_k(const storage_t<DT>* _
         for (int k = 0; k < 8; ++k) {
           const int a = (i * 64 + lane) * 8 + k;
           red[0][a] = (w ? red[0][a] : 0.f) + ag[i][k];
-          red[1][a] = (w ? red[1][a] : 0.f) + ab[i][k];
+          if constexpr (!RMS) red[1][a] = (w ? red[1][a] : 0.f) + ab[i][k];
         }
     }
     __syncthreads();
@@ -380,16 +407,16 @@ __global__ __launch_bounds__(64 * kLnWaves) void ln_bwd_k(const storage_t<DT>* _
     for (int rr = 0; rr < R; ++rr) {
       const int a = (rr * nv + (c >> 3)) * 8 + (c & 7);
       tg += red[0][a];
-      tb += red[1][a];
+      if constexpr (!RMS) tb += red[1][a];
     }
     pdg[(int64_t)blockIdx.x * C + c] = tg;
-    pdb[(int64_t)blockIdx.x * C + c] = tb;
+    if constexpr (!RMS) pdb[(int64_t)blockIdx.x * C + c] = tb;
   }
 }
 
 // column sums of two [nblk][C] partial arrays: one workgroup per 64 columns,
 // 16 row-groups per workgroup (each strides the rows), f64 accumulation, then a
-// fixed-order LDS merge (deterministic).  Was one thread per column: 3
+// fixed-order LDS merge (deterministic); b may be null (RMSNorm: dgamma alone).  Was one thread per column: 3
 // workgroups for C = 768 and a 1024-long dependent loop each (0.23 ms/call).
 constexpr int kColRG = 16;
 __global__ __launch_bounds__(64 * kColRG) void col_sum2_k(const float* __restrict__ a, const float* __restrict__ b,
@@ -403,7 +430,7 @@ __global__ __launch_bounds__(64 * kColRG) void col_sum2_k(const float* __restric
 #pragma unroll 4
     for (int i = ty; i < nblk; i += kColRG) {
       sa += a[(int64_t)i * C + c];
-      sb += b[(int64_t)i * C + c];
+      if (b) sb += b[(int64_t)i * C + c];
     }
   }
   red[0][ty][tx] = sa;
@@ -465,15 +492,16 @@ int ln_bwd_blocks(int64_t M) {
   else if (nch == 7) L(7, 0);                                        \
   else L(8, 0)
 
-#define TB_LNF(NCH_, RM_)                                                                                   \
-  ln_fwd_k<DT, NCH_, RM_><<<(int)nblk, 64 * kLnWaves, 0, st>>>((const T*)x, (const T*)res, gamma, beta, M, C, R, \
-                                                               eps, (T*)y, (T*)xsum, mean, rstd)
-#define TB_LNB(NCH_, RM_)                                                                                    \
-  ln_bwd_k<DT, NCH_, RM_><<<nblk, 64 * kLnWaves, 0, st>>>((const T*)dy, (const T*)x, (const T*)dadd, gamma, mean, \
-                                                          rstd, M, C, R, gpb, (T*)dx, pdg, pdb)
+#define TB_LNF(NCH_, RM_)                                                                                 \
+  ln_fwd_k<DT, NCH_, RM_, RMS><<<(int)nblk, 64 * kLnWaves, 0, st>>>((const T*)x, (const T*)res, gamma, beta, M, \
+                                                                    C, R, eps, (T*)y, (T*)xsum, mean, rstd)
+#define TB_LNB(NCH_, RM_)                                                                                  \
+  ln_bwd_k<DT, NCH_, RM_, RMS><<<nblk, 64 * kLnWaves, 0, st>>>((const T*)dy, (const T*)x, (const T*)dadd, gamma, \
+                                                               mean, rstd, M, C, R, gpb, (T*)dx, pdg, pdb)
 
-void ln_forward(int dt, const void* x, const void* res, const float* gamma, const float* beta, int64_t M, int C,
-                float eps, void* y, void* xsum, float* mean, float* rstd, hipStream_t st) {
+template <bool RMS>
+static void ln_forward_t(int dt, const void* x, const void* res, const float* gamma, const float* beta, int64_t M,
+                         int C, float eps, void* y, void* xsum, float* mean, float* rstd, hipStream_t st) {
   int R, nch;
   ln_shape(C, R, nch);
   const int64_t ngroups = (M + R - 1) / R;
@@ -485,9 +513,10 @@ void ln_forward(int dt, const void* x, const void* res, const float* gamma, cons
   });
 }
 
-void ln_backward(int dt, const void* dy, const void* x, const void* dadd, const float* gamma, const float* mean,
-                 const float* rstd, int64_t M, int C, void* dx, float* pdg, float* pdb, int nblk, float* dgamma,
-                 float* dbeta, hipStream_t st) {
+template <bool RMS>
+static void ln_backward_t(int dt, const void* dy, const void* x, const void* dadd, const float* gamma,
+                          const float* mean, const float* rstd, int64_t M, int C, void* dx, float* pdg, float* pdb,
+                          int nblk, float* dgamma, float* dbeta, hipStream_t st) {
   int R, nch;
   ln_shape(C, R, nch);
   const int64_t ngroups = (M + R - 1) / R;
@@ -502,5 +531,26 @@ void ln_backward(int dt, const void* dy, const void* x, const void* dadd, const 
 #undef TB_LNF
 #undef TB_LNB
 #undef TBAMD_LN_SHAPES
+
+void ln_forward(int dt, const void* x, const void* res, const float* gamma, const float* beta, int64_t M, int C,
+                float eps, void* y, void* xsum, float* mean, float* rstd, hipStream_t st) {
+  ln_forward_t<false>(dt, x, res, gamma, beta, M, C, eps, y, xsum, mean, rstd, st);
+}
+
+void ln_backward(int dt, const void* dy, const void* x, const void* dadd, const float* gamma, const float* mean,
+                 const float* rstd, int64_t M, int C, void* dx, float* pdg, float* pdb, int nblk, float* dgamma,
+                 float* dbeta, hipStream_t st) {
+  ln_backward_t<false>(dt, dy, x, dadd, gamma, mean, rstd, M, C, dx, pdg, pdb, nblk, dgamma, dbeta, st);
+}
+
+void rms_forward(int dt, const void* x, const void* res, const float* gamma, int64_t M, int C, float eps, void* y,
+                 void* xsum, float* rstd, hipStream_t st) {
+  ln_forward_t<true>(dt, x, res, gamma, nullptr, M, C, eps, y, xsum, nullptr, rstd, st);
+}
+
+void rms_backward(int dt, const void* dy, const void* x, const void* dadd, const float* gamma, const float* rstd,
+                  int64_t M, int C, void* dx, float* pdg, int nblk, float* dgamma, hipStream_t st) {
+  ln_backward_t<true>(dt, dy, x, dadd, gamma, nullptr, rstd, M, C, dx, pdg, nullptr, nblk, dgamma, nullptr, st);
+}
 
 }  // namespace tbamd

@@ -21,6 +21,14 @@
 //                   cost about that many shuffles instead of six times as many.  The lane left
 //                   holding (column, row) applies bias, GELU or the residual to the f32 sum and
 //                   stores one bf16.
+//                   RMSNorm prologue (rms): the same place and shape as the LayerNorm one, one pass
+//                   for the f32 mean of squares, x * rstd * gamma rounded to bf16 as the separate
+//                   RMSNorm kernel rounds it.
+//                   SwiGLU epilogue (GLU): W is [2Q][K], gate rows then up rows, and output column c
+//                   needs rows c and Q + c.  A walk of CW weight rows is ordered [gate c0 .., up c0 ..]
+//                   (CW / 2 output columns), so after the fold the two sums of an output element sit
+//                   in lanes that differ in bit 5 only: one shuffle pairs them and the gate lane
+//                   stores silu(g + bias[c]) * (u + bias[Q + c]) from f32 with one rounding.
 //
 // Determinism and row invariance.  The K order of an accumulator is fixed by (lane, chunk) alone and
 // the fold gives every value the sums a plain butterfly in the order 32 .. 1 gives it, whatever M,
@@ -93,12 +101,15 @@ __device__ __forceinline__ int fold_index(int lane) {
   return idx;
 }
 
-// MB: rows the accumulators are laid out for (M <= MB); CW: columns a wave walks at a time
-template <int MB, int CW>
+// MB: rows the accumulators are laid out for (M <= MB); CW: weight rows a wave walks at a time;
+// GLU: the SwiGLU epilogue (CW / 2 output columns per walk)
+template <int MB, int CW, bool GLU>
 __global__ __launch_bounds__(64 * kRowsWaves) void rows_linear_k(RowsLinearArgs a) {
   extern __shared__ uint4 xs[];  // [M][K / 8] chunks of 8 bf16
   constexpr int NV = MB * CW;
+  constexpr int CO = GLU ? CW / 2 : CW;  // output columns per walk
   static_assert(NV <= 64, "one lane per (column, row) in the epilogue");
+  static_assert(!GLU || CW >= 2, "a gate and an up row per output column");
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int nv = a.K >> 3;
 
@@ -111,8 +122,30 @@ __global__ __launch_bounds__(64 * kRowsWaves) void rows_linear_k(RowsLinearArgs 
     xs[i] = r;
   }
   __syncthreads();
-  // ---- LayerNorm prologue: one wave per row, each lane rewrites only the chunks it read
-  if (a.gamma) {  // workgroup-uniform
+  // ---- LayerNorm / RMSNorm prologue: one wave per row, each lane rewrites only the chunks it read
+  if (a.gamma && a.rms) {  // workgroup-uniform
+    const float inv = 1.f / (float)a.K;
+    for (int m = wid; m < a.M; m += kRowsWaves) {
+      uint4* row = xs + m * nv;
+      float s = 0.f;
+      for (int v = lane; v < nv; v += 64) {
+        float f[8];
+        rows_unpack8(row[v], f);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s += f[k] * f[k];
+      }
+      const float rs = rsqrtf(wave_sum(s) * inv + a.eps);
+      for (int v = lane; v < nv; v += 64) {
+        float f[8], g[8];
+        rows_unpack8(row[v], f);
+        rows_load8f(a.gamma + v * 8, g);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) f[k] = f[k] * rs * g[k];
+        row[v] = rows_pack8(f);
+      }
+    }
+    __syncthreads();
+  } else if (a.gamma) {
     const float inv = 1.f / (float)a.K;
     for (int m = wid; m < a.M; m += kRowsWaves) {
       uint4* row = xs + m * nv;
@@ -152,7 +185,7 @@ __global__ __launch_bounds__(64 * kRowsWaves) void rows_linear_k(RowsLinearArgs 
   const int64_t col0 = ((int64_t)blockIdx.x * kRowsWaves + wid) * a.cpw;
   const int64_t cend = col0 + a.cpw < (int64_t)a.Q ? col0 + a.cpw : (int64_t)a.Q;
   const int nr = (nv + 63) >> 6;  // 16-B chunks per lane and column
-  for (int64_t c0 = col0; c0 < cend; c0 += CW) {
+  for (int64_t c0 = col0; c0 < cend; c0 += CO) {
     float acc[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) acc[i] = 0.f;
@@ -165,8 +198,15 @@ __global__ __launch_bounds__(64 * kRowsWaves) void rows_linear_k(RowsLinearArgs 
         for (int c = 0; c < CW; ++c) {
           wq[u][c] = make_uint4(0, 0, 0, 0);
           // a column past the wave's range or a chunk past K never forms an address
-          if (v < nv && c0 + c < cend && TB_BOUNDS_OK(c0 + c < a.Q && v * 8 + 8 <= a.K, kBndGemmSrc))
-            wq[u][c] = *reinterpret_cast<const uint4*>(a.w + (c0 + c) * a.K + v * 8);
+          if constexpr (GLU) {  // walk slot c: gate row of output column c0 + c, or up row of c0 + c - CO
+            const int64_t oc = c0 + (c < CO ? c : c - CO);
+            const int64_t wr = c < CO ? oc : (int64_t)a.Q + oc;
+            if (v < nv && oc < cend && TB_BOUNDS_OK(oc < a.Q && wr < 2 * (int64_t)a.Q && v * 8 + 8 <= a.K, kBndGemmSrc))
+              wq[u][c] = *reinterpret_cast<const uint4*>(a.w + wr * a.K + v * 8);
+          } else {
+            if (v < nv && c0 + c < cend && TB_BOUNDS_OK(c0 + c < a.Q && v * 8 + 8 <= a.K, kBndGemmSrc))
+              wq[u][c] = *reinterpret_cast<const uint4*>(a.w + (c0 + c) * a.K + v * 8);
+          }
         }
       }
 #pragma unroll
@@ -195,7 +235,19 @@ __global__ __launch_bounds__(64 * kRowsWaves) void rows_linear_k(RowsLinearArgs 
     const int idx = fold_index<NV>(lane);
     const int c = idx / MB, m = idx - c * MB;
     const int64_t col = c0 + c;
-    if ((lane & (64 / NV - 1)) == 0 && m < a.M && col < cend) {
+    if constexpr (GLU) {
+      // walk slots c and c + CO are values idx and idx + NV / 2: fold_index puts them in lanes l and l ^ 32
+      const float up = __shfl_xor(acc[0], 32, 64);
+      if ((lane & (64 / NV - 1)) == 0 && c < CO && m < a.M && col < cend) {
+        float g = acc[0], u = up;
+        if (a.bias) {
+          g += bf2f(a.bias[col]);
+          u += bf2f(a.bias[(int64_t)a.Q + col]);
+        }
+        const int64_t o = (int64_t)m * a.Q + col;
+        if (TB_BOUNDS_OK(o < (int64_t)a.M * a.Q, kBndGemmDst)) a.y[o] = f2bf(silu_f(g) * u);
+      }
+    } else if ((lane & (64 / NV - 1)) == 0 && m < a.M && col < cend) {
       float z = acc[0];
       if (a.bias) z += bf2f(a.bias[col]);
       if (a.epi == kRowsGelu) z = gelu_f(z);
@@ -233,7 +285,7 @@ __global__ __launch_bounds__(256) void embed_rows_k(EmbedRowsArgs a) {
   if (ok) *reinterpret_cast<uint4*>(a.y + row * a.D + v * 8) = rows_pack8(e);
 }
 
-template <int MB, int CW>
+template <int MB, int CW, bool GLU>
 void rows_launch(const RowsLinearArgs& a, int grid, size_t lds, hipStream_t st) {
   // up to 16 x 4096 bf16 = 128 KiB of the CU's 160 KiB: above the default limit of a launch, raised
   // once per device at the first launch there (the warm-up step, ahead of any capture)
@@ -241,20 +293,20 @@ void rows_launch(const RowsLinearArgs& a, int grid, size_t lds, hipStream_t st) 
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (dev >= 0 && dev < 64 && !raised[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rows_linear_k<MB, CW>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rows_linear_k<MB, CW, GLU>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 4096 * 2);
     raised[dev] = true;
   }
-  hipLaunchKernelGGL((rows_linear_k<MB, CW>), dim3(grid), dim3(64 * kRowsWaves), lds, st, a);
+  hipLaunchKernelGGL((rows_linear_k<MB, CW, GLU>), dim3(grid), dim3(64 * kRowsWaves), lds, st, a);
 }
 
-template <int CW>
+template <int CW, bool GLU = false>
 void rows_dispatch(const RowsLinearArgs& a, int grid, size_t lds, hipStream_t st) {
-  if (a.M <= 1) rows_launch<1, CW>(a, grid, lds, st);
-  else if (a.M <= 2) rows_launch<2, CW>(a, grid, lds, st);
-  else if (a.M <= 4) rows_launch<4, CW>(a, grid, lds, st);
-  else if (a.M <= 8) rows_launch<8, CW>(a, grid, lds, st);
-  else rows_launch<16, CW>(a, grid, lds, st);
+  if (a.M <= 1) rows_launch<1, CW, GLU>(a, grid, lds, st);
+  else if (a.M <= 2) rows_launch<2, CW, GLU>(a, grid, lds, st);
+  else if (a.M <= 4) rows_launch<4, CW, GLU>(a, grid, lds, st);
+  else if (a.M <= 8) rows_launch<8, CW, GLU>(a, grid, lds, st);
+  else rows_launch<16, CW, GLU>(a, grid, lds, st);
 }
 
 }  // namespace
@@ -269,13 +321,25 @@ int rows_linear_cols_per_wave(int Q) {
   return want <= 1 ? 1 : want <= 2 ? 2 : want <= 4 ? 4 : want <= 8 ? 8 : 16;
 }
 
+// SwiGLU: a wave streams two weight rows per output column, so it takes half the columns a plain
+// product over the 2F weight rows would give it (at least one): F = 2048 at K = 768 is one column,
+// two rows, per wave and 512 workgroups, the grid of a plain Q = 4096.  A function of F alone.
+int rows_swiglu_cols_per_wave(int F) {
+  const int c = rows_linear_cols_per_wave(2 * F) / 2;
+  return c < 1 ? 1 : c;
+}
+
 void rows_linear(const RowsLinearArgs& a_, hipStream_t st) {
   RowsLinearArgs a = a_;
-  a.cpw = rows_linear_cols_per_wave(a.Q);
+  const bool glu = a.epi == kRowsSwiglu;
+  a.cpw = glu ? rows_swiglu_cols_per_wave(a.Q) : rows_linear_cols_per_wave(a.Q);
   const int per_wg = a.cpw * kRowsWaves;
   const int grid = (a.Q + per_wg - 1) / per_wg;
   const size_t lds = (size_t)a.M * a.K * 2;
-  if (a.cpw == 1) rows_dispatch<1>(a, grid, lds, st);
+  if (glu) {  // one or two output columns per walk
+    if (a.cpw == 1) rows_dispatch<2, true>(a, grid, lds, st);
+    else rows_dispatch<4, true>(a, grid, lds, st);
+  } else if (a.cpw == 1) rows_dispatch<1>(a, grid, lds, st);
   else if (a.cpw == 2) rows_dispatch<2>(a, grid, lds, st);
   else rows_dispatch<4>(a, grid, lds, st);
 }

@@ -107,6 +107,19 @@ void ln_forward(int dt, const void* x, const void* res, const float* gamma, cons
 void ln_backward(int dt, const void* dy, const void* x, const void* dadd, const float* gamma, const float* mean,
                  const float* rstd, int64_t M, int C, void* dx, float* pdg, float* pdb, int nblk, float* dgamma,
                  float* dbeta, hipStream_t st);
+// RMSNorm on the same row kernels: y = x * rsqrt(mean(x^2) + eps) * gamma (no beta; rstd the one saved
+// statistic); pdg: ln_bwd_blocks(M) * C floats
+void rms_forward(int dt, const void* x, const void* res, const float* gamma, int64_t M, int C, float eps, void* y,
+                 void* xsum, float* rstd, hipStream_t st);
+void rms_backward(int dt, const void* dy, const void* x, const void* dadd, const float* gamma, const float* rstd,
+                  int64_t M, int C, void* dx, float* pdg, int nblk, float* dgamma, hipStream_t st);
+
+// ---- SwiGLU gate (csrc/swiglu.hip; bf16 / f32, F % 8 == 0, 16-B aligned rows) ----
+// y[m][c] = silu(gu[m][c]) * gu[m][F + c] over packed gate | up rows of stride sgu (elements); y is
+// [M][F] contiguous.  Backward from the same gu: dgu [M][2F] contiguous, dgate | dup.
+void swiglu_forward(int dt, const void* gu, int64_t sgu, int64_t M, int F, void* y, hipStream_t st);
+void swiglu_backward(int dt, const void* gu, int64_t sgu, const void* dy, int64_t M, int F, void* dgu,
+                     hipStream_t st);
 
 // ---- optimizers (multi-tensor, chunk table) ----
 // hyper (optional, device f32): adamw [lr, bc1, bc2_sqrt] / sgd [lr] read by the kernel instead of
@@ -333,7 +346,9 @@ void attn_decode_append(const AttnDecodeArgs& a, const uint16_t* nk, const uint1
 // gamma / beta (f32 [K], both or neither): LayerNorm prologue with eps.  epi: kRowsGelu (exact GELU)
 // or kRowsResidual (+ res[M][Q], row stride sres; not y).  bias (bf16 [Q]) may be null.  cpw is
 // filled in by rows_linear.  Row m of y does not depend on M or on the other rows.
-enum : int { kRowsNone = 0, kRowsGelu = 1, kRowsResidual = 2 };
+// rms != 0: the prologue is RMSNorm with gamma (beta is not read).  epi kRowsSwiglu: w is [2Q][K]
+// (gate rows, then up rows), bias [2Q], y[m][c] = silu(g + bias[c]) * (u + bias[Q + c]); no residual.
+enum : int { kRowsNone = 0, kRowsGelu = 1, kRowsResidual = 2, kRowsSwiglu = 3 };
 struct RowsLinearArgs {
   const uint16_t* x;
   const uint16_t* w;
@@ -346,8 +361,10 @@ struct RowsLinearArgs {
   int64_t sx, sres;
   float eps;
   int cpw;
+  int rms;
 };
 int rows_linear_cols_per_wave(int Q);
+int rows_swiglu_cols_per_wave(int F);  // output columns per wave under kRowsSwiglu (two weight rows each)
 void rows_linear(const RowsLinearArgs& a, hipStream_t st);
 // y[b][t][:] = tok_w[clamp(tokens[b][t], 0, vocab - 1)] + pos_w[clamp(pos[b] + t, 0, max_len - 1)]
 // (f32 sum, one rounding); tokens int64 [B][T] with strides stok (elements), pos int32 [B] or null

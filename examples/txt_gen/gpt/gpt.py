@@ -45,6 +45,8 @@ class Config(BaseConfig):
     optim: OptimizerConfig
     scheduler: SchedulerConfig
     pos: str = "learned"  # "rope": rotary position embeddings (models/gpt.py)
+    norm: str = "layer"  # "rms": RMSNorm
+    mlp: str = "gelu"  # "swiglu": the gated SiLU MLP
 
 
 def load_bytes(path: str) -> torch.Tensor:
@@ -59,7 +61,8 @@ def main(conf: Config) -> None:
     data = conf.env.make(load_bytes(conf.text))
     if data.numel() <= conf.seq_len:
         raise ValueError(f"{conf.text or 'README.md'}: {data.numel()} bytes, need more than seq_len = {conf.seq_len}")
-    model = prepare_model(getattr(gpt, conf.arch)(vocab=256, max_len=conf.seq_len, pos=conf.pos), conf, channels_last=False)
+    model = prepare_model(getattr(gpt, conf.arch)(vocab=256, max_len=conf.seq_len, pos=conf.pos, norm=conf.norm, mlp=conf.mlp),
+                          conf, channels_last=False)
     net = getattr(model, "module", model)
     optim = conf.optim.make(model.parameters())
     sched = conf.scheduler.make(optim)

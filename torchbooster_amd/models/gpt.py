@@ -47,6 +47,16 @@ layer rotates the q and k parts of its packed projection by the token's position
 :class:`KVCache` is unchanged and holds rotated keys; ``max_len`` stays the capacity limit and is the
 length of the angle table, which one :class:`~torchbooster_amd.models.vit.Rope` per model owns outside
 the parameters and buffers.  ``pos="learned"`` (the default) is everything above unchanged.
+
+Llama-style blocks (``TransformerLM(..., norm="rms", mlp="swiglu", bias=False)``, each option on its own
+too): ``norm="rms"`` makes every norm, the final one included, an RMSNorm (``ops.norm.RMSNorm``, the RMS
+instantiation of the LayerNorm row kernels); ``mlp="swiglu"`` makes every MLP the gated SiLU
+``fc2(silu(gate) * up)`` with ``gate | up`` from one ``Linear(dim, 2 * int(dim * mlp_ratio))``
+(``ops.act.swiglu``, csrc/swiglu.hip; ``mlp_ratio=8/3`` has the parameters of a 4x GELU MLP); ``bias=False``
+drops the biases of ``qkv``, ``proj`` and the MLP linears (``head`` never had one).  With ``pos="rope"`` and
+``kv_heads`` that is the Llama / Mistral / Qwen decoder on every path above: the fused step runs the
+RMSNorm as the ``rms=`` prologue and the gate as the ``act="swiglu"`` epilogue of ``linear_rows``, the same
+number of launches per layer.  The defaults (``"layer"``, ``"gelu"``, ``True``) are everything above unchanged.
 """
 from __future__ import annotations
 
@@ -55,10 +65,9 @@ from typing import List, Optional, Tuple
 import torch
 from torch import Tensor, nn
 
-from torchbooster_amd.models.vit import Block, Rope, ln_args
+from torchbooster_amd.models.vit import Block, Rope, make_norm, norm_args
 from torchbooster_amd.ops.linear import Linear, embed_rows, linear_rows
 from torchbooster_amd.ops.loss import linear_cross_entropy
-from torchbooster_amd.ops.norm import LayerNorm
 
 __all__ = ["TransformerLM", "KVCache", "gpt_tiny", "gpt2_small"]
 
@@ -105,7 +114,8 @@ def _sample(logits: Tensor, temperature: float, top_k: Optional[int], generator)
 
 class TransformerLM(nn.Module):
     def __init__(self, vocab: int, dim: int, depth: int, heads: int, max_len: int, mlp_ratio: float = 4.0,
-                 kv_heads: Optional[int] = None, *, pos: str = "learned", rope_base: float = 10000.0) -> None:
+                 kv_heads: Optional[int] = None, *, pos: str = "learned", rope_base: float = 10000.0,
+                 norm: str = "layer", mlp: str = "gelu", bias: bool = True) -> None:
         super().__init__()
         if pos not in ("learned", "rope"):
             raise ValueError(f"pos must be 'learned' or 'rope', not {pos!r}")
@@ -115,9 +125,11 @@ class TransformerLM(nn.Module):
         self.rope = Rope(max_len, dim // heads, rope_base) if pos == "rope" else None
         self.pos = nn.Parameter(torch.zeros(1, max_len, dim)) if self.rope is None else None
         kw = {} if self.rope is None else {"rope": self.rope}  # learned: the calls it always made
+        if (norm, mlp, bias) != ("layer", "gelu", True):  # likewise the GPT-2 block
+            kw.update(norm=norm, mlp=mlp, bias=bias)
         self.blocks = nn.ModuleList([Block(dim, heads, mlp_ratio, causal=True, kv_heads=kv_heads, **kw)
                                      for _ in range(depth)])
-        self.norm = LayerNorm(dim, eps=1e-6)
+        self.norm = make_norm(norm, dim)
         self.head = Linear(dim, vocab, bias=False)
         nn.init.normal_(self.tok.weight, std=0.02)
         if self.pos is not None:
@@ -129,7 +141,7 @@ class TransformerLM(nn.Module):
                     nn.init.zeros_(m.bias)
 
     def features(self, tokens: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
-        """[B, N] token ids -> [B, N, dim], the output of the final LayerNorm (the input of ``head``)."""
+        """[B, N] token ids -> [B, N, dim], the output of the final norm (the input of ``head``)."""
         B, N = tokens.shape
         if N > self.max_len:
             raise ValueError(f"sequence length {N} exceeds max_len {self.max_len}")
@@ -220,10 +232,10 @@ class TransformerLM(nn.Module):
         return x[:, T - 1:].contiguous(), pending[:, T - 1:].contiguous()
 
     def _logits(self, x: Tensor, pending: Optional[Tensor], fused: bool = False) -> Tensor:
-        """The final LayerNorm and the head on ``[B, T, dim]`` -> ``[B, T, vocab]``.  Default: ``x`` and its
-        ``pending`` add; ``fused``: the residual stream alone, the LayerNorm as the product's prologue."""
+        """The final norm and the head on ``[B, T, dim]`` -> ``[B, T, vocab]``.  Default: ``x`` and its
+        ``pending`` add; ``fused``: the residual stream alone, the norm as the product's prologue."""
         if fused:
-            return linear_rows(x, self.head.weight, self.head.bias, ln=ln_args(self.norm))
+            return linear_rows(x, self.head.weight, self.head.bias, **norm_args(self.norm))
         h, _ = self.norm(x, pending)
         return self.head(h)
 
@@ -435,9 +447,12 @@ class TransformerLM(nn.Module):
             return out, out_lengths
 
 
-def gpt_tiny(vocab: int = 256, max_len: int = 128, pos: str = "learned") -> TransformerLM:
-    return TransformerLM(vocab, 128, 2, 2, max_len, pos=pos)
+def gpt_tiny(vocab: int = 256, max_len: int = 128, pos: str = "learned", *, norm: str = "layer", mlp: str = "gelu",
+             bias: bool = True, kv_heads: Optional[int] = None, mlp_ratio: float = 4.0) -> TransformerLM:
+    return TransformerLM(vocab, 128, 2, 2, max_len, mlp_ratio, kv_heads, pos=pos, norm=norm, mlp=mlp, bias=bias)
 
 
-def gpt2_small(vocab: int = 50257, max_len: int = 1024, pos: str = "learned") -> TransformerLM:
-    return TransformerLM(vocab, 768, 12, 12, max_len, pos=pos)
+def gpt2_small(vocab: int = 50257, max_len: int = 1024, pos: str = "learned", *, norm: str = "layer",
+               mlp: str = "gelu", bias: bool = True, kv_heads: Optional[int] = None,
+               mlp_ratio: float = 4.0) -> TransformerLM:
+    return TransformerLM(vocab, 768, 12, 12, max_len, mlp_ratio, kv_heads, pos=pos, norm=norm, mlp=mlp, bias=bias)

@@ -23,10 +23,11 @@ from torchbooster_amd.ops.attention import (attention_decode_packed, attention_e
                                             kv_cache_append, rope_packed, rope_table)
 from torchbooster_amd.ops.conv import Conv2d
 
-from torchbooster_amd.ops.norm import LayerNorm
+from torchbooster_amd.ops.act import swiglu
+from torchbooster_amd.ops.norm import LayerNorm, RMSNorm
 from torchbooster_amd.ops.linear import GeluLink, Linear, LinearGELU, linear, linear_rows
 
-__all__ = ["ViT", "vit_b_16", "vit_s_16", "vit_tiny", "Attention", "Block", "Rope"]
+__all__ = ["ViT", "vit_b_16", "vit_s_16", "vit_tiny", "Attention", "Block", "Rope", "SwiGLU"]
 
 
 class Rope:
@@ -72,6 +73,23 @@ def ln_args(norm: LayerNorm):
     return norm.weight, norm.bias, norm.eps
 
 
+def norm_args(norm):
+    """The norm prologue of ``ops.linear.linear_rows`` for a norm module, as keyword arguments:
+    ``ln=(weight, bias, eps)`` for a LayerNorm, ``rms=(weight, eps)`` for an RMSNorm."""
+    if isinstance(norm, RMSNorm):
+        return {"rms": (norm.weight, norm.eps)}
+    return {"ln": ln_args(norm)}
+
+
+def make_norm(kind: str, dim: int):
+    """The block norm ``kind`` names: ``"layer"`` (LayerNorm) or ``"rms"`` (RMSNorm), eps 1e-6."""
+    if kind == "layer":
+        return LayerNorm(dim, eps=1e-6)
+    if kind == "rms":
+        return RMSNorm(dim, eps=1e-6)
+    raise ValueError(f"norm must be 'layer' or 'rms', not {kind!r}")
+
+
 class Attention(nn.Module):
     """``causal``: query i attends to keys j <= i; ``key_lengths`` (int32 [B], clamped into [1, N]):
     the keys of batch b at or past its length are hidden (ops/attention.py).
@@ -89,6 +107,7 @@ class Attention(nn.Module):
     key / value heads, query head ``h`` reading kv head ``h // (heads // kv_heads)``.  The projection is
     ``Linear(dim, (heads + 2 * kv_heads) * hd)`` and a cache ``[B, kv_heads, cap, hd]``.  ``None`` is
     ``heads``: plain multi-head attention, the same parameters and the same calls as without it.
+    ``bias=False``: ``qkv`` and ``proj`` without biases.
 
     ``rope`` (a :class:`Rope`; ``None``: nothing changes): the q and k parts of the packed projection are
     rotated right behind ``self.qkv`` (``ops.attention.rope_packed``), so every path below reads rotated
@@ -96,7 +115,7 @@ class Attention(nn.Module):
     prefill, at ``positions[b] + t`` in a decode step and an extend; the cached paths rotate in place."""
 
     def __init__(self, dim: int, heads: int, causal: bool = False, kv_heads: Optional[int] = None,
-                 rope: Optional[Rope] = None) -> None:
+                 rope: Optional[Rope] = None, bias: bool = True) -> None:
         super().__init__()
         if kv_heads is not None and (kv_heads < 1 or heads % kv_heads):
             raise ValueError(f"kv_heads {kv_heads} must divide heads {heads}")
@@ -107,8 +126,8 @@ class Attention(nn.Module):
         if rope is not None and rope.head_dim != self.hd:
             raise ValueError(f"rope is for head dim {rope.head_dim}, this layer has {self.hd}")
         self.rope = rope
-        self.qkv = Linear(dim, 3 * dim if kv_heads is None else (heads + 2 * self.kv_heads) * self.hd)
-        self.proj = Linear(dim, dim)
+        self.qkv = Linear(dim, 3 * dim if kv_heads is None else (heads + 2 * self.kv_heads) * self.hd, bias=bias)
+        self.proj = Linear(dim, dim, bias=bias)
 
     def rotate(self, qkv: Tensor, positions: Optional[Tensor] = None, inplace: bool = False) -> Tensor:
         """The packed projection with q and k rotated; ``qkv`` itself without ``rope``."""
@@ -151,10 +170,10 @@ class Attention(nn.Module):
 
 
 class MLP(nn.Module):
-    def __init__(self, dim: int, hidden: int) -> None:
+    def __init__(self, dim: int, hidden: int, bias: bool = True) -> None:
         super().__init__()
-        self.fc1 = LinearGELU(dim, hidden)  # GELU fused into its backward / bias-grad pass
-        self.fc2 = Linear(hidden, dim)
+        self.fc1 = LinearGELU(dim, hidden, bias=bias)  # GELU fused into its backward / bias-grad pass
+        self.fc2 = Linear(hidden, dim, bias=bias)
 
     def forward(self, x: Tensor) -> Tensor:
         # fc2 is the hidden activation's only consumer: its input gradient takes fc1's GELU
@@ -163,14 +182,37 @@ class MLP(nn.Module):
         return self.fc2(self.fc1(x, link), gelu_in=link)
 
 
-class Block(nn.Module):
-    def __init__(self, dim: int, heads: int, mlp_ratio: float = 4.0, causal: bool = False,
-                 kv_heads: Optional[int] = None, rope: Optional[Rope] = None) -> None:
+class SwiGLU(nn.Module):
+    """The gated SiLU MLP of Llama-style blocks: ``fc2(silu(gate) * up)`` with ``gate | up = fc1(x)``, the
+    two input projections packed into ONE ``Linear(dim, 2 * hidden)`` (one GEMM; ``ops.act.swiglu``)."""
+
+    def __init__(self, dim: int, hidden: int, bias: bool = True) -> None:
         super().__init__()
-        self.ln1 = LayerNorm(dim, eps=1e-6)
-        self.attn = Attention(dim, heads, causal, kv_heads, rope)
-        self.ln2 = LayerNorm(dim, eps=1e-6)
-        self.mlp = MLP(dim, int(dim * mlp_ratio))
+        self.fc1 = Linear(dim, 2 * hidden, bias=bias)
+        self.fc2 = Linear(hidden, dim, bias=bias)
+
+    def forward(self, x: Tensor) -> Tensor:
+        return self.fc2(swiglu(self.fc1(x)))
+
+
+class Block(nn.Module):
+    """Pre-norm transformer block.  The defaults are the GPT-2 / ViT block: LayerNorm, a GELU MLP, biases.
+    ``norm="rms"``: ``ln1`` / ``ln2`` are :class:`~torchbooster_amd.ops.norm.RMSNorm` (the attribute names
+    stay: the ``(x, pending)`` protocol of ``forward`` is the same); ``mlp="swiglu"``: ``self.mlp`` is a
+    :class:`SwiGLU` of hidden width ``int(dim * mlp_ratio)``; ``bias=False``: no bias in ``qkv``, ``proj`` and
+    the MLP's linears -- together the Llama-style block."""
+
+    def __init__(self, dim: int, heads: int, mlp_ratio: float = 4.0, causal: bool = False,
+                 kv_heads: Optional[int] = None, rope: Optional[Rope] = None, norm: str = "layer",
+                 mlp: str = "gelu", bias: bool = True) -> None:
+        super().__init__()
+        if mlp not in ("gelu", "swiglu"):
+            raise ValueError(f"mlp must be 'gelu' or 'swiglu', not {mlp!r}")
+        self.ln1 = make_norm(norm, dim)
+        self.attn = Attention(dim, heads, causal, kv_heads, rope, bias=bias)
+        self.ln2 = make_norm(norm, dim)
+        hidden = int(dim * mlp_ratio)
+        self.mlp = SwiGLU(dim, hidden, bias) if mlp == "swiglu" else MLP(dim, hidden, bias)
 
     def forward(self, x: Tensor, pending: Optional[Tensor] = None, key_lengths: Optional[Tensor] = None, *,
                 cache=None, positions: Optional[Tensor] = None, extend: bool = False):
@@ -189,18 +231,19 @@ class Block(nn.Module):
     def forward_rows(self, x: Tensor, *, cache, positions: Tensor, extend: bool = False) -> Tensor:
         """The decoding layer on the few-row kernels (ops/linear.py ``linear_rows``; causal, forward only):
         ``x`` ``[B, T, dim]`` is the residual stream itself -- there is no ``pending`` -- and so is the
-        result.  Both LayerNorms run as prologues of the product behind them, bias / GELU / residual as
-        epilogues, and the attention is ``Attention.cached(fused=True)``: with ``T == 1`` 5 launches with a
+        result.  Both norms (LayerNorm or RMSNorm) run as prologues of the product behind them, bias / GELU or
+        SwiGLU / residual as epilogues, and the attention is ``Attention.cached(fused=True)``: with ``T == 1`` 5 launches with a
         single-chunk cache, 6 otherwise (one more with rotary positions: the rotation of ``qkv``).
         ``T > 1`` needs ``extend=True``.  Computes what ``forward`` computes with ``cache`` / ``positions`` /
         ``extend``, to rounding."""
         at = self.attn
         if x.shape[1] != 1 and not extend:
             raise ValueError("forward_rows: more than one token per sequence needs extend=True")
-        qkv = linear_rows(x, at.qkv.weight, at.qkv.bias, ln=ln_args(self.ln1))
+        qkv = linear_rows(x, at.qkv.weight, at.qkv.bias, **norm_args(self.ln1))
         a = at.cached(qkv, cache, positions, extend=extend, fused=True)
         x = linear_rows(a, at.proj.weight, at.proj.bias, residual=x)
-        h = linear_rows(x, self.mlp.fc1.weight, self.mlp.fc1.bias, ln=ln_args(self.ln2), act="gelu")
+        act = "swiglu" if isinstance(self.mlp, SwiGLU) else "gelu"
+        h = linear_rows(x, self.mlp.fc1.weight, self.mlp.fc1.bias, **norm_args(self.ln2), act=act)
         return linear_rows(h, self.mlp.fc2.weight, self.mlp.fc2.bias, residual=x)
 
 

@@ -31,6 +31,8 @@ from torch import Tensor, nn
 
 from torchbooster_amd.ops import gemm as G
 from torchbooster_amd.ops._ext import native, slot_alias, take_slot, use_native
+from torchbooster_amd.ops.act import swiglu
+from torchbooster_amd.ops.norm import rms_norm
 
 __all__ = ["Linear", "linear", "LinearGELU", "linear_gelu", "GeluLink", "linear_rows", "embed_rows"]
 
@@ -289,7 +291,7 @@ def _rows_forward_only(*tensors: Optional[Tensor]) -> None:
 
 
 def linear_rows(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, ln=None, act: Optional[str] = None,
-                residual: Optional[Tensor] = None) -> Tensor:
+                residual: Optional[Tensor] = None, rms=None) -> Tensor:
     """``epilogue(linear(prologue(x), weight, bias))`` for the few rows of a decode step, in ONE kernel.
 
     ``x`` ``[..., K]``, ``weight`` ``[Q, K]`` (the ``nn.Linear`` layout, read once), ``bias`` ``[Q]`` ->
@@ -297,17 +299,30 @@ def linear_rows(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, ln=
     tensor is written).  ``act="gelu"``: exact GELU; ``residual`` ``[..., Q]``: added.  Both epilogues work
     on the f32 accumulator, which is rounded once at the store; they exclude each other.
 
+    ``rms = (gamma, eps)``: RMSNorm over ``K`` first instead (``ops.norm.rms_norm``; exclusive with ``ln``,
+    and not the same thing as ``ln=(gamma, None, eps)``, which stays LayerNorm without a bias).
+    ``act="swiglu"``: ``weight`` is ``[2F, K]`` and ``bias`` ``[2F]``, the packed ``gate | up`` projection of
+    ``ops.act.swiglu``, and the result is ``silu(gate) * up`` ``[..., F]`` -- both halves are accumulated in
+    the same pass and paired in registers; no residual.
+
     The native kernel (csrc/rows_gemm.hip) takes CUDA bf16 operands with at most 16 rows, ``K % 8 == 0``
     and ``K <= 4096``; row ``m`` of its result has the same bits whether it is computed alone or among 16
     rows.  Everything else (CPU tensors, other dtypes, more rows, another ``K``,
-    ``TBAMD_FORCE_REFERENCE=1``) is the PyTorch composition ``F.layer_norm -> F.linear -> F.gelu`` /
-    ``+ residual`` in the dtype of ``x``.  Forward only."""
-    _rows_forward_only(x, weight, bias, residual, *((ln[0], ln[1]) if ln is not None else ()))
-    if act not in (None, "gelu"):
+    ``TBAMD_FORCE_REFERENCE=1``) is the PyTorch composition ``F.layer_norm`` / ``rms_norm -> F.linear ->
+    F.gelu`` / ``swiglu`` / ``+ residual``, every tensor in the dtype of ``x`` (the two norms take their statistics in
+    f32 for 16-bit inputs and round once).  Forward only."""
+    _rows_forward_only(x, weight, bias, residual, *((ln[0], ln[1]) if ln is not None else ()),
+                       *((rms[0],) if rms is not None else ()))
+    if act not in (None, "gelu", "swiglu"):
         raise ValueError(f"linear_rows: unsupported activation {act!r}")
     if act is not None and residual is not None:
         raise ValueError("linear_rows: one epilogue, act or residual")
-    K, Q = x.shape[-1], weight.shape[0]
+    if ln is not None and rms is not None:
+        raise ValueError("linear_rows: one prologue, ln or rms")
+    glu = act == "swiglu"
+    if glu and weight.shape[0] % 2:
+        raise ValueError(f"linear_rows: act='swiglu' needs weight [2F, K], not {weight.shape[0]} rows")
+    K, Q = x.shape[-1], weight.shape[0] // 2 if glu else weight.shape[0]
     lead = x.shape[:-1]
     with torch.no_grad():
         rows = x.reshape(-1, K)
@@ -317,7 +332,8 @@ def linear_rows(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, ln=
                 and K % 8 == 0 and 8 <= K <= ROWS_MAX_K and not torch.is_autocast_enabled("cuda")
                 and (bias is None or bias.dtype == bf) and (residual is None or residual.dtype == bf)
                 and (ln is None or (ln[0] is not None and ln[1] is not None and ln[0].dtype == torch.float32
-                                    and ln[1].dtype == torch.float32))):
+                                    and ln[1].dtype == torch.float32))
+                and (rms is None or (rms[0] is not None and rms[0].dtype == torch.float32))):
             if rows.stride(1) != 1 or (M > 1 and rows.stride(0) % 8) or rows.data_ptr() % 16:
                 rows = rows.contiguous()
             res = None
@@ -326,10 +342,15 @@ def linear_rows(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, ln=
                 if res.stride(1) != 1:
                     res = res.contiguous()
             g, b, eps = (ln[0].contiguous(), ln[1].contiguous(), float(ln[2])) if ln is not None else (None, None, 0.0)
+            if rms is not None:
+                g, eps = rms[0].contiguous(), float(rms[1])
             y = native().rows_linear(rows, weight.contiguous(), None if bias is None else bias.contiguous(), g, b, eps,
-                                     1 if act == "gelu" else 2 if res is not None else 0, res)
+                                     3 if glu else 1 if act == "gelu" else 2 if res is not None else 0, res,
+                                     rms=rms is not None)
             return y.view(*lead, Q)
         h = x
+        if rms is not None:
+            h = rms_norm(h, rms[0], float(rms[1]))
         if ln is not None:
             g, b, eps = ln
             h = F.layer_norm(h, (K,), None if g is None else g.to(h.dtype), None if b is None else b.to(h.dtype),
@@ -337,6 +358,8 @@ def linear_rows(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, ln=
         y = F.linear(h, weight.to(h.dtype), None if bias is None else bias.to(h.dtype))
         if act == "gelu":
             y = F.gelu(y)
+        if glu:
+            y = swiglu(y)
         if residual is not None:
             y = y + residual.to(y.dtype)
         return y

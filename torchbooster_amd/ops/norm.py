@@ -19,7 +19,7 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from torchbooster_amd.ops import streams
-from torchbooster_amd.ops._ext import slot_alias, take_slot, native, use_native
+from torchbooster_amd.ops._ext import DTYPE_CODE, slot_alias, take_slot, native, use_native
 
 ACT_CODES = {"none": 0, "identity": 0, None: 0, "relu": 1, "gelu": 2, "silu": 3, "leaky_relu": 4}
 
@@ -848,3 +848,84 @@ class LayerNorm(nn.LayerNorm):
 
     def forward(self, x: Tensor, residual: Optional[Tensor] = None):
         return layer_norm(x, self.weight, self.bias, self.eps, residual)
+
+
+# --------------------------------------------------------------- RMSNorm
+class _RMSFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, residual, weight, eps):
+        C = native()
+        shape = x.shape
+        rows = x.reshape(-1, shape[-1])
+        res_rows = residual.reshape(-1, shape[-1]) if residual is not None else None
+        y, xsum, rstd = C.rms_forward(rows, res_rows, weight, eps)
+        xin = xsum if residual is not None else rows
+        ctx.save_for_backward(xin, weight, rstd)
+        ctx.shape = shape
+        ctx.has_res = residual is not None
+        ctx.w_dtype = weight.dtype if weight is not None else None
+        ctx.params = (weight, None)  # for the zero-copy gradient slot
+        ctx.set_materialize_grads(False)
+        if residual is not None:
+            return y.view(shape), xsum.view(shape)
+        return y.view(shape), None
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy, dxsum):
+        C = native()
+        xin, weight, rstd = ctx.saved_tensors
+        shape = ctx.shape
+        if dy is None:  # only the residual-stream output was used
+            return dxsum, (dxsum if ctx.has_res else None), None, None
+        # the residual-stream gradient is added inside the kernel (no extra pass)
+        dadd = dxsum.reshape(-1, shape[-1]) if dxsum is not None else None
+        gs, _ = _affine_slots(ctx, weight, 2)
+        dx, dg = C.rms_backward(dy.reshape(-1, shape[-1]), xin, weight, rstd, dadd, gs)
+        dx = dx.view(shape)
+        dw = _affine_grad(dg, gs, ctx.w_dtype) if weight is not None and ctx.needs_input_grad[2] else None
+        return dx, (dx if ctx.has_res else None), dw, None
+
+
+def rms_norm(x: Tensor, weight: Optional[Tensor], eps: float = 1e-6, residual: Optional[Tensor] = None):
+    """RMSNorm over the last dim: ``x * rsqrt(mean(x^2) + eps) * weight`` (f32 statistics, no bias).  With
+    ``residual`` returns ``(rms(x + residual), x + residual)``, the contract of :func:`layer_norm`: the
+    norm is computed from the unrounded f32 sum and the stream output is that sum rounded once.
+
+    Native (csrc/layernorm.hip, the RMS instantiation of the LayerNorm row kernels) for what
+    :func:`layer_norm` takes natively; everything else is the same formula in PyTorch in the dtype of
+    ``x`` (fp64 stays fp64; 16-bit inputs take their statistics in f32 and round once, as ``F.layer_norm``)."""
+    if use_native(x) and x.dtype in DTYPE_CODE and x.shape[-1] % 8 == 0 and 8 <= x.shape[-1] <= 4096:
+        y, xs = _RMSFn.apply(x, residual, weight, eps)
+        return (y, xs) if residual is not None else y
+    xs = x if residual is None else x + residual
+    xf = xs.float() if xs.dtype in (torch.bfloat16, torch.float16) else xs  # f32 statistics, as F.layer_norm
+    y = xf * torch.rsqrt(xf.pow(2).mean(dim=-1, keepdim=True) + eps)
+    if weight is not None:
+        y = y * weight.to(xf.dtype)
+    y = y.to(xs.dtype)
+    return (y, xs) if residual is not None else y
+
+
+class RMSNorm(nn.Module):
+    """RMSNorm over the last dim on the native row kernel; the weight stays f32 under dtype casts.
+    ``forward(x, residual=None)`` as :class:`LayerNorm`."""
+
+    def __init__(self, dim: int, eps: float = 1e-6) -> None:
+        super().__init__()
+        self.dim = int(dim)
+        self.eps = float(eps)
+        self.weight = nn.Parameter(torch.ones(self.dim))
+
+    def _apply(self, fn, recurse=True):
+        super()._apply(fn, recurse)
+        p = self.weight
+        if p is not None and p.is_floating_point() and p.dtype != torch.float32:
+            p.data = p.data.float()
+        return self
+
+    def forward(self, x: Tensor, residual: Optional[Tensor] = None):
+        return rms_norm(x, self.weight, self.eps, residual)
+
+    def extra_repr(self) -> str:
+        return f"{self.dim}, eps={self.eps}"
