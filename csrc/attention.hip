@@ -27,15 +27,28 @@
 //
 // Masks (AttnArgs::causal, AttnArgs::klen; self-attention): query i of batch b sees keys
 // j < min(klen[b], causal ? i + 1 : N), klen[b] clamped into [1, N] in the kernel.  Every kernel is
-// a template on MASK: the <false> instantiations are the dense kernels, the <true> ones are launched
-// only when a mask is requested.  The masked kernels SKIP tiles no query of the workgroup (or wave)
-// sees, run the dense tile body on tiles wholly inside every limit of the wave, and the masked body
-// (the per-lane limit in place of N in the EDGE compares) only on tiles a limit cuts through: the
-// causal diagonal and the length edge.  Tiles run in increasing key order and tile 0 always holds
+// a template on MASK (the 128-row kernels on MODE, whose kDense / kMask are these two): the <false>
+// instantiations are the dense kernels, the <true> ones are launched only when a mask is requested.
+// The masked kernels SKIP tiles no query of the workgroup (or wave) sees, run the dense tile body on
+// tiles wholly inside every limit of the wave, and the masked body (the per-lane limit in place of N
+// in the EDGE compares) only on tiles a limit cuts through: the causal diagonal and the length edge.  Tiles run in increasing key order and tile 0 always holds
 // key 0, which every query sees, so the running max is finite before any tile in which a query sees
 // nothing (there p = exp2(-inf) = 0 and alpha = 1).  In the 128-row kernels the tile loop bounds are
 // workgroup-uniform: a wave past its own limit skips the compute of a tile, never its staging or
 // its barrier.
+//
+// Sliding window (AttnArgs::window = W > 0, causal): a query whose limit above is hi sees keys
+// max(0, hi - W) <= j < hi.  A third instantiation of the three 128-row kernels (kWin; the dense and the
+// masked ones are the code they were), which windowed calls always take.  Forward and dQ: the
+// workgroup's tile range starts at the tile that holds its smallest lower limit (the prologue stages
+// that tile); a wave runs the windowed body -- the masked body with a second compare, key < lo -> -inf
+// -- on the tiles a lower limit of its queries cuts, the dense body between the limits, the windowed
+// body again on the tiles an upper limit cuts.  A query may see nothing in the first tiles its wave
+// computes (W = 64: query 255 sees nothing of keys 64 .. 127), so the windowed body alone guards
+// -inf - -inf: ms = mn == -inf ? 0 : mn, which makes alpha and every p an exact 0 there.  The sub-tile
+// skips (nvk) know the upper side only.  dK/dV: key j is seen by queries j <= i < j + W and, because a
+// pad query (i >= len) sees the last W valid keys, by every i >= j when j >= len - W; so the per-key
+// qmin gains a qmax, and a wave's (and the workgroup's) query tile range an upper end.
 #include <type_traits>
 
 #include "common.h"
@@ -47,6 +60,8 @@ namespace {
 
 constexpr int kBlk = 128;           // queries (fwd, dQ) or keys (dK/dV) per workgroup: 4 waves x 32
 constexpr float kLog2e = 1.4426950408889634f;
+// the instantiations of the 128-row kernels: no mask, causal / lengths, those plus a sliding window
+constexpr int kDense = 0, kMask = 1, kWin = 2;
 
 // keys visible in batch b before the causal limit: klen[b] clamped into [1, N] (N without lengths)
 __device__ __forceinline__ int key_len(const AttnArgs& a, int b) {
@@ -97,11 +112,15 @@ __device__ __forceinline__ void fwd_store(const AttnArgs& a, int b, int h, int q
 // range reduction for denormal results -- an ldexp, two selects and an add per score).
 // LIM (masked kernels, with EDGE): N is the largest key limit of the wave's queries (sub-tile skips)
 // and lim[qt] the lane's own query's limit, which replaces N in the key mask.
-template <bool EDGE, bool LIM = false>
+// WIN (windowed kernels, with LIM): keys below low[qt] are masked too, and a query that has seen no
+// key yet keeps m = -inf without forming -inf - -inf.
+template <bool EDGE, bool LIM = false, bool WIN = false>
 __device__ __forceinline__ void fwd_tile(const uint4* Kt, const uint4* Vt, int t, int N, int nqt, float c,
                                          const bf16x8_t (&qf)[2][2], f32x4_t (&acc)[4][2], float (&m)[2],
-                                         float (&l)[2], int fr, int fg, const int (&lim)[2]) {
+                                         float (&l)[2], int fr, int fg, const int (&lim)[2],
+                                         const int (&low)[2]) {
   static_assert(EDGE || !LIM, "the masked body is an edge body");
+  static_assert(LIM || !WIN, "the windowed body is a masked body");
   // valid keys in this tile: 16-key sub-tiles (and 32-key PV steps) past N are skipped
   // (N = 197 -> the last tile holds 5 keys: 13 sub-tiles of 16 computed instead of 16)
   const int nvk = EDGE ? N - t * kTile : kTile;
@@ -133,20 +152,25 @@ __device__ __forceinline__ void fwd_tile(const uint4* Kt, const uint4* Vt, int t
       for (int i = 0; i < 4; ++i) {
         if constexpr (EDGE) {
           if (key0 + 16 * mt + i >= (LIM ? lim[qt] : N)) s[mt][qt][i] = -INFINITY;
+          if constexpr (WIN) {
+            if (key0 + 16 * mt + i < low[qt]) s[mt][qt][i] = -INFINITY;
+          }
         }
         mx = fmaxf(mx, s[mt][qt][i]);
       }
     mx = fmaxf(mx, __shfl_xor(mx, 16));
     mx = fmaxf(mx, __shfl_xor(mx, 32));
     const float mn = fmaxf(m[qt], mx * c);
-    const float alpha = __builtin_amdgcn_exp2f(m[qt] - mn);
+    float ms = mn;
+    if constexpr (WIN) ms = mn == -INFINITY ? 0.f : mn;  // no key seen yet: alpha = 0, every p = 0
+    const float alpha = __builtin_amdgcn_exp2f(m[qt] - ms);
     m[qt] = mn;
     float ls = 0.f;
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[mt][qt][i], c, -mn));
+        const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[mt][qt][i], c, -ms));
         s[mt][qt][i] = p;
         ls += p;
       }
@@ -174,20 +198,32 @@ __device__ __forceinline__ void fwd_tile(const uint4* Kt, const uint4* Vt, int t
 struct QLim {
   int lim[2];  // the lane's own queries' limits (q0 + 16 qt + fr)
   int lo, hi;  // smallest / largest limit in the wave (wave-uniform)
+  // windowed kernels: the lower limits max(0, limit - window) of the lane's queries and of the wave's
+  // first / last query (limits grow with the query, so these are the wave's smallest / largest)
+  int low[2];
+  int wlo, whi;
 };
 
+template <bool WIN = false>
 __device__ __forceinline__ QLim q_limits(const AttnArgs& a, int len, int q0, int fr) {
-  QLim r;
+  QLim r{};
   const int wq0 = __builtin_amdgcn_readfirstlane(q0);
   r.lo = a.causal ? min(len, wq0 + 1) : len;
   r.hi = a.causal ? min(len, wq0 + 32) : len;
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) r.lim[qt] = a.causal ? min(len, q0 + 16 * qt + fr + 1) : len;
+  if constexpr (WIN) {
+    r.wlo = max(0, r.lo - a.window);
+    r.whi = max(0, r.hi - a.window);
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) r.low[qt] = max(0, r.lim[qt] - a.window);
+  }
   return r;
 }
 
-template <bool MASK>
+template <int MODE>
 __global__ __launch_bounds__(256, 2) void attn_fwd_k(AttnArgs a) {
+  constexpr bool MASK = MODE != kDense, WIN = MODE == kWin;
   __shared__ __attribute__((aligned(16))) uint4 lds[2 * 2 * kTileU4];  // [buf][K | V] = 32 KiB
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fg = lane >> 4;
@@ -223,17 +259,29 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_k(AttnArgs a) {
   // nt: tiles the workgroup visits (workgroup-uniform: every wave stages and meets the barrier of
   // each); nfull: the leading tiles the wave runs with the unmasked body
   int nt = (N + kTile - 1) / kTile, nfull = N / kTile;
+  // windowed: tb, the workgroup's first tile (workgroup-uniform, < nt), and ta, the end of the tiles
+  // from tb on that a lower limit of the wave cuts or hides; [ta, nfull) is then between the limits
+  int tb = 0, ta = 0;
   QLim ql{};
   if constexpr (MASK) {
     const int len = key_len(a, b);
-    ql = q_limits(a, len, q0, fr);
+    ql = q_limits<WIN>(a, len, q0, fr);
     // the largest limit of the workgroup's queries: key tiles past it are never staged
     const int lim_wg = a.causal ? min(len, min(N, xb * kBlk + kBlk)) : len;
     nt = (lim_wg + kTile - 1) / kTile;
     nfull = min(nt, ql.lo / kTile);
+    if constexpr (WIN) {
+      // the smallest lower limit of the workgroup is its first query's: key tiles before it are never staged
+      tb = max(0, min(len, xb * kBlk + 1) - a.window) / kTile;
+      ta = min(nt, max(tb, (ql.whi + kTile - 1) / kTile));
+      nfull = max(nfull, ta);
+    }
   }
-  stage_tile(lds, kp, a.sk[2], 0, N, wave, lane);
-  stage_tile(lds + kTileU4, vp, a.sv[2], 0, N, wave, lane);
+  {
+    uint4* K0 = lds + (tb & 1) * 2 * kTileU4;
+    stage_tile(K0, kp, a.sk[2], tb * kTile, N, wave, lane);
+    stage_tile(K0 + kTileU4, vp, a.sv[2], tb * kTile, N, wave, lane);
+  }
   auto next = [&](int t) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // tile t landed; every wave is done with the other buffer
@@ -247,10 +295,19 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_k(AttnArgs a) {
   // kernel); a wave with no query only helps stage tiles
   auto run = [&](auto nq) {
     constexpr int NQ = decltype(nq)::value;
-    for (int t = 0; t < nfull; ++t) {
+    if constexpr (WIN) {
+      // tiles a lower limit of the wave cuts through; before the wave's smallest one only stage and sync
+      for (int t = tb; t < ta; ++t) {
+        next(t);
+        const uint4* Kt = lds + (t & 1) * 2 * kTileU4;
+        if (wave_live && t * kTile < ql.hi && (t + 1) * kTile > ql.wlo)
+          fwd_tile<true, true, true>(Kt, Kt + kTileU4, t, ql.hi, NQ, c, qf, acc, m, l, fr, fg, ql.lim, ql.low);
+      }
+    }
+    for (int t = WIN ? ta : 0; t < nfull; ++t) {
       next(t);
       const uint4* Kt = lds + (t & 1) * 2 * kTileU4;
-      if (wave_live) fwd_tile<false>(Kt, Kt + kTileU4, t, N, NQ, c, qf, acc, m, l, fr, fg, ql.lim);
+      if (wave_live) fwd_tile<false>(Kt, Kt + kTileU4, t, N, NQ, c, qf, acc, m, l, fr, fg, ql.lim, ql.low);
     }
     if constexpr (MASK) {
       // tiles a limit of the wave cuts through; past the wave's largest limit only stage and sync
@@ -258,12 +315,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_k(AttnArgs a) {
         next(t);
         const uint4* Kt = lds + (t & 1) * 2 * kTileU4;
         if (wave_live && t * kTile < ql.hi)
-          fwd_tile<true, true>(Kt, Kt + kTileU4, t, ql.hi, NQ, c, qf, acc, m, l, fr, fg, ql.lim);
+          fwd_tile<true, true, WIN>(Kt, Kt + kTileU4, t, ql.hi, NQ, c, qf, acc, m, l, fr, fg, ql.lim, ql.low);
       }
     } else if (nfull < nt) {
       next(nfull);
       const uint4* Kt = lds + (nfull & 1) * 2 * kTileU4;
-      if (wave_live) fwd_tile<true>(Kt, Kt + kTileU4, nfull, N, NQ, c, qf, acc, m, l, fr, fg, ql.lim);
+      if (wave_live) fwd_tile<true>(Kt, Kt + kTileU4, nfull, N, NQ, c, qf, acc, m, l, fr, fg, ql.lim, ql.low);
     }
   };
   if (nqt == 2) run(std::integral_constant<int, 2>{});
@@ -335,14 +392,14 @@ __global__ __launch_bounds__(512, MASK ? 1 : 2) void attn_fwd_head_k(AttnArgs a)
   }
   for (int t = 0; t < nfull; ++t)
     fwd_tile<false>(lds + t * kTileU4, lds + (kHeadTiles + t) * kTileU4, t, N, nqt, c, qf, acc, m, l, fr, fg,
-                    ql.lim);
+                    ql.lim, ql.low);
   if constexpr (MASK) {
     for (int t = nfull; t < nt; ++t)
       fwd_tile<true, true>(lds + t * kTileU4, lds + (kHeadTiles + t) * kTileU4, t, ql.hi, nqt, c, qf, acc, m, l, fr,
-                           fg, ql.lim);
+                           fg, ql.lim, ql.low);
   } else if (nfull < nt) {
     fwd_tile<true>(lds + nfull * kTileU4, lds + (kHeadTiles + nfull) * kTileU4, nfull, N, nqt, c, qf, acc, m, l, fr,
-                   fg, ql.lim);
+                   fg, ql.lim, ql.low);
   }
   fwd_store(a, b, h, q0, acc, m, l, fr, fg);
 }
@@ -383,12 +440,13 @@ __device__ __forceinline__ void dq_rows(const AttnArgs& a, int b, int h, int q0,
 }
 
 // One 64-key tile of the dQ pass: Sᵀ = K·Qᵀ, dPᵀ = V·dOᵀ, dSᵀ = Pᵀ∘(dPᵀ-δ), dQᵀ += Kᵀ·dSᵀ
-// (LIM: as fwd_tile)
-template <bool EDGE, bool LIM = false>
+// (LIM, WIN: as fwd_tile; the stored log-sum-exp is finite, so there is nothing to guard)
+template <bool EDGE, bool LIM = false, bool WIN = false>
 __device__ __forceinline__ void dq_tile(const uint4* Kt, const uint4* Vt, int t, int N, int nqt, float c,
                                         const DqRows& r, f32x4_t (&acc)[4][2], int fr, int fg,
-                                        const int (&lim)[2]) {
+                                        const int (&lim)[2], const int (&low)[2]) {
   static_assert(EDGE || !LIM, "the masked body is an edge body");
+  static_assert(LIM || !WIN, "the windowed body is a masked body");
   const int nvk = EDGE ? N - t * kTile : kTile;  // valid keys in the tile
   f32x4_t s[4][2], dp[4][2];
 #pragma unroll
@@ -419,9 +477,12 @@ __device__ __forceinline__ void dq_tile(const uint4* Kt, const uint4* Vt, int t,
     for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float p =
+        float p =
             !EDGE || key0 + 16 * mt + i < (LIM ? lim[qt] : N) ? __builtin_amdgcn_exp2f(s[mt][qt][i] * c - r.lse2[qt])
                                                               : 0.f;
+        if constexpr (WIN) {
+          if (key0 + 16 * mt + i < low[qt]) p = 0.f;
+        }
         s[mt][qt][i] = p * (dp[mt][qt][i] - r.delta[qt]);  // dS (in units of the scaled scores)
       }
 #pragma unroll
@@ -458,8 +519,9 @@ __device__ __forceinline__ void dq_store(const AttnArgs& a, int b, int h, int q0
 // ViT-B call and was removed, profiles/r05_vit.)
 // (The masked instantiation takes 176 VGPRs -- 32 B of scratch when held to 168 -- so it has bounds
 // of its own: two waves per SIMD.)
-template <bool MASK>
-__global__ __launch_bounds__(256, MASK ? 2 : 3) void attn_bwd_dq_k(AttnArgs a) {
+template <int MODE>
+__global__ __launch_bounds__(256, MODE != kDense ? 2 : 3) void attn_bwd_dq_k(AttnArgs a) {
+  constexpr bool MASK = MODE != kDense, WIN = MODE == kWin;
   __shared__ __attribute__((aligned(16))) uint4 lds[2 * 2 * kTileU4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fg = lane >> 4;
@@ -481,16 +543,25 @@ __global__ __launch_bounds__(256, MASK ? 2 : 3) void attn_bwd_dq_k(AttnArgs a) {
     for (int qt = 0; qt < 2; ++qt) acc[dt][qt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   int nt = (N + kTile - 1) / kTile, nfull = N / kTile;  // (both as the forward)
+  int tb = 0, ta = 0;                                    // (windowed: as the forward)
   QLim ql{};
   if constexpr (MASK) {
     const int len = key_len(a, b);
-    ql = q_limits(a, len, q0, fr);
+    ql = q_limits<WIN>(a, len, q0, fr);
     const int lim_wg = a.causal ? min(len, min(N, xb * kBlk + kBlk)) : len;
     nt = (lim_wg + kTile - 1) / kTile;
     nfull = min(nt, ql.lo / kTile);
+    if constexpr (WIN) {
+      tb = max(0, min(len, xb * kBlk + 1) - a.window) / kTile;
+      ta = min(nt, max(tb, (ql.whi + kTile - 1) / kTile));
+      nfull = max(nfull, ta);
+    }
   }
-  stage_tile(lds, kp, a.sk[2], 0, N, wave, lane);
-  stage_tile(lds + kTileU4, vp, a.sv[2], 0, N, wave, lane);
+  {
+    uint4* K0 = lds + (tb & 1) * 2 * kTileU4;
+    stage_tile(K0, kp, a.sk[2], tb * kTile, N, wave, lane);
+    stage_tile(K0 + kTileU4, vp, a.sv[2], tb * kTile, N, wave, lane);
+  }
   // tile t landed (every wave is done with the other buffer) -> stage tile t + 1 into it
   auto next = [&](int t) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -506,22 +577,30 @@ __global__ __launch_bounds__(256, MASK ? 2 : 3) void attn_bwd_dq_k(AttnArgs a) {
   // the loop, which pass the same barriers in the same order
   auto run = [&](auto nq) {
     constexpr int NQ = decltype(nq)::value;
-    for (int t = 0; t < nfull; ++t) {
+    if constexpr (WIN) {
+      for (int t = tb; t < ta; ++t) {  // (as the forward)
+        next(t);
+        const uint4* Kt = lds + (t & 1) * 2 * kTileU4;
+        if (wave_live && t * kTile < ql.hi && (t + 1) * kTile > ql.wlo)
+          dq_tile<true, true, true>(Kt, Kt + kTileU4, t, ql.hi, NQ, c, r, acc, fr, fg, ql.lim, ql.low);
+      }
+    }
+    for (int t = WIN ? ta : 0; t < nfull; ++t) {
       next(t);
       const uint4* Kt = lds + (t & 1) * 2 * kTileU4;
-      if (wave_live) dq_tile<false>(Kt, Kt + kTileU4, t, N, NQ, c, r, acc, fr, fg, ql.lim);
+      if (wave_live) dq_tile<false>(Kt, Kt + kTileU4, t, N, NQ, c, r, acc, fr, fg, ql.lim, ql.low);
     }
     if constexpr (MASK) {
       for (int t = nfull; t < nt; ++t) {  // (as the forward)
         next(t);
         const uint4* Kt = lds + (t & 1) * 2 * kTileU4;
         if (wave_live && t * kTile < ql.hi)
-          dq_tile<true, true>(Kt, Kt + kTileU4, t, ql.hi, NQ, c, r, acc, fr, fg, ql.lim);
+          dq_tile<true, true, WIN>(Kt, Kt + kTileU4, t, ql.hi, NQ, c, r, acc, fr, fg, ql.lim, ql.low);
       }
     } else if (nfull < nt) {
       next(nfull);
       const uint4* Kt = lds + (nfull & 1) * 2 * kTileU4;
-      if (wave_live) dq_tile<true>(Kt, Kt + kTileU4, nfull, N, NQ, c, r, acc, fr, fg, ql.lim);
+      if (wave_live) dq_tile<true>(Kt, Kt + kTileU4, nfull, N, NQ, c, r, acc, fr, fg, ql.lim, ql.low);
     }
   };
   if (nqt == 2) run(std::integral_constant<int, 2>{});
@@ -554,10 +633,13 @@ __device__ __forceinline__ void kv_rows(const AttnArgs& a, int b, int h, int k0,
 // lse_t / del_t: the tile's 64 log2-domain log-sum-exps (+inf past N) and deltas in LDS.
 // LIM (masked kernels): qmin[kt] is the first query that sees the lane's key (the key itself when
 // causal, 0 otherwise, INT_MAX for a key at or past the length): P = 0 for the queries before it.
-template <bool EDGE, bool LIM = false>
+// WIN (windowed kernels, with LIM): qmax[kt] is the end of the queries that see the key: P = 0 from it on.
+template <bool EDGE, bool LIM = false, bool WIN = false>
 __device__ __forceinline__ void dkdv_tile(const uint4* Qt, const uint4* Dt, const float* lse_t, const float* del_t,
                                           int t, int N, int nkt, float c, const KvRows& r, f32x4_t (&dv)[4][2],
-                                          f32x4_t (&dk)[4][2], int fr, int fg, const int (&qmin)[2]) {
+                                          f32x4_t (&dk)[4][2], int fr, int fg, const int (&qmin)[2],
+                                          const int (&qmax)[2]) {
+  static_assert(LIM || !WIN, "the windowed body is a masked body");
   const int nvq = EDGE ? N - t * kTile : kTile;  // valid queries in the tile
   f32x4_t s[4][2], dp[4][2];
 #pragma unroll
@@ -594,6 +676,9 @@ __device__ __forceinline__ void dkdv_tile(const uint4* Qt, const uint4* Dt, cons
         float p = __builtin_amdgcn_exp2f(s[mt][kt][i] * c - lv[i]);
         if constexpr (LIM) {
           if (t * kTile + 16 * mt + 4 * fg + i < qmin[kt]) p = 0.f;
+        }
+        if constexpr (WIN) {
+          if (t * kTile + 16 * mt + 4 * fg + i >= qmax[kt]) p = 0.f;
         }
         s[mt][kt][i] = p;
         dp[mt][kt][i] = p * (dp[mt][kt][i] - dl[i]);
@@ -649,10 +734,16 @@ struct KLim {
   int k0;       // wave-uniform copy of the wave's first key
   bool work;    // some key of the wave is inside the length
   int tm;
+  // windowed kernels.  Key j < len is seen by the queries j <= i < j + window and, as a pad query
+  // (i >= len) sees the last `window` valid keys, by every i >= j when j >= len - window: INT_MAX.
+  int qmax[2];  // the end of the queries that see the lane's own keys
+  int qfull;    // the smallest qmax of the wave (its first key's): every query before it sees every key
+  int qend;     // the largest qmax of the wave's keys inside the length (its last such key's)
 };
 
+template <bool WIN = false>
 __device__ __forceinline__ KLim k_limits(const AttnArgs& a, int len, int k0, int fr, int t0, int t_end) {
-  KLim r;
+  KLim r{};
   r.k0 = __builtin_amdgcn_readfirstlane(k0);
   r.work = r.k0 < len;
 #pragma unroll
@@ -663,11 +754,23 @@ __device__ __forceinline__ KLim k_limits(const AttnArgs& a, int len, int k0, int
   // causal: the first tile whose every query sees every key of the wave starts at or after k0 + 31
   const int tm = r.k0 + 32 > len ? t_end : a.causal ? (r.k0 + 31 + kTile - 1) / kTile : t0;
   r.tm = min(max(tm, t0), t_end);
+  if constexpr (WIN) {
+    const int edge = len - a.window;  // keys from here on are seen by every later query
+#pragma unroll
+    for (int kt = 0; kt < 2; ++kt) {
+      const int ki = k0 + 16 * kt + fr;
+      r.qmax[kt] = ki < edge ? ki + a.window : INT_MAX;
+    }
+    const int last = min(r.k0 + 32, len) - 1;
+    r.qfull = r.k0 < edge ? r.k0 + a.window : INT_MAX;
+    r.qend = last < edge ? last + a.window : INT_MAX;
+  }
   return r;
 }
 
-template <bool MASK>
+template <int MODE>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_k(AttnArgs a) {
+  constexpr bool MASK = MODE != kDense, WIN = MODE == kWin;
   // [buf][Q | dO] tiles, then [buf][lse2 | delta] x 64 floats
   __shared__ __attribute__((aligned(16))) uint4 lds[2 * 2 * kTileU4 + 2 * 2 * kTile / 4];
   float* rowc = reinterpret_cast<float*>(lds + 2 * 2 * kTileU4);
@@ -715,8 +818,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_k(AttnArgs a) {
     // no tile, stages nothing and stores its zero accumulators.
     const int len = key_len(a, b);
     const int t0 = a.causal ? xb * (kBlk / kTile) : 0;
-    const int t_end = xb * kBlk < len ? nt : t0;
-    const KLim kl = k_limits(a, len, k0, fr, t0, t_end);
+    int t_end = xb * kBlk < len ? nt : t0;
+    if constexpr (WIN) {
+      // the block's last key inside the length: unless it is one of the last `window` valid keys (which
+      // every later query sees), no query from last + window on sees a key of the block
+      const int last = min(xb * kBlk + kBlk, len) - 1;
+      if (t0 < t_end && last < len - a.window) t_end = min(nt, (last + a.window + kTile - 1) / kTile);
+    }
+    const KLim kl = k_limits<WIN>(a, len, k0, fr, t0, t_end);
     const bool work = wave_live && kl.work;
     if (t0 < t_end) issue(t0, t0 & 1);
     auto next = [&](int t) {
@@ -730,22 +839,36 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_k(AttnArgs a) {
       const uint4* Qt = lds + (t & 1) * 2 * kTileU4;
       const float* lse_t = rowc + (t & 1) * 2 * kTile;
       // (causal: a tile whose last query is before the wave's first key only stages and syncs)
-      if (work && (!a.causal || (t + 1) * kTile > kl.k0))
-        dkdv_tile<true, true>(Qt, Qt + kTileU4, lse_t, lse_t + kTile, t, N, nkt, c, r, dv, dk, fr, fg, kl.qmin);
+      if (work && (!a.causal || (t + 1) * kTile > kl.k0) && (!WIN || t * kTile < kl.qend))
+        dkdv_tile<true, true, WIN>(Qt, Qt + kTileU4, lse_t, lse_t + kTile, t, N, nkt, c, r, dv, dk, fr, fg, kl.qmin,
+                                   kl.qmax);
     }
-    const int nf = min(nfull, t_end);
+    // windowed: the unmasked tiles end where a query no longer sees the wave's first key
+    const int nf = WIN ? min(max(min(nfull, kl.qfull / kTile), kl.tm), t_end) : min(nfull, t_end);
     for (int t = kl.tm; t < nf; ++t) {
       next(t);
       const uint4* Qt = lds + (t & 1) * 2 * kTileU4;
       const float* lse_t = rowc + (t & 1) * 2 * kTile;
-      if (work) dkdv_tile<false>(Qt, Qt + kTileU4, lse_t, lse_t + kTile, t, N, nkt, c, r, dv, dk, fr, fg, kl.qmin);
+      if (work)
+        dkdv_tile<false>(Qt, Qt + kTileU4, lse_t, lse_t + kTile, t, N, nkt, c, r, dv, dk, fr, fg, kl.qmin, kl.qmax);
     }
-    if (nfull < t_end && kl.tm <= nfull) {  // the edge tile, unless the masked loop took it
+    if constexpr (WIN) {
+      // the tiles the windows' ends cut through, the edge tile among them; past the wave's last only stage and sync
+      for (int t = nf; t < t_end; ++t) {
+        next(t);
+        const uint4* Qt = lds + (t & 1) * 2 * kTileU4;
+        const float* lse_t = rowc + (t & 1) * 2 * kTile;
+        if (work && t * kTile < kl.qend)
+          dkdv_tile<true, true, true>(Qt, Qt + kTileU4, lse_t, lse_t + kTile, t, N, nkt, c, r, dv, dk, fr, fg, kl.qmin,
+                                      kl.qmax);
+      }
+    } else if (nfull < t_end && kl.tm <= nfull) {  // the edge tile, unless the masked loop took it
       next(nfull);
       const uint4* Qt = lds + (nfull & 1) * 2 * kTileU4;
       const float* lse_t = rowc + (nfull & 1) * 2 * kTile;
       if (work)
-        dkdv_tile<true>(Qt, Qt + kTileU4, lse_t, lse_t + kTile, nfull, N, nkt, c, r, dv, dk, fr, fg, kl.qmin);
+        dkdv_tile<true>(Qt, Qt + kTileU4, lse_t, lse_t + kTile, nfull, N, nkt, c, r, dv, dk, fr, fg, kl.qmin,
+                        kl.qmax);
     }
   } else {
     const int none[2] = {0, 0};
@@ -760,14 +883,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_k(AttnArgs a) {
       next(t);
       const uint4* Qt = lds + (t & 1) * 2 * kTileU4;
       const float* lse_t = rowc + (t & 1) * 2 * kTile;
-      if (wave_live) dkdv_tile<false>(Qt, Qt + kTileU4, lse_t, lse_t + kTile, t, N, nkt, c, r, dv, dk, fr, fg, none);
+      if (wave_live)
+        dkdv_tile<false>(Qt, Qt + kTileU4, lse_t, lse_t + kTile, t, N, nkt, c, r, dv, dk, fr, fg, none, none);
     }
     if (nfull < nt) {
       next(nfull);
       const uint4* Qt = lds + (nfull & 1) * 2 * kTileU4;
       const float* lse_t = rowc + (nfull & 1) * 2 * kTile;
       if (wave_live)
-        dkdv_tile<true>(Qt, Qt + kTileU4, lse_t, lse_t + kTile, nfull, N, nkt, c, r, dv, dk, fr, fg, none);
+        dkdv_tile<true>(Qt, Qt + kTileU4, lse_t, lse_t + kTile, nfull, N, nkt, c, r, dv, dk, fr, fg, none, none);
     }
   }
   dkdv_store(a, b, h, k0, dk, dv, fr, fg);
@@ -830,21 +954,21 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkdv_head_k(AttnArgs a) {
       if (!kl.work) return;  // every key of the wave is past the length: zeros are stored
       for (int t = t0; t < kl.tm; ++t)
         dkdv_tile<true, true>(lds + t * kTileU4, lds + (kHeadTiles + t) * kTileU4, rowc + t * kTile,
-                              rowc + kRows + t * kTile, t, N, NK, c, r, dv, dk, fr, fg, kl.qmin);
+                              rowc + kRows + t * kTile, t, N, NK, c, r, dv, dk, fr, fg, kl.qmin, kl.qmax);
       for (int t = kl.tm; t < nfull; ++t)
         dkdv_tile<false>(lds + t * kTileU4, lds + (kHeadTiles + t) * kTileU4, rowc + t * kTile,
-                         rowc + kRows + t * kTile, t, N, NK, c, r, dv, dk, fr, fg, kl.qmin);
+                         rowc + kRows + t * kTile, t, N, NK, c, r, dv, dk, fr, fg, kl.qmin, kl.qmax);
       if (nfull < nt && kl.tm <= nfull)
         dkdv_tile<true>(lds + nfull * kTileU4, lds + (kHeadTiles + nfull) * kTileU4, rowc + nfull * kTile,
-                        rowc + kRows + nfull * kTile, nfull, N, NK, c, r, dv, dk, fr, fg, kl.qmin);
+                        rowc + kRows + nfull * kTile, nfull, N, NK, c, r, dv, dk, fr, fg, kl.qmin, kl.qmax);
     } else {
       const int none[2] = {0, 0};
       for (int t = 0; t < nfull; ++t)
         dkdv_tile<false>(lds + t * kTileU4, lds + (kHeadTiles + t) * kTileU4, rowc + t * kTile,
-                         rowc + kRows + t * kTile, t, N, NK, c, r, dv, dk, fr, fg, none);
+                         rowc + kRows + t * kTile, t, N, NK, c, r, dv, dk, fr, fg, none, none);
       if (nfull < nt)
         dkdv_tile<true>(lds + nfull * kTileU4, lds + (kHeadTiles + nfull) * kTileU4, rowc + nfull * kTile,
-                        rowc + kRows + nfull * kTile, nfull, N, NK, c, r, dv, dk, fr, fg, none);
+                        rowc + kRows + nfull * kTile, nfull, N, NK, c, r, dv, dk, fr, fg, none, none);
     }
   };
   if (nkt == 2) run(std::integral_constant<int, 2>{});
@@ -870,16 +994,22 @@ int attn_set_head_mask(int mask) {
   return old;
 }
 
-// the masked instantiations run only when a mask is requested (same grids, same kernel choice)
+// the masked instantiations run only when a mask is requested (same grids, same kernel choice); a
+// windowed call always takes the 128-row kernels, whatever N and attn_set_head_mask say
 void attn_fwd(const AttnArgs& a, hipStream_t st) {
   const bool mask = a.causal || a.klen;
+  if (a.window > 0) {
+    const int nblk = (a.N + kBlk - 1) / kBlk;
+    hipLaunchKernelGGL(attn_fwd_k<kWin>, dim3(nblk * a.H * a.B), dim3(256), 0, st, a);
+    return;
+  }
   if ((g_attn_head & 1) && a.N <= kHeadTiles * kTile) {
     hipLaunchKernelGGL(mask ? attn_fwd_head_k<true> : attn_fwd_head_k<false>, dim3(a.H * a.B),
                        dim3(kHeadWaves * 64), 0, st, a);
     return;
   }
   const int nblk = (a.N + kBlk - 1) / kBlk;
-  hipLaunchKernelGGL(mask ? attn_fwd_k<true> : attn_fwd_k<false>, dim3(nblk * a.H * a.B), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(mask ? attn_fwd_k<kMask> : attn_fwd_k<kDense>, dim3(nblk * a.H * a.B), dim3(256), 0, st, a);
 }
 
 void attn_bwd(const AttnArgs& a, hipStream_t st) {
@@ -887,12 +1017,18 @@ void attn_bwd(const AttnArgs& a, hipStream_t st) {
   const bool fits = a.N <= kHeadTiles * kTile;
   const int nblk = (a.N + kBlk - 1) / kBlk;
   // dQ pass first: it also writes delta = rowsum(dO * O), which the dK/dV pass reads
-  hipLaunchKernelGGL(mask ? attn_bwd_dq_k<true> : attn_bwd_dq_k<false>, dim3(nblk * a.H * a.B), dim3(256), 0, st, a);
+  if (a.window > 0) {
+    hipLaunchKernelGGL(attn_bwd_dq_k<kWin>, dim3(nblk * a.H * a.B), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(attn_bwd_dkdv_k<kWin>, dim3(nblk * a.H * a.B), dim3(256), 0, st, a);
+    return;
+  }
+  hipLaunchKernelGGL(mask ? attn_bwd_dq_k<kMask> : attn_bwd_dq_k<kDense>, dim3(nblk * a.H * a.B), dim3(256), 0, st,
+                     a);
   if ((g_attn_head & 4) && fits)
     hipLaunchKernelGGL(mask ? attn_bwd_dkdv_head_k<true> : attn_bwd_dkdv_head_k<false>, dim3(a.H * a.B),
                        dim3(kHeadWaves * 64), 0, st, a);
   else
-    hipLaunchKernelGGL(mask ? attn_bwd_dkdv_k<true> : attn_bwd_dkdv_k<false>, dim3(nblk * a.H * a.B), dim3(256), 0,
+    hipLaunchKernelGGL(mask ? attn_bwd_dkdv_k<kMask> : attn_bwd_dkdv_k<kDense>, dim3(nblk * a.H * a.B), dim3(256), 0,
                        st, a);
 }
 

@@ -44,6 +44,15 @@
 // Rows at or past len never enter arithmetic: their loads are not issued (the row index is
 // clamped to the chunk's first row, which is < len, and the load is predicated), and their
 // probability is the constant 0, not exp2 of anything.  The cache may hold any bit pattern there.
+//
+// Sliding window (AttnDecodeArgs::window = W > 0, a host value): the query sees rows lo <= j < len,
+// lo = max(0, len - W), and the rows below lo are treated exactly as the rows at or past len: not
+// loaded, probability the constant 0.  A wave whose chunk ends at or below lo writes "empty" and exits,
+// so a step streams at most W rows (plus what 8-row alignment adds) whatever len is; the chunk lo cuts
+// starts its row loop at lo rounded down to 8, which keeps a wave load one aligned 1 KiB.  The grid is
+// still a function of cap.  The merge takes its maximum over all chunks and skips the empty ones
+// wherever they are: the chunk that holds row len - 1 is never empty.  The split kernels are templates
+// on WIN: the <false> instantiations, which every call without a window takes, are the code they were.
 #include "common.h"
 #include "tbamd.h"
 
@@ -111,7 +120,7 @@ struct AttnNewRow {
 // to the cache: exactly one store per row, and no wave reads that cache row.  p outside [0, cap)
 // equals no visible row index: nothing is stored.  With one chunk the wave finishes each head with
 // the merge kernel's own arithmetic (M - M, fma by exp2 of it, divide) and writes bf16.
-template <bool FUSED, int GB>
+template <bool FUSED, int GB, bool WIN>
 __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, const AttnNewRow& n) {
   const int lane = threadIdx.x;
   const int g = lane >> 3, c = lane & 7;
@@ -126,7 +135,8 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
   const int start = ck * a.chunk;
   float* wm = a.ws + (int64_t)a.nparts * 64;
   float* wl = wm + a.nparts;
-  if (start >= len) {  // wave-uniform
+  const int lo = WIN ? max(len - a.window, 0) : 0;  // the first visible row (< len)
+  if (start >= len || (WIN && start + a.chunk <= lo)) {  // wave-uniform
     if (lane < GB) {
       wm[part0 + lane * a.nchunks] = -INFINITY;
       wl[part0 + lane * a.nchunks] = 0.f;
@@ -134,6 +144,9 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
     return;
   }
   const int end = min(start + a.chunk, len);
+  // the chunk's first visible row (lo < len and lo < start + chunk: < end), and the 8-row group it is in
+  const int vis = WIN ? max(start, lo) : start;
+  const int first = WIN ? max(start, lo & ~7) : start;
 
   float q[GB][8];
 #pragma unroll
@@ -152,14 +165,14 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
     for (int i = 0; i < 8; ++i) acc[j][i] = 0.f;
   }
 
-  for (int r0 = start + g; r0 < end; r0 += 8 * kUnroll) {
+  for (int r0 = first + g; r0 < end; r0 += 8 * kUnroll) {
     uint4 kr[kUnroll], vr[kUnroll];
     bool ok[kUnroll];
 #pragma unroll
     for (int u = 0; u < kUnroll; ++u) {
       const int r = r0 + 8 * u;
-      ok[u] = r < end;
-      const int rr = ok[u] ? r : start;  // a hidden row never forms an address
+      ok[u] = r < end && (!WIN || r >= lo);
+      const int rr = ok[u] ? r : vis;  // a hidden row never forms an address
       kr[u] = make_uint4(0, 0, 0, 0);
       vr[u] = make_uint4(0, 0, 0, 0);
       if (FUSED && ok[u] && (int64_t)r == p) {  // 0 <= r < len <= cap: the store is inside the cache
@@ -193,7 +206,9 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
         mn[j] = fmaxf(mn[j], s[j][u]);
       }
     }
-    // r0 < end: row u = 0 is visible, so mn is finite from here on
+    // r0 < end: row u = 0 is visible, so mn is finite from here on -- except in a row group's first
+    // pass over the chunk a window cuts, where r0 may lie below lo: if none of its rows is visible,
+    // mn = m = -inf, alpha is the constant 0 and no p is exp2 of anything
 #pragma unroll
     for (int j = 0; j < GB; ++j) {
       const float alpha = m[j] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m[j] - mn[j]);
@@ -258,14 +273,14 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
   }
 }
 
-template <int GB>
+template <int GB, bool WIN>
 __global__ __launch_bounds__(64) void attn_decode_split_k(AttnDecodeArgs a) {
-  attn_decode_split_body<false, GB>(a, AttnNewRow{nullptr, nullptr, 0});
+  attn_decode_split_body<false, GB, WIN>(a, AttnNewRow{nullptr, nullptr, 0});
 }
 
-template <int GB>
+template <int GB, bool WIN>
 __global__ __launch_bounds__(64) void attn_decode_append_split_k(AttnDecodeArgs a, AttnNewRow n) {
-  attn_decode_split_body<true, GB>(a, n);
+  attn_decode_split_body<true, GB, WIN>(a, n);
 }
 
 // grid: B * H one-wave workgroups; lane = output dim
@@ -277,7 +292,7 @@ __global__ __launch_bounds__(64) void attn_decode_merge_k(AttnDecodeArgs a) {
   const float* wm = a.ws + (int64_t)a.nparts * 64 + (int64_t)bh * a.nchunks;
   const float* wl = wm + a.nparts;
   float M = -INFINITY;
-  for (int ck = 0; ck < a.nchunks; ++ck) M = fmaxf(M, wm[ck]);  // chunk 0 is never empty: finite
+  for (int ck = 0; ck < a.nchunks; ++ck) M = fmaxf(M, wm[ck]);  // the chunk of row len - 1 is never empty: finite
   float o = 0.f, L = 0.f;
   for (int ck = 0; ck < a.nchunks; ++ck) {
     const float mc = wm[ck];
@@ -339,10 +354,13 @@ int attn_decode_set_head_block(int n) {
   return old;
 }
 
-int attn_decode_head_block(int B, int H, int Hkv, int cap) {
+int attn_decode_head_block(int B, int H, int Hkv, int cap, int window) {
   const int G = H / Hkv;
   if (g_decode_head_block && G % g_decode_head_block == 0) return g_decode_head_block;
-  const int64_t waves = (int64_t)B * H * attn_decode_chunks(cap);
+  // the waves that stream rows: under a window the other chunks write "empty" and exit
+  int live = attn_decode_chunks(cap);
+  if (window > 0 && (int64_t)window + g_decode_chunk < cap) live = attn_decode_chunks(window + g_decode_chunk);
+  const int64_t waves = (int64_t)B * H * live;
   for (int gb = 4; gb > 1; --gb)
     if (G % gb == 0 && waves / gb >= kDecodeShareWaves) return gb;
   return 1;
@@ -354,21 +372,38 @@ static int decode_plan(AttnDecodeArgs& a) {
   a.nchunks = attn_decode_chunks(a.cap);
   a.nparts = a.B * a.H * a.nchunks;
   a.group = a.H / a.Hkv;
-  const int gb = attn_decode_head_block(a.B, a.H, a.Hkv, a.cap);
+  const int gb = attn_decode_head_block(a.B, a.H, a.Hkv, a.cap, a.window);
   a.nblk = a.group / gb;
   return gb;
+}
+
+// the split launch for head block gb; WIN: the windowed instantiations
+template <bool WIN>
+static void launch_split(int gb, dim3 grid, const AttnDecodeArgs& a, hipStream_t st) {
+  switch (gb) {
+    case 1: hipLaunchKernelGGL((attn_decode_split_k<1, WIN>), grid, dim3(64), 0, st, a); break;
+    case 2: hipLaunchKernelGGL((attn_decode_split_k<2, WIN>), grid, dim3(64), 0, st, a); break;
+    case 3: hipLaunchKernelGGL((attn_decode_split_k<3, WIN>), grid, dim3(64), 0, st, a); break;
+    default: hipLaunchKernelGGL((attn_decode_split_k<4, WIN>), grid, dim3(64), 0, st, a); break;
+  }
+}
+
+template <bool WIN>
+static void launch_append_split(int gb, dim3 grid, const AttnDecodeArgs& a, const AttnNewRow& n, hipStream_t st) {
+  switch (gb) {
+    case 1: hipLaunchKernelGGL((attn_decode_append_split_k<1, WIN>), grid, dim3(64), 0, st, a, n); break;
+    case 2: hipLaunchKernelGGL((attn_decode_append_split_k<2, WIN>), grid, dim3(64), 0, st, a, n); break;
+    case 3: hipLaunchKernelGGL((attn_decode_append_split_k<3, WIN>), grid, dim3(64), 0, st, a, n); break;
+    default: hipLaunchKernelGGL((attn_decode_append_split_k<4, WIN>), grid, dim3(64), 0, st, a, n); break;
+  }
 }
 
 void attn_decode(const AttnDecodeArgs& a_, hipStream_t st) {
   AttnDecodeArgs a = a_;
   const int gb = decode_plan(a);
   const dim3 grid(a.nparts / gb);  // B * Hkv * nblk * nchunks
-  switch (gb) {
-    case 1: hipLaunchKernelGGL(attn_decode_split_k<1>, grid, dim3(64), 0, st, a); break;
-    case 2: hipLaunchKernelGGL(attn_decode_split_k<2>, grid, dim3(64), 0, st, a); break;
-    case 3: hipLaunchKernelGGL(attn_decode_split_k<3>, grid, dim3(64), 0, st, a); break;
-    default: hipLaunchKernelGGL(attn_decode_split_k<4>, grid, dim3(64), 0, st, a); break;
-  }
+  if (a.window > 0) launch_split<true>(gb, grid, a, st);
+  else launch_split<false>(gb, grid, a, st);
   hipLaunchKernelGGL(attn_decode_merge_k, dim3(a.B * a.H), dim3(64), 0, st, a);
 }
 
@@ -379,12 +414,8 @@ void attn_decode_append(const AttnDecodeArgs& a_, const uint16_t* nk, const uint
   const int gb = decode_plan(a);
   const dim3 grid(a.nparts / gb);
   const AttnNewRow n{nk, nv, snew};
-  switch (gb) {
-    case 1: hipLaunchKernelGGL(attn_decode_append_split_k<1>, grid, dim3(64), 0, st, a, n); break;
-    case 2: hipLaunchKernelGGL(attn_decode_append_split_k<2>, grid, dim3(64), 0, st, a, n); break;
-    case 3: hipLaunchKernelGGL(attn_decode_append_split_k<3>, grid, dim3(64), 0, st, a, n); break;
-    default: hipLaunchKernelGGL(attn_decode_append_split_k<4>, grid, dim3(64), 0, st, a, n); break;
-  }
+  if (a.window > 0) launch_append_split<true>(gb, grid, a, n, st);
+  else launch_append_split<false>(gb, grid, a, n, st);
   if (a.nchunks > 1) hipLaunchKernelGGL(attn_decode_merge_k, dim3(a.B * a.H), dim3(64), 0, st, a);
 }
 

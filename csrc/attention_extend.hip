@@ -52,6 +52,18 @@
 // Rows between a query's own limit L(b, t) and hi are the rows this call's tokens just appended
 // for later queries of the same 16-query tile: real finite data.  Their scores are masked to -inf,
 // their probability is an exact 0, and that 0 IS multiplied with their v in the MFMA.
+//
+// Sliding window (AttnExtendArgs::window = W > 0, a host value): query t sees the rows
+// max(0, L(b, t) - W) <= j < L(b, t).  lo = the lower limit of the tile's FIRST query (the smallest,
+// as L grows with t), raised to the split's start: a split that ends at or below it writes "empty", and
+// rows below lo are treated as the rows at or past hi -- zero K fragment, index replaced before an
+// address is formed, zero-row V staging -- so they never enter arithmetic.  Rows between lo and a
+// query's own lower limit are real, previously appended data whose scores are masked to -inf (an
+// exact-zero probability in the MFMA).  Visibility inside a split is now an interval: a row may see
+// nothing in one tile and something in the next (the ms guard below covers it), and a row's first
+// non-empty split need not be split 0 -- the merge takes its maximum over all splits, and the split
+// that holds row L(b, t) - 1 is never empty for query t.  The split kernel is a template on WIN: the
+// <false> instantiation, which every call without a window takes, is the code it was.
 #include "common.h"
 #include "mfma_tile.h"
 #include "tbamd.h"
@@ -71,13 +83,15 @@ __device__ __forceinline__ int extend_len(const int* pos, int b, int t, int cap)
 }
 
 // A fragments of key rows k0 .. k0 + 63: lane holds K[k0 + 16 mt + fr][32 ks + 8 fg .. + 7]
-__device__ __forceinline__ void load_k(bf16x8_t (&kf)[4][2], const uint16_t* kb, int64_t rs, int k0, int start, int hi,
+// (rows outside [lo, hi) are zeros; lo itself is a row inside the range: the split's start without a window)
+template <bool WIN>
+__device__ __forceinline__ void load_k(bf16x8_t (&kf)[4][2], const uint16_t* kb, int64_t rs, int k0, int lo, int hi,
                                        int fr, int fg) {
 #pragma unroll
   for (int mt = 0; mt < 4; ++mt) {
     const int r = k0 + 16 * mt + fr;
-    const bool ok = r < hi;
-    const int rr = ok ? r : start;  // a hidden row never forms an address
+    const bool ok = r < hi && (!WIN || r >= lo);
+    const int rr = ok ? r : lo;  // a hidden row never forms an address
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       kf[mt][ks] = bf16x8_t{};
@@ -87,13 +101,29 @@ __device__ __forceinline__ void load_k(bf16x8_t (&kf)[4][2], const uint16_t* kb,
 }
 
 // V rows k0 .. k0 + 63 -> swizzled LDS tile by ONE wave (stage_tile's four wave slots in turn);
-// rows at or past hi come from the zero row
-__device__ __forceinline__ void stage_v(uint4* tile, const uint16_t* vb, int64_t rs, int k0, int hi, int lane) {
+// rows at or past hi and, under a window, rows below lo come from the zero row
+template <bool WIN>
+__device__ __forceinline__ void stage_v(uint4* tile, const uint16_t* vb, int64_t rs, int k0, int lo, int hi,
+                                        int lane) {
+  if constexpr (!WIN) {
 #pragma unroll
-  for (int w = 0; w < 4; ++w) stage_tile(tile, vb, rs, k0, hi, w, lane);
+    for (int w = 0; w < 4; ++w) stage_tile(tile, vb, rs, k0, hi, w, lane);
+    return;
+  }
+#pragma unroll
+  for (int w = 0; w < 4; ++w)
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {  // stage_tile with a lower row bound
+      const int row = 32 * it + w * 8 + (lane >> 3);
+      const int r = k0 + row;
+      const int ch = (lane & 7) ^ aswz(row);
+      const void* src = r < hi && r >= lo ? (const void*)(vb + (int64_t)r * rs + ch * 8) : (const void*)g_tile_zero;
+      glds16(src, tile + (32 * it + w * 8) * 8);
+    }
 }
 
 // grid: B * H * nqt * nsplit one-wave workgroups, split fastest
+template <bool WIN>
 __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
   __shared__ __attribute__((aligned(16))) uint4 lds[2 * kTileU4];  // V, double buffered: 16 KiB
   const int lane = threadIdx.x;
@@ -110,7 +140,10 @@ __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
   const int hi = min(extend_len(a.pos, b, min(q0 + kQT, a.T) - 1, a.cap), start + a.split);
   float* wm = a.ws + (int64_t)a.nparts * (kQT * 64);
   float* wl = wm + (int64_t)a.nparts * kQT;
-  if (start >= hi) {
+  // the tile's smallest lower limit (its first query's) raised to the split: workgroup-uniform, < hi
+  // in a live split
+  const int lo = WIN ? max(start, extend_len(a.pos, b, q0, a.cap) - a.window) : start;
+  if (start >= hi || (WIN && lo >= hi)) {
     if (lane < kQT) {
       wm[(int64_t)part * kQT + lane] = -INFINITY;
       wl[(int64_t)part * kQT + lane] = 0.f;
@@ -120,6 +153,8 @@ __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
   const int qi = q0 + fr;
   const bool qreal = qi < a.T;
   const int lim = min(extend_len(a.pos, b, qreal ? qi : a.T - 1, a.cap), hi);  // the lane's own query
+  // its lower limit (0 without a window): keys below it are masked
+  const int low = WIN ? extend_len(a.pos, b, qreal ? qi : a.T - 1, a.cap) - a.window : 0;
 
   // Qᵀ as the B operand: lane holds Q[q0 + fr][32 ks + 8 fg .. + 7]
   bf16x8_t qf[2];
@@ -139,10 +174,12 @@ __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
   float m = -INFINITY, l = 0.f;
 
   bf16x8_t kn[4][2];
-  load_k(kn, kb, a.sk[2], start, start, hi, fr, fg);
-  stage_v(lds, vb, a.sv[2], start, hi, lane);
+  // tiles run from the 64-row tile of the split that holds lo (start itself without a window)
+  const int kbeg = WIN ? start + (lo - start) / kTile * kTile : start;
+  load_k<WIN>(kn, kb, a.sk[2], kbeg, lo, hi, fr, fg);
+  stage_v<WIN>(lds, vb, a.sv[2], kbeg, lo, hi, lane);
   int buf = 0;
-  for (int k0 = start; k0 < hi; k0 += kTile, buf ^= 1) {
+  for (int k0 = kbeg; k0 < hi; k0 += kTile, buf ^= 1) {
     wait_loads();
     __syncthreads();  // tile k0 landed (registers and LDS); the other buffer's reads are done
     bf16x8_t kf[4][2];
@@ -151,8 +188,8 @@ __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) kf[mt][ks] = kn[mt][ks];
     if (k0 + kTile < hi) {
-      load_k(kn, kb, a.sk[2], k0 + kTile, start, hi, fr, fg);
-      stage_v(lds + (buf ^ 1) * kTileU4, vb, a.sv[2], k0 + kTile, hi, lane);
+      load_k<WIN>(kn, kb, a.sk[2], k0 + kTile, lo, hi, fr, fg);
+      stage_v<WIN>(lds + (buf ^ 1) * kTileU4, vb, a.sv[2], k0 + kTile, lo, hi, lane);
     }
     const uint4* Vt = lds + buf * kTileU4;
 
@@ -171,13 +208,15 @@ __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
     for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        s[mt][i] = key0 + 16 * mt + i < lim ? s[mt][i] * c : -INFINITY;
+        const int key = key0 + 16 * mt + i;
+        s[mt][i] = key < lim && (!WIN || key >= low) ? s[mt][i] * c : -INFINITY;
         mx = fmaxf(mx, s[mt][i]);
       }
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
     const float mn = fmaxf(m, mx);
-    // a row that has seen no key yet (mn = -inf) must not form -inf - -inf
+    // a row that has seen no key yet (mn = -inf) must not form -inf - -inf (under a window that is
+    // any row whose lower limit lies past this tile, not only one that sees nothing in the split)
     const float ms = mn == -INFINITY ? 0.f : mn;
     const float alpha = __builtin_amdgcn_exp2f(m - ms);  // m = -inf: 0, and acc, l are 0 anyway
     m = mn;
@@ -205,7 +244,7 @@ __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
   l += __shfl_xor(l, 32, 64);
   // acc[dt][i] = Oᵀ[16 dt + 4 fg + i][fr]
   if (a.nsplit == 1) {
-    if (qreal) {  // split 0 holds key 0: l > 0
+    if (qreal) {  // the one split holds row L(b, t) - 1: l > 0
       const float inv = 1.f / l;
       uint16_t* op = a.o + b * a.so[0] + qi * a.so[1] + h * 64 + 4 * fg;
 #pragma unroll
@@ -236,7 +275,7 @@ __global__ __launch_bounds__(64) void attn_extend_merge_k(AttnExtendArgs a) {
   const float* wm = a.ws + (int64_t)a.nparts * (kQT * 64) + part0 * kQT + row;
   const float* wl = wm + (int64_t)a.nparts * kQT;
   float M = -INFINITY;
-  for (int s = 0; s < a.nsplit; ++s) M = fmaxf(M, wm[s * kQT]);  // split 0 is never empty: finite
+  for (int s = 0; s < a.nsplit; ++s) M = fmaxf(M, wm[s * kQT]);  // the split of row L(b, t) - 1 is never empty: finite
   float o = 0.f, L = 0.f;
   for (int s = 0; s < a.nsplit; ++s) {
     const float ms = wm[s * kQT];
@@ -306,7 +345,8 @@ void attn_extend(const AttnExtendArgs& a_, hipStream_t st) {
   a.nqt = (a.T + kQT - 1) / kQT;
   a.nparts = a.B * a.H * a.nqt * a.nsplit;
   a.group = a.H / a.Hkv;
-  hipLaunchKernelGGL(attn_extend_split_k, dim3(a.nparts), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(a.window > 0 ? attn_extend_split_k<true> : attn_extend_split_k<false>, dim3(a.nparts), dim3(64), 0,
+                     st, a);
   if (a.nsplit > 1) hipLaunchKernelGGL(attn_extend_merge_k, dim3(a.B * a.T * a.H), dim3(64), 0, st, a);
 }
 

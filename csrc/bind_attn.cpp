@@ -41,8 +41,14 @@ Tensor workspace_or_new(const optional<Tensor>& workspace, int64_t need, const T
 // The masks (self-attention; both optional): causal, and key_lengths = [B] int32 on q's device,
 // contiguous -- keys j >= key_lengths[b] are hidden from every query of batch b.  The kernels read
 // the lengths from device memory (no host sync, graph-capture safe) and clamp each into [1, N].
-void attn_masks(tbamd::AttnArgs& a, const Tensor& q, int64_t B, bool causal, const optional<Tensor>& key_lengths) {
+// window (0: none; needs causal): the sliding window of csrc/attention.hip.  One that can hide nothing
+// (>= N) is no window: the same kernels as without it.
+void attn_masks(tbamd::AttnArgs& a, const Tensor& q, int64_t B, bool causal, const optional<Tensor>& key_lengths,
+                int64_t window) {
+  TORCH_CHECK(window >= 0, "attention: window must be >= 1 (0: none)");
+  TORCH_CHECK(window == 0 || causal, "attention: a window needs causal attention");
   a.causal = causal ? 1 : 0;
+  a.window = window < a.N ? (int)window : 0;
   a.klen = nullptr;
   if (!given(key_lengths)) return;
   const Tensor& kl = *key_lengths;
@@ -56,7 +62,7 @@ void attn_masks(tbamd::AttnArgs& a, const Tensor& q, int64_t B, bool causal, con
 
 // -> (o [B, N, H, 64] contiguous, lse [B, H, N] f32)
 std::vector<Tensor> attn_forward(const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool causal,
-                                 const optional<Tensor>& key_lengths) {
+                                 const optional<Tensor>& key_lengths, int64_t window) {
   const at::DeviceGuard guard(q.device());
   const int64_t B = q.size(0), H = q.size(1), N = q.size(2);
   TORCH_CHECK(N >= 1 && B * H * ((N + 127) / 128) < (int64_t)INT32_MAX, "attention: bad size");
@@ -72,7 +78,7 @@ std::vector<Tensor> attn_forward(const Tensor& q, const Tensor& k, const Tensor&
   a.o = const_cast<uint16_t*>(op);
   a.lse = lse.data_ptr<float>();
   a.B = (int)B, a.H = (int)H, a.N = (int)N, a.scale = (float)scale;
-  attn_masks(a, q, B, causal, key_lengths);
+  attn_masks(a, q, B, causal, key_lengths, window);
   tbamd::attn_fwd(a, cur_stream());
   return {o, lse};
 }
@@ -80,7 +86,7 @@ std::vector<Tensor> attn_forward(const Tensor& q, const Tensor& k, const Tensor&
 // writes dq, dk, dv (views, e.g. slices of one packed dqkv buffer)
 void attn_backward(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o, const Tensor& dout,
                    const Tensor& lse, double scale, const Tensor& dq, const Tensor& dk, const Tensor& dv, bool causal,
-                   const optional<Tensor>& key_lengths) {
+                   const optional<Tensor>& key_lengths, int64_t window) {
   const at::DeviceGuard guard(q.device());
   const int64_t B = q.size(0), H = q.size(1), N = q.size(2);
   tbamd::AttnArgs a{};
@@ -102,14 +108,20 @@ void attn_backward(const Tensor& q, const Tensor& k, const Tensor& v, const Tens
   a.lse = lse.data_ptr<float>();
   a.delta = delta.data_ptr<float>();
   a.B = (int)B, a.H = (int)H, a.N = (int)N, a.scale = (float)scale;
-  attn_masks(a, q, B, causal, key_lengths);
+  attn_masks(a, q, B, causal, key_lengths, window);
   tbamd::attn_bwd(a, cur_stream());
 }
 
 // ---- KV-cache decoding (csrc/attention_decode.hip).  Cache: [B, Hkv, cap, 64] bf16 views (checked as
 // attn_view checks q/k/v); lengths / positions: [B] int32 on the same device, read by the kernels.
 // kv_heads (trailing, 0 = heads) is grouped-query attention: it must divide heads, the cache must
-// have that many heads and a packed row is (H + 2*Hkv)*64 wide (bind_common.h).
+// have that many heads and a packed row is (H + 2*Hkv)*64 wide (bind_common.h).  window (trailing, 0 =
+// none): the sliding window of the decode / extend kernels; one that can hide nothing (>= cap) is none.
+int cache_window(int64_t window, int64_t cap, const char* what) {
+  TORCH_CHECK(window >= 0, what, ": window must be >= 1 (0: none)");
+  return window < cap ? (int)window : 0;
+}
+
 const int* decode_lengths(const Tensor& t, const char* name, const Tensor& like, int64_t B) {
   check_cuda(t, name);
   TORCH_CHECK(t.scalar_type() == at::kInt, "attention decode: ", name, " must be int32");
@@ -184,7 +196,7 @@ Tensor decode_args(tbamd::AttnDecodeArgs& a, const Tensor* qkv, int64_t H, int64
 // place -> o [B, H*64].  len = clamp(lengths[b] + add, 1, cap).  workspace (optional, tests): f32,
 // at least attn_decode_workspace floats; by default it comes from the caching allocator.
 Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const Tensor& v_cache, const Tensor& lengths,
-                   int64_t add, double scale, const optional<Tensor>& workspace, int64_t kv_heads) {
+                   int64_t add, double scale, const optional<Tensor>& workspace, int64_t kv_heads, int64_t window) {
   const at::DeviceGuard guard(k_cache.device());
   const int64_t H = heads, Hkv = kv_heads_of(heads, kv_heads, "attention decode");
   const bool packed = q.dim() == 3 && q.size(1) == 1 && q.size(2) == packed_qkv_width(H, Hkv);
@@ -200,6 +212,7 @@ Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const 
   }
   Tensor ws = workspace_or_new(workspace, tbamd::attn_decode_workspace(a.B, a.H, a.cap), k_cache, "attention decode");
   a.ws = ws.data_ptr<float>();
+  a.window = cache_window(window, a.cap, "attention decode");
   tbamd::attn_decode(a, cur_stream());
   return o;
 }
@@ -208,11 +221,12 @@ Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const 
 // cache row positions[b] (dropped outside [0, cap)) and the query sees rows j <= positions[b] ->
 // o [B, H*64].  Same bits, output and caches, as attn_kv_append followed by attn_decode(add = 1).
 Tensor attn_decode_append(const Tensor& qkv, int64_t heads, const Tensor& k_cache, const Tensor& v_cache,
-                          const Tensor& positions, double scale, int64_t kv_heads) {
+                          const Tensor& positions, double scale, int64_t kv_heads, int64_t window) {
   const at::DeviceGuard guard(k_cache.device());
   const int64_t H = heads, Hkv = kv_heads_of(heads, kv_heads, "attention decode");
   tbamd::AttnDecodeArgs a{};
   Tensor o = decode_args(a, &qkv, H, Hkv, k_cache, v_cache, positions, "positions", 1, scale);
+  a.window = cache_window(window, a.cap, "attention decode");
   Tensor ws;  // a single chunk is normalised in the split kernel: no partials
   if (tbamd::attn_decode_chunks(a.cap) > 1) {
     ws = at::empty({tbamd::attn_decode_workspace(a.B, a.H, a.cap)}, k_cache.options().dtype(at::kFloat));
@@ -391,7 +405,7 @@ Tensor rope_packed(const Tensor& qkv, int64_t heads, const Tensor& table, const 
 // workspace (optional, tests): f32, at least attn_extend_workspace floats; by default it comes
 // from the caching allocator (none at all with a single key split).
 Tensor attn_extend(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& positions,
-                   double scale, const optional<Tensor>& workspace, int64_t kv_heads) {
+                   double scale, const optional<Tensor>& workspace, int64_t kv_heads, int64_t window) {
   const at::DeviceGuard guard(k_cache.device());
   TORCH_CHECK(k_cache.dim() == 4, "attention extend: cache must be [B, H, cap, 64]");
   const int64_t B = k_cache.size(0), cap = k_cache.size(2);
@@ -425,6 +439,7 @@ Tensor attn_extend(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache
   a.so[0] = T * H * 64, a.so[1] = H * 64;
   a.ws = need > 0 ? ws.data_ptr<float>() : nullptr;
   a.B = (int)B, a.T = (int)T, a.H = (int)H, a.Hkv = (int)Hkv, a.cap = (int)cap, a.scale = (float)scale;
+  a.window = cache_window(window, cap, "attention extend");
   tbamd::attn_extend(a, cur_stream());
   return o;
 }
@@ -433,17 +448,17 @@ Tensor attn_extend(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache
 
 void register_attn(pybind11::module& m) {
   m.def("attn_forward", &attn_forward, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
-        py::arg("causal") = false, py::arg("key_lengths") = py::none());
+        py::arg("causal") = false, py::arg("key_lengths") = py::none(), py::arg("window") = 0);
   m.def("attn_backward", &attn_backward, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("dout"),
         py::arg("lse"), py::arg("scale"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("causal") = false,
-        py::arg("key_lengths") = py::none());
+        py::arg("key_lengths") = py::none(), py::arg("window") = 0);
   m.def("attn_kv_append", &attn_kv_append, py::arg("qkv"), py::arg("heads"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("positions"), py::arg("kv_heads") = 0);
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("heads"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("lengths"), py::arg("add"), py::arg("scale"), py::arg("workspace") = py::none(),
-        py::arg("kv_heads") = 0);
+        py::arg("kv_heads") = 0, py::arg("window") = 0);
   m.def("attn_decode_append", &attn_decode_append, py::arg("qkv"), py::arg("heads"), py::arg("k_cache"),
-        py::arg("v_cache"), py::arg("positions"), py::arg("scale"), py::arg("kv_heads") = 0);
+        py::arg("v_cache"), py::arg("positions"), py::arg("scale"), py::arg("kv_heads") = 0, py::arg("window") = 0);
   m.def("rows_linear", &rows_linear, py::arg("x"), py::arg("weight"), py::arg("bias") = py::none(),
         py::arg("gamma") = py::none(), py::arg("beta") = py::none(), py::arg("eps") = 0.0, py::arg("epi") = 0,
         py::arg("residual") = py::none(), py::arg("out") = py::none(), py::arg("rms") = false);
@@ -458,7 +473,7 @@ void register_attn(pybind11::module& m) {
         py::arg("positions") = py::none(), py::arg("kv_heads") = 0, py::arg("inverse") = false,
         py::arg("out") = py::none());
   m.def("attn_extend", &attn_extend, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("positions"),
-        py::arg("scale"), py::arg("workspace") = py::none(), py::arg("kv_heads") = 0);
+        py::arg("scale"), py::arg("workspace") = py::none(), py::arg("kv_heads") = 0, py::arg("window") = 0);
   // knobs and workspace sizes
   m.def("attn_set_head_mask", [](int64_t m) { return (int64_t)tbamd::attn_set_head_mask((int)m); });
   m.def("attn_decode_workspace", [](int64_t B, int64_t H, int64_t cap) {
@@ -472,12 +487,13 @@ void register_attn(pybind11::module& m) {
     TORCH_CHECK(n <= 4, "attn_decode_set_head_block: 0 (the default policy) or 1 .. 4");
     return (int64_t)tbamd::attn_decode_set_head_block((int)n);
   });
-  m.def("attn_decode_head_block", [](int64_t B, int64_t H, int64_t kv_heads, int64_t cap) {
+  m.def("attn_decode_head_block", [](int64_t B, int64_t H, int64_t kv_heads, int64_t cap, int64_t window) {
     const int64_t Hkv = kv_heads_of(H, kv_heads, "attn_decode_head_block");
     TORCH_CHECK(B >= 1 && cap >= 1 && B < (int64_t)INT32_MAX && H < (int64_t)INT32_MAX && cap < (int64_t)INT32_MAX / 2,
                 "attn_decode_head_block: bad size");
-    return (int64_t)tbamd::attn_decode_head_block((int)B, (int)H, (int)Hkv, (int)cap);
-  });
+    return (int64_t)tbamd::attn_decode_head_block((int)B, (int)H, (int)Hkv, (int)cap,
+                                                  cache_window(window, cap, "attn_decode_head_block"));
+  }, py::arg("B"), py::arg("H"), py::arg("kv_heads"), py::arg("cap"), py::arg("window") = 0);
   m.def("attn_extend_splits", [](int64_t B, int64_t H, int64_t T, int64_t cap) {
     return (int64_t)tbamd::attn_extend_splits((int)B, (int)H, (int)T, (int)cap);
   });

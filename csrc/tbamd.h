@@ -277,6 +277,9 @@ struct AttnArgs {
   // value never moves an address and no row is fully masked.  nullptr: every key.
   int causal;
   const int* klen;
+  // sliding window (0: none; needs causal): a query whose key limit is hi = min(len, i + 1) sees keys
+  // max(0, hi - window) <= j < hi.  A host value; windowed calls always run the 128-row kernels.
+  int window;
 };
 int attn_supported(int D);
 // whole-head kernel mask (1 forward, 4 dK/dV); mask < 0 only reads it.  Returns the previous mask.
@@ -318,13 +321,16 @@ struct AttnDecodeArgs {
   float scale;
   int64_t sq[2], sk[3], sv[3], so[2];
   int chunk, nchunks, nparts, group, nblk;
+  // sliding window (0: none): rows below max(0, len - window) never enter arithmetic either -- chunks
+  // that end at or below that row write "empty", the chunk it cuts starts there
+  int window;
 };
 // query heads per wave: 0 = the default policy (the largest of 4, 3, 2 that divides G and leaves the
 // grid enough waves, else 1: a function of B, H, Hkv, cap and the chunk size only), otherwise a
 // forced size in 1 .. 4 (used where it divides G, the default policy elsewhere); n < 0 only reads
 // it.  Returns the previous value.
 int attn_decode_set_head_block(int n);
-int attn_decode_head_block(int B, int H, int Hkv, int cap);
+int attn_decode_head_block(int B, int H, int Hkv, int cap, int window = 0);
 // keys per workgroup (a multiple of 8, >= 8); n < 0 only reads it.  Returns the previous value.
 int attn_decode_set_chunk(int n);
 int attn_decode_chunks(int cap);
@@ -417,6 +423,9 @@ struct AttnExtendArgs {
   float scale;
   int64_t sq[3], sk[3], sv[3], so[2];
   int split, nsplit, nqt, nparts, group;
+  // sliding window (0: none): query t sees rows max(0, L(b, t) - window) <= j < L(b, t); rows below
+  // the lower limit of a wave's first query are not loaded
+  int window;
 };
 // keys per split: 0 = the default policy (split only when B * H * ceil(T / 16) cannot occupy the
 // chip), otherwise a forced size (a multiple of 8, >= 8; at or above cap: one split); n < 0 only

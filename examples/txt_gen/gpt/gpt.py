@@ -47,6 +47,7 @@ class Config(BaseConfig):
     pos: str = "learned"  # "rope": rotary position embeddings (models/gpt.py)
     norm: str = "layer"  # "rms": RMSNorm
     mlp: str = "gelu"  # "swiglu": the gated SiLU MLP
+    window: int = 0  # > 0: sliding-window attention, a token sees itself and the window - 1 tokens before it
 
 
 def load_bytes(path: str) -> torch.Tensor:
@@ -61,8 +62,9 @@ def main(conf: Config) -> None:
     data = conf.env.make(load_bytes(conf.text))
     if data.numel() <= conf.seq_len:
         raise ValueError(f"{conf.text or 'README.md'}: {data.numel()} bytes, need more than seq_len = {conf.seq_len}")
-    model = prepare_model(getattr(gpt, conf.arch)(vocab=256, max_len=conf.seq_len, pos=conf.pos, norm=conf.norm, mlp=conf.mlp),
-                          conf, channels_last=False)
+    net = getattr(gpt, conf.arch)(vocab=256, max_len=conf.seq_len, pos=conf.pos, norm=conf.norm, mlp=conf.mlp,
+                                  window=conf.window or None)
+    model = prepare_model(net, conf, channels_last=False)
     net = getattr(model, "module", model)
     optim = conf.optim.make(model.parameters())
     sched = conf.scheduler.make(optim)

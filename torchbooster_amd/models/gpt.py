@@ -57,10 +57,19 @@ drops the biases of ``qkv``, ``proj`` and the MLP linears (``head`` never had on
 ``kv_heads`` that is the Llama / Mistral / Qwen decoder on every path above: the fused step runs the
 RMSNorm as the ``rms=`` prologue and the gate as the ``act="swiglu"`` epilogue of ``linear_rows``, the same
 number of launches per layer.  The defaults (``"layer"``, ``"gelu"``, ``True``) are everything above unchanged.
+
+Sliding-window attention (``TransformerLM(..., window=W)``): a token sees itself and the ``W - 1`` tokens
+before it (ops/attention.py states the rule for pad rows and the cache paths) in every layer, or, with a
+sequence of ``depth`` entries, each ``None`` or an int, per layer -- alternating local / global layers
+(Mistral, Gemma 2 / 3, gpt-oss).  Training skips the key tiles left of the window, a decode step streams
+at most ``W`` cache rows per layer whatever the context, and ``prefill`` / ``decode_step`` / ``extend`` /
+``generate`` (``graph=True``, ``cache=``, ``fused=True``, ``draft=`` -- whose two models may differ in
+``window``) keep their meaning.  A :class:`KVCache` is unchanged: full capacity, rows never recycled.
+``window=None`` (the default) is everything above unchanged.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 from torch import Tensor, nn
@@ -115,10 +124,19 @@ def _sample(logits: Tensor, temperature: float, top_k: Optional[int], generator)
 class TransformerLM(nn.Module):
     def __init__(self, vocab: int, dim: int, depth: int, heads: int, max_len: int, mlp_ratio: float = 4.0,
                  kv_heads: Optional[int] = None, *, pos: str = "learned", rope_base: float = 10000.0,
-                 norm: str = "layer", mlp: str = "gelu", bias: bool = True) -> None:
+                 norm: str = "layer", mlp: str = "gelu", bias: bool = True,
+                 window: Union[None, int, Sequence[Optional[int]]] = None) -> None:
         super().__init__()
         if pos not in ("learned", "rope"):
             raise ValueError(f"pos must be 'learned' or 'rope', not {pos!r}")
+        if window is None or isinstance(window, int):
+            windows = [window] * depth
+        elif isinstance(window, (str, bytes)) or not hasattr(window, "__iter__"):
+            raise ValueError(f"window must be None, an int >= 1 or a sequence of {depth} such entries, not {window!r}")
+        else:
+            windows = list(window)
+            if len(windows) != depth:
+                raise ValueError(f"window has {len(windows)} entries, the model {depth} layers")
         self.max_len = max_len
         self.tok = nn.Embedding(vocab, dim)
         # learned: a [1, max_len, dim] table added to the token embedding; rope: none, the layers rotate q / k
@@ -127,8 +145,9 @@ class TransformerLM(nn.Module):
         kw = {} if self.rope is None else {"rope": self.rope}  # learned: the calls it always made
         if (norm, mlp, bias) != ("layer", "gelu", True):  # likewise the GPT-2 block
             kw.update(norm=norm, mlp=mlp, bias=bias)
-        self.blocks = nn.ModuleList([Block(dim, heads, mlp_ratio, causal=True, kv_heads=kv_heads, **kw)
-                                     for _ in range(depth)])
+        # (no window: the calls it always made)
+        self.blocks = nn.ModuleList([Block(dim, heads, mlp_ratio, causal=True, kv_heads=kv_heads, **kw,
+                                           **({} if w is None else {"window": w})) for w in windows])
         self.norm = make_norm(norm, dim)
         self.head = Linear(dim, vocab, bias=False)
         nn.init.normal_(self.tok.weight, std=0.02)
@@ -448,11 +467,13 @@ class TransformerLM(nn.Module):
 
 
 def gpt_tiny(vocab: int = 256, max_len: int = 128, pos: str = "learned", *, norm: str = "layer", mlp: str = "gelu",
-             bias: bool = True, kv_heads: Optional[int] = None, mlp_ratio: float = 4.0) -> TransformerLM:
-    return TransformerLM(vocab, 128, 2, 2, max_len, mlp_ratio, kv_heads, pos=pos, norm=norm, mlp=mlp, bias=bias)
+             bias: bool = True, kv_heads: Optional[int] = None, mlp_ratio: float = 4.0, window=None) -> TransformerLM:
+    return TransformerLM(vocab, 128, 2, 2, max_len, mlp_ratio, kv_heads, pos=pos, norm=norm, mlp=mlp, bias=bias,
+                         window=window)
 
 
 def gpt2_small(vocab: int = 50257, max_len: int = 1024, pos: str = "learned", *, norm: str = "layer",
                mlp: str = "gelu", bias: bool = True, kv_heads: Optional[int] = None,
-               mlp_ratio: float = 4.0) -> TransformerLM:
-    return TransformerLM(vocab, 768, 12, 12, max_len, mlp_ratio, kv_heads, pos=pos, norm=norm, mlp=mlp, bias=bias)
+               mlp_ratio: float = 4.0, window=None) -> TransformerLM:
+    return TransformerLM(vocab, 768, 12, 12, max_len, mlp_ratio, kv_heads, pos=pos, norm=norm, mlp=mlp, bias=bias,
+                         window=window)

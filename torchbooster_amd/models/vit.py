@@ -112,11 +112,21 @@ class Attention(nn.Module):
     ``rope`` (a :class:`Rope`; ``None``: nothing changes): the q and k parts of the packed projection are
     rotated right behind ``self.qkv`` (``ops.attention.rope_packed``), so every path below reads rotated
     q / k and a cache holds rotated keys.  Token ``t`` is at position ``t`` without a cache and in a
-    prefill, at ``positions[b] + t`` in a decode step and an extend; the cached paths rotate in place."""
+    prefill, at ``positions[b] + t`` in a decode step and an extend; the cached paths rotate in place.
+
+    ``window`` (an int >= 1, needs ``causal``; ``None``: nothing changes): sliding-window attention
+    (ops/attention.py) -- a token sees itself and the ``window - 1`` tokens before it -- passed to every
+    attention call below: training, prefill, decode step (``fused`` or not) and extend."""
 
     def __init__(self, dim: int, heads: int, causal: bool = False, kv_heads: Optional[int] = None,
-                 rope: Optional[Rope] = None, bias: bool = True) -> None:
+                 rope: Optional[Rope] = None, bias: bool = True, window: Optional[int] = None) -> None:
         super().__init__()
+        if window is not None:
+            if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+                raise ValueError(f"window must be None or an int >= 1, not {window!r}")
+            if not causal:
+                raise ValueError("window needs causal attention")
+        self.window = window
         if kv_heads is not None and (kv_heads < 1 or heads % kv_heads):
             raise ValueError(f"kv_heads {kv_heads} must divide heads {heads}")
         self.heads = heads
@@ -129,6 +139,14 @@ class Attention(nn.Module):
         self.qkv = Linear(dim, 3 * dim if kv_heads is None else (heads + 2 * self.kv_heads) * self.hd, bias=bias)
         self.proj = Linear(dim, dim, bias=bias)
 
+    def _kw(self) -> dict:
+        """``kv_heads`` / ``window`` where the layer has them: plain MHA without a window makes the calls it
+        always made."""
+        kw = {} if self.kv_heads == self.heads else {"kv_heads": self.kv_heads}
+        if self.window is not None:
+            kw["window"] = self.window
+        return kw
+
     def rotate(self, qkv: Tensor, positions: Optional[Tensor] = None, inplace: bool = False) -> Tensor:
         """The packed projection with q and k rotated; ``qkv`` itself without ``rope``."""
         if self.rope is None:
@@ -139,7 +157,7 @@ class Attention(nn.Module):
                 positions: Optional[Tensor] = None, extend: bool = False) -> Tensor:
         if cache is not None:
             return self.proj(self.cached(self.qkv(x), cache, positions, key_lengths, extend=extend))
-        kw = {} if self.kv_heads == self.heads else {"kv_heads": self.kv_heads}  # MHA: the calls it always made
+        kw = self._kw()
         return self.proj(attention_packed(self.rotate(self.qkv(x)), self.heads, 1.0 / math.sqrt(self.hd),
                                           causal=self.causal, key_lengths=key_lengths, **kw))
 
@@ -155,7 +173,7 @@ class Attention(nn.Module):
             raise ValueError("a KV cache needs positions")
         k_cache, v_cache = cache
         scale = 1.0 / math.sqrt(self.hd)
-        kw = {} if self.kv_heads == self.heads else {"kv_heads": self.kv_heads}  # MHA: the calls it always made
+        kw = self._kw()
         one = qkv.shape[1] == 1
         # a prefill's tokens sit at 0 .. N - 1 whatever row they are appended at, a step's at positions[b] + t
         qkv = self.rotate(qkv, positions if extend or one else None, inplace=True)
@@ -165,7 +183,8 @@ class Attention(nn.Module):
             return attention_decode_packed(qkv, self.heads, k_cache, v_cache, positions, scale, **kw)
         if extend:
             return attention_extend_packed(qkv, self.heads, k_cache, v_cache, positions, scale, **kw)
-        kv_cache_append(k_cache, v_cache, qkv, self.heads, positions, **kw)
+        kv_cache_append(k_cache, v_cache, qkv, self.heads, positions,
+                        **({} if self.kv_heads == self.heads else {"kv_heads": self.kv_heads}))
         return attention_packed(qkv, self.heads, scale, causal=True, key_lengths=key_lengths, **kw)
 
 
@@ -200,16 +219,16 @@ class Block(nn.Module):
     ``norm="rms"``: ``ln1`` / ``ln2`` are :class:`~torchbooster_amd.ops.norm.RMSNorm` (the attribute names
     stay: the ``(x, pending)`` protocol of ``forward`` is the same); ``mlp="swiglu"``: ``self.mlp`` is a
     :class:`SwiGLU` of hidden width ``int(dim * mlp_ratio)``; ``bias=False``: no bias in ``qkv``, ``proj`` and
-    the MLP's linears -- together the Llama-style block."""
+    the MLP's linears -- together the Llama-style block.  ``window``: the sliding window of :class:`Attention`."""
 
     def __init__(self, dim: int, heads: int, mlp_ratio: float = 4.0, causal: bool = False,
                  kv_heads: Optional[int] = None, rope: Optional[Rope] = None, norm: str = "layer",
-                 mlp: str = "gelu", bias: bool = True) -> None:
+                 mlp: str = "gelu", bias: bool = True, window: Optional[int] = None) -> None:
         super().__init__()
         if mlp not in ("gelu", "swiglu"):
             raise ValueError(f"mlp must be 'gelu' or 'swiglu', not {mlp!r}")
         self.ln1 = make_norm(norm, dim)
-        self.attn = Attention(dim, heads, causal, kv_heads, rope, bias=bias)
+        self.attn = Attention(dim, heads, causal, kv_heads, rope, bias=bias, window=window)
         self.ln2 = make_norm(norm, dim)
         hidden = int(dim * mlp_ratio)
         self.mlp = SwiGLU(dim, hidden, bias) if mlp == "swiglu" else MLP(dim, hidden, bias)

@@ -30,6 +30,25 @@ With both, query ``i`` of batch ``b`` sees keys ``j < min(key_lengths[b], i + 1)
 kernels skip the key tiles no query of a workgroup sees instead of masking them; gradients of
 hidden keys are zeros.
 
+Sliding window (``window=``, a host ``int`` ``W >= 1``, never a device value; ``None``: no window), one
+rule on every path: a row whose upper key limit is ``hi`` sees the keys ``max(0, hi - W) <= j < hi`` --
+the window is counted back from the limit the row already has.  In :func:`attention` /
+:func:`attention_packed` (which need ``causal=True`` for it) ``hi = min(clamp(key_lengths[b], 1, N),
+i + 1)``: a valid token sees itself and the ``W - 1`` tokens before it (``i - W < j <= i``, the Hugging Face
+``sliding_window``), a query at a padded position the last ``W`` valid keys, so still no row is fully
+masked; ``W = 1`` is a row that sees only itself.  In the cache functions below ``hi`` is the limit they
+state (``len`` of a decode, ``L(b, t)`` of an extend).  ``window < 1`` or a non-int raises ``ValueError``.
+A window that can hide nothing -- ``W >= N``, or ``W >= cap`` for the cache functions, decided on the
+host from shapes alone -- IS the call with ``window=None``: the same kernels, the same bits.  Natively a
+windowed training call always runs the three 128-row kernels (a third instantiation, which also skips
+the key tiles left of the window; there is no windowed whole-head kernel and ``attn_set_head_mask`` does
+not apply), a windowed decode streams at most ``W`` rows per (batch, kv head) whatever the length, and a
+windowed extend starts at its first query's lower limit.  Cache rows below ``max(0, hi - W)`` of a decode
+NEVER enter arithmetic (not loaded, probability the constant 0; selected away before the multiply on the
+PyTorch path); in an extend that holds for the rows below the smallest lower limit of a wave's 16
+queries natively and of the call's first query on the PyTorch path, while rows between that bound and a
+query's own lower limit are real, previously appended data that may meet an exact-zero probability.
+
 KV-cache decoding (forward only; csrc/attention_decode.hip).  A cache is, per layer, a ``k_cache`` and
 a ``v_cache`` of ``[B, H, cap, D]`` (``torch.empty`` is fine: see the guarantee below; ``[B, Hkv, cap, D]``
 with ``kv_heads``, see the end of this docstring).
@@ -110,25 +129,52 @@ __all__ = ["attention", "attention_packed", "attention_ref", "native_supported",
            "rope_table", "rope_packed"]
 
 
-def _visible(N: int, device, causal: bool, key_lengths: Optional[Tensor]) -> Optional[Tensor]:
-    """The boolean mask (True = attend) of the two masks, broadcastable to [B, H, N, N]; None = dense."""
-    m = None
+def _window(window, limit: Optional[int] = None) -> Optional[int]:
+    """``window`` checked (``None`` or an int >= 1); ``None`` too when it can hide nothing (``>= limit``)."""
+    if window is None:
+        return None
+    if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+        raise ValueError(f"window must be None or an int >= 1, not {window!r}")
+    return None if limit is not None and window >= limit else window
+
+
+def _visible(N: int, device, causal: bool, key_lengths: Optional[Tensor],
+             window: Optional[int] = None) -> Optional[Tensor]:
+    """The boolean mask (True = attend) of the masks, broadcastable to [B, H, N, N]; None = dense.
+    ``window`` (with ``causal``): keys below ``max(0, hi - window)`` are hidden, ``hi`` the row's limit."""
+    m = kl = None
     if key_lengths is not None:
         kl = key_lengths.to(device=device, dtype=torch.int64).clamp(1, N)  # the kernels' clamp
         m = (torch.arange(N, device=device)[None, :] < kl[:, None])[:, None, None, :]
     if causal:
         c = torch.ones(N, N, dtype=torch.bool, device=device).tril()
         m = c if m is None else m & c
+    if window is not None:
+        i = torch.arange(N, device=device)
+        hi = i + 1 if kl is None else torch.minimum(kl[:, None], (i + 1)[None, :])  # [N] or [B, N]
+        w = i >= (hi - window).clamp_min(0)[..., None]  # [N, N] or [B, N, N]: key j at or past the row's lower limit
+        m = m & (w if kl is None else w[:, None])
     return m
 
 
+def _check_window(window, causal: bool, N: int) -> Optional[int]:
+    """The window of :func:`attention` / :func:`attention_packed`: it needs ``causal``; ``>= N`` is none."""
+    window = _window(window, N)
+    if window is not None and not causal:
+        raise ValueError("window needs causal=True")
+    return window
+
+
 def attention_ref(q: Tensor, k: Tensor, v: Tensor, scale: Optional[float] = None, *, causal: bool = False,
-                  key_lengths: Optional[Tensor] = None) -> Tensor:
+                  key_lengths: Optional[Tensor] = None, window: Optional[int] = None) -> Tensor:
     """softmax(q kᵀ · scale) v over [..., N, D] tensors (f32 softmax); with a mask, over
     [B, H, N, D] (the fp32 oracle of the masked kernels when given fp32 inputs)."""
     scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else scale
+    if window is not None and not causal:
+        _window(window)
+        raise ValueError("window needs causal=True")
     s = torch.matmul(q, k.transpose(-1, -2)) * scale
-    m = _visible(q.shape[-2], q.device, causal, key_lengths)
+    m = _visible(q.shape[-2], q.device, causal, key_lengths, _window(window, q.shape[-2]))
     if m is not None:
         s = s.masked_fill(~m, float("-inf"))
     p = torch.softmax(s.float(), dim=-1).to(q.dtype)
@@ -142,9 +188,10 @@ def _check_lengths(key_lengths: Optional[Tensor], B: int, like: Tensor) -> None:
         raise ValueError("key_lengths must be an int32 tensor of shape [B] on the device of the inputs")
 
 
-def _sdpa(q: Tensor, k: Tensor, v: Tensor, scale: float, causal: bool, key_lengths: Optional[Tensor]) -> Tensor:
+def _sdpa(q: Tensor, k: Tensor, v: Tensor, scale: float, causal: bool, key_lengths: Optional[Tensor],
+          window: Optional[int] = None) -> Tensor:
     """Stock PyTorch (the comparator of --mode stock benchmarks; CPU path), same mask semantics."""
-    m = _visible(q.shape[-2], q.device, causal, key_lengths)
+    m = _visible(q.shape[-2], q.device, causal, key_lengths, window)
     return F.scaled_dot_product_attention(q, k, v, attn_mask=m, scale=scale)
 
 
@@ -156,10 +203,11 @@ class _AttnFn(torch.autograd.Function):
     """q, k, v: [B, H, N, 64] views -> o [B, N, H, 64] (contiguous)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale, causal=False, key_lengths=None):
-        o, lse = native().attn_forward(q, k, v, scale, causal, key_lengths)
+    def forward(ctx, q, k, v, scale, causal=False, key_lengths=None, window=None):
+        kw = {} if window is None else {"window": window}  # no window: the call it always made
+        o, lse = native().attn_forward(q, k, v, scale, causal, key_lengths, **kw)
         ctx.save_for_backward(q, k, v, o, lse, key_lengths)
-        ctx.scale, ctx.causal = scale, causal
+        ctx.scale, ctx.causal, ctx.kw = scale, causal, kw
         return o
 
     @staticmethod
@@ -171,22 +219,23 @@ class _AttnFn(torch.autograd.Function):
         dk = torch.empty(k.shape, dtype=k.dtype, device=k.device)
         dv = torch.empty(v.shape, dtype=v.dtype, device=v.device)
         native().attn_backward(q, k, v, o.permute(0, 2, 1, 3), do.permute(0, 2, 1, 3), lse, ctx.scale, dq, dk, dv,
-                               ctx.causal, key_lengths)
-        return dq, dk, dv, None, None, None
+                               ctx.causal, key_lengths, **ctx.kw)
+        return dq, dk, dv, None, None, None, None
 
 
 class _AttnPackedFn(torch.autograd.Function):
     """qkv: [B, N, 3*H*64] -> [B, N, H*64]; the gradient is one packed buffer."""
 
     @staticmethod
-    def forward(ctx, qkv, heads, scale, causal=False, key_lengths=None):
+    def forward(ctx, qkv, heads, scale, causal=False, key_lengths=None, window=None):
         B, N, E3 = qkv.shape
         D = E3 // (3 * heads)
         t = qkv.view(B, N, 3, heads, D)
         q, k, v = (t[:, :, i].transpose(1, 2) for i in range(3))
-        o, lse = native().attn_forward(q, k, v, scale, causal, key_lengths)
+        kw = {} if window is None else {"window": window}  # no window: the call it always made
+        o, lse = native().attn_forward(q, k, v, scale, causal, key_lengths, **kw)
         ctx.save_for_backward(qkv, o, lse, key_lengths)
-        ctx.cfg = (heads, D, scale, causal)
+        ctx.cfg, ctx.kw = (heads, D, scale, causal), kw
         return o.view(B, N, heads * D)
 
     @staticmethod
@@ -202,8 +251,8 @@ class _AttnPackedFn(torch.autograd.Function):
         native().attn_backward(t[:, :, 0].transpose(1, 2), t[:, :, 1].transpose(1, 2), t[:, :, 2].transpose(1, 2),
                                o.permute(0, 2, 1, 3), do.permute(0, 2, 1, 3), lse, scale,
                                g[:, :, 0].transpose(1, 2), g[:, :, 1].transpose(1, 2), g[:, :, 2].transpose(1, 2),
-                               causal, key_lengths)
-        return dqkv, None, None, None, None
+                               causal, key_lengths, **ctx.kw)
+        return dqkv, None, None, None, None, None
 
 
 def _kv_heads(heads: int, kv_heads: Optional[int]) -> int:
@@ -233,9 +282,10 @@ def _rows(t: Tensor) -> Tensor:
 
 
 def attention(q: Tensor, k: Tensor, v: Tensor, scale: Optional[float] = None, *, causal: bool = False,
-              key_lengths: Optional[Tensor] = None) -> Tensor:
+              key_lengths: Optional[Tensor] = None, window: Optional[int] = None) -> Tensor:
     """[B, H, N, D] -> [B, H, N, D].  ``causal`` / ``key_lengths``: the masks of the module docstring
-    (self-attention: q, k, v of one shape; lengths clamped into [1, N]).
+    (self-attention: q, k, v of one shape; lengths clamped into [1, N]).  ``window`` (needs ``causal``): the
+    sliding window of the module docstring; ``window >= N`` is ``window=None``.
 
     Grouped-query attention: ``k`` / ``v`` may be ``[B, Hkv, N, D]`` with ``Hkv`` dividing ``H``; they are
     expanded to ``H`` heads (one copy) and dK / dV are summed over each group by autograd.  There is no
@@ -244,24 +294,33 @@ def attention(q: Tensor, k: Tensor, v: Tensor, scale: Optional[float] = None, *,
     if q.dim() == 4 and k.dim() == 4 and k.shape == v.shape and k.shape[1] != q.shape[1]:
         G = q.shape[1] // _kv_heads(q.shape[1], k.shape[1])
         k, v = _expand_kv(k, G, 1), _expand_kv(v, G, 1)
+    window = _check_window(window, causal, q.shape[-2])
     if (causal or key_lengths is not None) and not (q.dim() == 4 and q.shape == k.shape == v.shape):
         raise ValueError("attention masks need [B, H, N, D] self-attention inputs of one shape")
     _check_lengths(key_lengths, q.shape[0], q)
     if native_supported(q) and q.dim() == 4 and q.shape == k.shape == v.shape:
         q, k, v = _rows(q), _rows(k), _rows(v)
-        return _AttnFn.apply(q, k, v, scale, bool(causal), key_lengths).permute(0, 2, 1, 3)
-    return _sdpa(q, k, v, scale, causal, key_lengths)
+        if window is None:  # the call it always made
+            return _AttnFn.apply(q, k, v, scale, bool(causal), key_lengths).permute(0, 2, 1, 3)
+        return _AttnFn.apply(q, k, v, scale, True, key_lengths, window).permute(0, 2, 1, 3)
+    if window is None:
+        return _sdpa(q, k, v, scale, causal, key_lengths)
+    return _sdpa(q, k, v, scale, causal, key_lengths, window)
 
 
 def attention_packed(qkv: Tensor, heads: int, scale: Optional[float] = None, *, causal: bool = False,
-                     key_lengths: Optional[Tensor] = None, kv_heads: Optional[int] = None) -> Tensor:
-    """[B, N, 3*H*D] packed q|k|v (head-major inside each) -> [B, N, H*D]; masks as :func:`attention`.
+                     key_lengths: Optional[Tensor] = None, kv_heads: Optional[int] = None,
+                     window: Optional[int] = None) -> Tensor:
+    """[B, N, 3*H*D] packed q|k|v (head-major inside each) -> [B, N, H*D]; masks and ``window`` as
+    :func:`attention`.
 
     ``kv_heads`` (grouped-query attention): ``qkv`` is ``[B, N, (H + 2*Hkv)*D]``.  With ``Hkv < H`` the
     packed tensor is split, k / v are expanded to ``H`` heads (one materialised copy) and
     :func:`attention` runs on that under autograd, which sums dK / dV over each group: a group-aware
     training kernel is out of scope."""
     hkv = _kv_heads(heads, kv_heads)
+    window = _check_window(window, causal, qkv.shape[1])
+    wkw = {} if window is None else {"window": window}  # no window: the calls it always made
     if hkv != heads:
         B, N, E = qkv.shape
         if E % (heads + 2 * hkv):
@@ -270,16 +329,17 @@ def attention_packed(qkv: Tensor, heads: int, scale: Optional[float] = None, *, 
         q = qkv[..., :heads * D].view(B, N, heads, D).transpose(1, 2)
         k, v = (_expand_kv(qkv[..., o * D:(o + hkv) * D].view(B, N, hkv, D), heads // hkv, 2).transpose(1, 2)
                 for o in (heads, heads + hkv))
-        o = attention(q, k, v, 1.0 / math.sqrt(D) if scale is None else scale, causal=causal, key_lengths=key_lengths)
+        o = attention(q, k, v, 1.0 / math.sqrt(D) if scale is None else scale, causal=causal, key_lengths=key_lengths,
+                      **wkw)
         return o.transpose(1, 2).reshape(B, N, heads * D)
     B, N, E3 = qkv.shape
     D = E3 // (3 * heads)
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     _check_lengths(key_lengths, B, qkv)
     if native_supported(qkv.view(B, N, 3, heads, D)) and _rows_ok(qkv):
-        return _AttnPackedFn.apply(qkv, heads, scale, bool(causal), key_lengths)
+        return _AttnPackedFn.apply(qkv, heads, scale, bool(causal), key_lengths, *wkw.values())
     t = qkv.view(B, N, 3, heads, D).permute(2, 0, 3, 1, 4)
-    o = _sdpa(t[0], t[1], t[2], scale, causal, key_lengths)
+    o = _sdpa(t[0], t[1], t[2], scale, causal, key_lengths, *wkw.values())
     return o.transpose(1, 2).reshape(B, N, heads * D)
 
 
@@ -335,13 +395,19 @@ def _append_ref(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, posit
         cache.copy_(torch.where(take, rows, cache))
 
 
-def _decode_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tensor, scale: float) -> Tensor:
+def _decode_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tensor, scale: float,
+                window: Optional[int] = None) -> Tensor:
     """The PyTorch path of :func:`attention_decode` (softmax in fp32, or fp64 for fp64 inputs).  Hidden
-    rows are selected away before either product: a masked score is -inf whatever k held, and v is
-    zeroed there because 0 * NaN is NaN.  A cache of ``Hkv < H`` heads is grouped-query attention."""
+    rows -- at or past the length, and below ``len - window`` -- are selected away before either product:
+    a masked score is -inf whatever k held, and v is zeroed there because 0 * NaN is NaN.  A cache of
+    ``Hkv < H`` heads is grouped-query attention."""
     cap = k_cache.shape[2]
     n = lengths.to(torch.int64).clamp(1, cap)  # the kernels' clamp
-    vis = (torch.arange(cap, device=q.device)[None, :] < n[:, None])[:, None, :]  # [B, 1, cap]
+    j = torch.arange(cap, device=q.device)[None, :]
+    vis = j < n[:, None]
+    if window is not None:
+        vis = vis & (j >= n[:, None] - window)
+    vis = vis[:, None, :]  # [B, 1, cap]
     ct = torch.float64 if q.dtype == torch.float64 else torch.float32
     v = torch.where(vis[..., None], v_cache, torch.zeros((), dtype=v_cache.dtype, device=q.device)).to(ct)
     B, H, D = q.shape
@@ -370,30 +436,43 @@ def kv_cache_append(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, p
         _append_ref(k_cache, v_cache, qkv, heads, positions, hkv)
 
 
+def _cache_window(window, k_cache: Tensor) -> dict:
+    """The ``window`` of a cache function as the trailing keyword of the native calls and of the PyTorch
+    paths: ``{}`` -- the calls they always made -- without one or when it can hide nothing (``>= cap``)."""
+    window = _window(window, k_cache.shape[2] if k_cache.dim() == 4 else None)
+    return {} if window is None else {"window": window}
+
+
 def attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tensor,
-                     scale: Optional[float] = None, *, kv_heads: Optional[int] = None) -> Tensor:
-    """One query per (batch, head): ``q`` ``[B, H, D]`` against the first ``clamp(lengths[b], 1, cap)``
+                     scale: Optional[float] = None, *, kv_heads: Optional[int] = None,
+                     window: Optional[int] = None) -> Tensor:
+    """One query per (batch, head): ``q`` ``[B, H, D]`` against the first ``len = clamp(lengths[b], 1, cap)``
     rows of ``k_cache`` / ``v_cache`` ``[B, Hkv, cap, D]`` -> ``[B, H, D]``.  ``kv_heads``: ``Hkv`` of
-    grouped-query attention (module docstring); ``None`` is ``H``."""
+    grouped-query attention (module docstring); ``None`` is ``H``.  ``window``: only the rows
+    ``max(0, len - window) <= j < len`` (module docstring); ``window >= cap`` is ``window=None``."""
     _forward_only(q, k_cache, v_cache)
     if q.dim() != 3:
         raise RuntimeError("q must be [B, H, D]")
     B, H, D = q.shape
     hkv = _kv_heads(H, kv_heads)
+    wkw = _cache_window(window, k_cache)
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     with torch.no_grad():
         if _decode_native(q, k_cache, v_cache):
-            return native().attn_decode(_rows(q), H, k_cache, v_cache, lengths, 0, scale, None, hkv).view(B, H, D)
+            return native().attn_decode(_rows(q), H, k_cache, v_cache, lengths, 0, scale, None, hkv,
+                                        **wkw).view(B, H, D)
         _check_cache(k_cache, v_cache, B, hkv, D, lengths, "lengths")
-        return _decode_ref(q, k_cache, v_cache, lengths, scale)
+        return _decode_ref(q, k_cache, v_cache, lengths, scale, **wkw)
 
 
 def attention_decode_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
                             scale: Optional[float] = None, *, fused: bool = False,
-                            kv_heads: Optional[int] = None) -> Tensor:
+                            kv_heads: Optional[int] = None, window: Optional[int] = None) -> Tensor:
     """One decode step on the packed ``[B, 1, (H + 2*Hkv)*D]`` projection of the new token: append its k / v
     at row ``positions[b]``, then attend to keys ``j <= positions[b]`` -> ``[B, 1, H*D]``.  ``kv_heads``:
-    ``Hkv`` of grouped-query attention (module docstring); ``None`` is ``H``.
+    ``Hkv`` of grouped-query attention (module docstring); ``None`` is ``H``.  ``window``: as
+    :func:`attention_decode`, with ``len = clamp(positions[b] + 1, 1, cap)``; the appended row is always
+    inside it.
 
     ``fused=True`` (native path): the append is folded into the split kernel -- the wave whose chunk
     holds row ``positions[b]`` takes it from ``qkv`` and stores it to the cache -- and a cache of a single
@@ -401,34 +480,42 @@ def attention_decode_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: T
     have the bits of ``fused=False``."""
     _forward_only(qkv, k_cache, v_cache)
     hkv, B, _, D, scale = _packed_dims(qkv, heads, kv_heads, scale, T="1")
+    wkw = _cache_window(window, k_cache)
     with torch.no_grad():
         if _decode_native(qkv, k_cache, v_cache):
             qkv, C = _rows(qkv), native()
             if fused:
                 return C.attn_decode_append(qkv, heads, k_cache, v_cache, positions, scale,
-                                            hkv).view(B, 1, heads * D)
+                                            hkv, **wkw).view(B, 1, heads * D)
             C.attn_kv_append(qkv, heads, k_cache, v_cache, positions, hkv)
             return C.attn_decode(qkv, heads, k_cache, v_cache, positions, 1, scale, None,
-                                 hkv).view(B, 1, heads * D)
+                                 hkv, **wkw).view(B, 1, heads * D)
         _check_cache(k_cache, v_cache, B, hkv, D, positions, "positions")
         _append_ref(k_cache, v_cache, qkv, heads, positions, hkv)
         q = qkv[:, 0, :heads * D].reshape(B, heads, D)
-        return _decode_ref(q, k_cache, v_cache, positions.to(torch.int64) + 1, scale).reshape(B, 1, heads * D)
+        return _decode_ref(q, k_cache, v_cache, positions.to(torch.int64) + 1, scale,
+                           **wkw).reshape(B, 1, heads * D)
 
 
-def _extend_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor, scale: float) -> Tensor:
+def _extend_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor, scale: float,
+                window: Optional[int] = None) -> Tensor:
     """The PyTorch path of :func:`attention_extend` (softmax in fp32, or fp64 for fp64 inputs), sync-free.
     ``q`` ``[B, T, H, D]`` -> ``[B, T, H, D]``.  Scores are masked to -inf by ``L(b, t)``; v is zeroed at
     rows ``>= clamp(positions[b] + T, 1, cap)`` before the product because 0 * NaN is NaN.  Rows between
     a query's limit and that bound (this call's tokens) are multiplied by an exact-zero probability.
-    A cache of ``Hkv < H`` heads is grouped-query attention."""
+    A cache of ``Hkv < H`` heads is grouped-query attention.  ``window``: scores below ``L(b, t) - window``
+    are masked as well, and v is also zeroed below the first query's lower limit ``L(b, 0) - window``."""
     B, T, H, D = q.shape
     cap = k_cache.shape[2]
     pos = positions.to(torch.int64)
     lim = (pos[:, None] + torch.arange(1, T + 1, device=q.device)[None, :]).clamp(1, cap)  # L(b, t): [B, T]
     j = torch.arange(cap, device=q.device)
-    vis = (j[None, None, :] < lim[:, :, None])[:, None]  # [B, 1, T, cap]
-    held = (j[None, :] < (pos + T).clamp(1, cap)[:, None])[:, None, :, None]  # [B, 1, cap, 1]
+    vis = j[None, None, :] < lim[:, :, None]  # [B, T, cap]
+    held = j[None, :] < (pos + T).clamp(1, cap)[:, None]  # [B, cap]
+    if window is not None:
+        vis = vis & (j[None, None, :] >= lim[:, :, None] - window)
+        held = held & (j[None, :] >= lim[:, :1] - window)
+    vis, held = vis[:, None], held[:, None, :, None]  # [B, 1, T, cap], [B, 1, cap, 1]
     ct = torch.float64 if q.dtype == torch.float64 else torch.float32
     v = torch.where(held, v_cache, torch.zeros((), dtype=v_cache.dtype, device=q.device)).to(ct)
     if k_cache.shape[1] != H:  # query head h reads kv head h // G
@@ -442,7 +529,8 @@ def _extend_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor, 
 
 
 def attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
-                     scale: Optional[float] = None, *, kv_heads: Optional[int] = None) -> Tensor:
+                     scale: Optional[float] = None, *, kv_heads: Optional[int] = None,
+                     window: Optional[int] = None) -> Tensor:
     """``T`` queries per (batch, head): ``q`` ``[B, T, H, D]`` (any view with a contiguous last dim), whose
     k / v rows are already in ``k_cache`` / ``v_cache`` ``[B, Hkv, cap, D]`` at rows ``positions[b] + t``.
     Query ``t`` sees rows ``j < clamp(positions[b] + t + 1, 1, cap)`` -> ``[B, T, H, D]``.  ``kv_heads``:
@@ -450,30 +538,36 @@ def attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Ten
 
     Cache rows at or past ``clamp(positions[b] + T, 1, cap)`` never enter arithmetic; rows between a
     query's own limit and that bound are this call's tokens (real finite data) and may be multiplied by
-    an exact-zero probability."""
+    an exact-zero probability.  ``window``: query ``t`` sees only the rows at or past ``L(b, t) - window``
+    (module docstring, which also says what may enter arithmetic); ``window >= cap`` is ``window=None``."""
     _forward_only(q, k_cache, v_cache)
     if q.dim() != 4 or q.shape[1] < 1:
         raise RuntimeError("q must be [B, T >= 1, H, D]")
     B, T, H, D = q.shape
     hkv = _kv_heads(H, kv_heads)
+    wkw = _cache_window(window, k_cache)
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     with torch.no_grad():
         if _decode_native(q, k_cache, v_cache):
-            return native().attn_extend(_rows(q), k_cache, v_cache, positions, scale, None, hkv).view(B, T, H, D)
+            return native().attn_extend(_rows(q), k_cache, v_cache, positions, scale, None, hkv,
+                                        **wkw).view(B, T, H, D)
         _check_cache(k_cache, v_cache, B, hkv, D, positions, "positions")
-        return _extend_ref(q, k_cache, v_cache, positions, scale)
+        return _extend_ref(q, k_cache, v_cache, positions, scale, **wkw)
 
 
 def attention_extend_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
-                            scale: Optional[float] = None, *, kv_heads: Optional[int] = None) -> Tensor:
+                            scale: Optional[float] = None, *, kv_heads: Optional[int] = None,
+                            window: Optional[int] = None) -> Tensor:
     """``T`` new tokens on their packed ``[B, T, (H + 2*Hkv)*D]`` projection: append their k / v at rows
     ``positions[b] + t`` (rows outside ``[0, cap)`` are dropped), then query ``t`` attends to rows
     ``j < clamp(positions[b] + t + 1, 1, cap)`` -> ``[B, T, H*D]``.  ``T == 1`` is
     :func:`attention_decode_packed`.  What may enter arithmetic: see :func:`attention_extend`.
-    ``kv_heads``: ``Hkv`` of grouped-query attention (module docstring); ``None`` is ``H``."""
+    ``kv_heads``: ``Hkv`` of grouped-query attention (module docstring); ``None`` is ``H``.  ``window``: as
+    :func:`attention_extend` (``T == 1``: the same window in :func:`attention_decode_packed`)."""
     dims = _packed_dims(qkv, heads, kv_heads, scale, T="T >= 1")
+    wkw = _cache_window(window, k_cache)
     if dims[2] == 1:
-        return attention_decode_packed(qkv, heads, k_cache, v_cache, positions, scale, kv_heads=kv_heads)
+        return attention_decode_packed(qkv, heads, k_cache, v_cache, positions, scale, kv_heads=kv_heads, **wkw)
     _forward_only(qkv, k_cache, v_cache)
     hkv, B, T, D, scale = dims
     with torch.no_grad():
@@ -481,11 +575,11 @@ def attention_extend_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: T
             qkv, C = _rows(qkv), native()
             C.attn_kv_append(qkv, heads, k_cache, v_cache, positions, hkv)
             q = qkv[..., :heads * D].view(B, T, heads, D)
-            return C.attn_extend(q, k_cache, v_cache, positions, scale, None, hkv)
+            return C.attn_extend(q, k_cache, v_cache, positions, scale, None, hkv, **wkw)
         _check_cache(k_cache, v_cache, B, hkv, D, positions, "positions")
         _append_ref(k_cache, v_cache, qkv, heads, positions, hkv)
         q = qkv[..., :heads * D].reshape(B, T, heads, D)
-        return _extend_ref(q, k_cache, v_cache, positions, scale).reshape(B, T, heads * D)
+        return _extend_ref(q, k_cache, v_cache, positions, scale, **wkw).reshape(B, T, heads * D)
 
 
 # ---------------------------------------------------------------- rotary position embedding
