@@ -53,6 +53,35 @@
 // still a function of cap.  The merge takes its maximum over all chunks and skips the empty ones
 // wherever they are: the chunk that holds row len - 1 is never empty.  The split kernels are templates
 // on WIN: the <false> instantiations, which every call without a window takes, are the code they were.
+//
+// Rolling cache (AttnDecodeArgs::ring / AttnAppendArgs::ring, host values; needs 1 <= W <= R): the cache
+// is a ring of R = cap slots, logical row j lives in slot j mod R and len = max(klen[b] + add, 1) counts
+// tokens: it is not clamped to R.  Slot p holds logical row j(p), the largest j = p (mod R) below len
+// (csrc/attn_ring.h), and the query sees slot p iff max(0, len - W) <= j(p): the rule above over logical
+// rows.  j(p) < 0 is a slot never written; it is hidden by the same test.  The loops stay over physical
+// slots -- a wave load is still one aligned 1 KiB, the grid a function of R -- and only the per-slot
+// predicate and the chunk's "empty" decision change: a hidden slot is not loaded (its index is replaced
+// by the chunk's first slot before an address is formed) and its probability is the constant 0.  At
+// most R - W slots of a full ring are hidden, so the row loop starts at the chunk's start; a chunk with
+// no visible slot writes "empty" (possible once R - W >= chunk), and the chunk of slot (len - 1) mod R is
+// never empty, which is all the merge needs.  A row group may meet hidden slots anywhere in its walk,
+// not only first: the m = -inf guard below is what covers it (mn = m, alpha = 1 or the constant 0, p = 0).
+// The fused append takes the step's row from qkv in every wave that meets slot positions[b] mod R, which
+// IS the newest row's slot, and the group's first head block stores it there.
+//
+// Why a ring is safe where the linear cache relied on "rows past the position are never read": an extend
+// appends its T rows before its first query reads, and the host requires T <= R - W + 1.  The row written
+// for token T - 1 replaces logical row pos + T - 1 - R <= pos - W, below the first query's lower limit
+// pos + 1 - W, and later queries only look further right.  The same inequality covers rows past the
+// position -- the pad tokens of a ragged extend, the rejected rows of a speculative round: such a stale
+// slot is read as logical row pos + t - R, which no later query can see, until the sequence overwrites it.
+//
+// attn_kv_append_k<true> stores token t to slot (pos[b] + t) mod R iff pos[b] + t >= 0 and n_b - R <= t <
+// n_b, n_b = clamp(len[b], 1, T) (T without len): the last R valid rows of a long prefill, no pad rows,
+// and -- R consecutive t -- at most one store per slot per launch, so there is no write race.  A negative
+// position still never becomes an address.  RING is a template parameter next to WIN: every call without
+// `ring` takes the instantiations that existed before.
+#include "attn_ring.h"
 #include "common.h"
 #include "tbamd.h"
 
@@ -83,6 +112,7 @@ __device__ __forceinline__ int decode_len(const int* klen, int b, int add, int c
   return (int)(l < 1 ? 1 : (l > cap ? cap : l));
 }
 
+template <bool RING>
 __global__ __launch_bounds__(256) void attn_kv_append_k(AttnAppendArgs a) {
   // one lane per 16 B: (b, t, k|v, h, c)
   const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -96,8 +126,15 @@ __global__ __launch_bounds__(256) void attn_kv_append_k(AttnAppendArgs a) {
   r >>= 1;
   const int t = (int)(r % a.T);
   const int b = (int)(r / a.T);
-  const int64_t row = (int64_t)a.pos[b] + t;
-  if (row < 0 || row >= a.cap) return;  // dropped: a bad position never moves an address
+  int64_t row = (int64_t)a.pos[b] + t;
+  if constexpr (RING) {
+    int n = a.T;
+    if (a.len != nullptr) n = min(max(a.len[b], 1), a.T);
+    if (row < 0 || t >= n || t < n - a.cap) return;  // pad rows, and all but the last cap valid rows
+    row = (int64_t)((uint32_t)row % (uint32_t)a.cap);  // 0 <= row < 2^32
+  } else if (row < 0 || row >= a.cap) {
+    return;  // dropped: a bad position never moves an address
+  }
   const uint16_t* src = a.qkv + b * a.sqkv[0] + t * a.sqkv[1] + (int64_t)(a.H + which * a.Hkv) * 64 + h * 64 + c * 8;
   uint16_t* dst = which ? a.vc + b * a.sv[0] + h * a.sv[1] + row * a.sv[2] + c * 8
                         : a.kc + b * a.sk[0] + h * a.sk[1] + row * a.sk[2] + c * 8;
@@ -120,7 +157,7 @@ struct AttnNewRow {
 // to the cache: exactly one store per row, and no wave reads that cache row.  p outside [0, cap)
 // equals no visible row index: nothing is stored.  With one chunk the wave finishes each head with
 // the merge kernel's own arithmetic (M - M, fma by exp2 of it, divide) and writes bf16.
-template <bool FUSED, int GB, bool WIN>
+template <bool FUSED, int GB, bool WIN, bool RING>
 __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, const AttnNewRow& n) {
   const int lane = threadIdx.x;
   const int g = lane >> 3, c = lane & 7;
@@ -131,12 +168,22 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
   const int hk = bh % a.Hkv, b = bh / a.Hkv;
   const int h0 = hk * a.group + hb * GB;
   const int part0 = (b * a.H + h0) * a.nchunks + ck;  // head h0 + j: part0 + j * nchunks
-  const int len = decode_len(a.klen, b, a.add, a.cap);
+  // RING: len is the ring's size, the bound of the slots; the length itself is n below
+  const int len = RING ? a.cap : decode_len(a.klen, b, a.add, a.cap);
   const int start = ck * a.chunk;
   float* wm = a.ws + (int64_t)a.nparts * 64;
   float* wl = wm + a.nparts;
-  const int lo = WIN ? max(len - a.window, 0) : 0;  // the first visible row (< len)
-  if (start >= len || (WIN && start + a.chunk <= lo)) {  // wave-uniform
+  const int lo = WIN && !RING ? max(len - a.window, 0) : 0;  // the first visible row (< len)
+  // RING: n = the unclamped length, pm = the slot of logical row n - 1, wv = how many rows the query
+  // sees; slot r is visible iff ring_back(pm, r, cap) < wv, and a chunk none of whose slots is is empty
+  int pm = 0, wv = 0;
+  if constexpr (RING) {
+    const int64_t n = max((int64_t)a.klen[b] + a.add, (int64_t)1);
+    pm = ring_newest(n, a.cap);
+    wv = (int)min((int64_t)a.window, n);
+  }
+  if (RING ? !ring_any(pm, 0, wv, start, min(start + a.chunk, len), len)
+           : (start >= len || (WIN && start + a.chunk <= lo))) {  // wave-uniform
     if (lane < GB) {
       wm[part0 + lane * a.nchunks] = -INFINITY;
       wl[part0 + lane * a.nchunks] = 0.f;
@@ -145,8 +192,9 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
   }
   const int end = min(start + a.chunk, len);
   // the chunk's first visible row (lo < len and lo < start + chunk: < end), and the 8-row group it is in
-  const int vis = WIN ? max(start, lo) : start;
-  const int first = WIN ? max(start, lo & ~7) : start;
+  // (RING: the chunk's start -- a slot of the tensor, which is all a replaced index has to be)
+  const int vis = WIN && !RING ? max(start, lo) : start;
+  const int first = WIN && !RING ? max(start, lo & ~7) : start;
 
   float q[GB][8];
 #pragma unroll
@@ -155,7 +203,8 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
   const float sc = a.scale * kLog2e;
   const uint16_t* kb = a.k + b * a.sk[0] + hk * a.sk[1] + c * 8;
   const uint16_t* vb = a.v + b * a.sv[0] + hk * a.sv[1] + c * 8;
-  const int64_t p = FUSED ? (int64_t)a.klen[b] : -1;
+  // RING: the step's row is logical row klen[b] = n - 1 when that is >= 0: slot pm; -1 meets no slot
+  const int64_t p = FUSED ? (RING ? ((int64_t)a.klen[b] >= 0 ? (int64_t)pm : -1) : (int64_t)a.klen[b]) : -1;
 
   float m[GB], l[GB], acc[GB][8];
 #pragma unroll
@@ -171,7 +220,8 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
 #pragma unroll
     for (int u = 0; u < kUnroll; ++u) {
       const int r = r0 + 8 * u;
-      ok[u] = r < end && (!WIN || r >= lo);
+      if constexpr (RING) ok[u] = r < end && ring_back(pm, r, len) < wv;
+      else ok[u] = r < end && (!WIN || r >= lo);
       const int rr = ok[u] ? r : vis;  // a hidden row never forms an address
       kr[u] = make_uint4(0, 0, 0, 0);
       vr[u] = make_uint4(0, 0, 0, 0);
@@ -208,7 +258,9 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
     }
     // r0 < end: row u = 0 is visible, so mn is finite from here on -- except in a row group's first
     // pass over the chunk a window cuts, where r0 may lie below lo: if none of its rows is visible,
-    // mn = m = -inf, alpha is the constant 0 and no p is exp2 of anything
+    // mn = m = -inf, alpha is the constant 0 and no p is exp2 of anything.  In a ring a pass may be all
+    // hidden anywhere in the walk: before the first visible slot it is that case, after it mn = m is
+    // finite, alpha is exp2(0) and every p the constant 0
 #pragma unroll
     for (int j = 0; j < GB; ++j) {
       const float alpha = m[j] == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(m[j] - mn[j]);
@@ -273,14 +325,14 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
   }
 }
 
-template <int GB, bool WIN>
+template <int GB, bool WIN, bool RING = false>
 __global__ __launch_bounds__(64) void attn_decode_split_k(AttnDecodeArgs a) {
-  attn_decode_split_body<false, GB, WIN>(a, AttnNewRow{nullptr, nullptr, 0});
+  attn_decode_split_body<false, GB, WIN, RING>(a, AttnNewRow{nullptr, nullptr, 0});
 }
 
-template <int GB, bool WIN>
+template <int GB, bool WIN, bool RING = false>
 __global__ __launch_bounds__(64) void attn_decode_append_split_k(AttnDecodeArgs a, AttnNewRow n) {
-  attn_decode_split_body<true, GB, WIN>(a, n);
+  attn_decode_split_body<true, GB, WIN, RING>(a, n);
 }
 
 // grid: B * H one-wave workgroups; lane = output dim
@@ -331,7 +383,9 @@ int64_t attn_decode_workspace(int B, int H, int cap) { return (int64_t)B * H * a
 void attn_kv_append(const AttnAppendArgs& a, hipStream_t st) {
   const int64_t total = (int64_t)a.B * a.T * 2 * a.Hkv * 8;
   if (total == 0) return;
-  hipLaunchKernelGGL(attn_kv_append_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (a.ring) hipLaunchKernelGGL(attn_kv_append_k<true>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(attn_kv_append_k<false>, grid, dim3(256), 0, st, a);
 }
 
 // Query heads per wave.  A head block of GB loads a K / V row G / GB times instead of G times, and
@@ -354,7 +408,8 @@ int attn_decode_set_head_block(int n) {
   return old;
 }
 
-int attn_decode_head_block(int B, int H, int Hkv, int cap, int window) {
+int attn_decode_head_block(int B, int H, int Hkv, int cap, int window, int ring) {
+  if (ring) window = 0;  // a ring is cap live rows: any chunk may hold visible slots
   const int G = H / Hkv;
   if (g_decode_head_block && G % g_decode_head_block == 0) return g_decode_head_block;
   // the waves that stream rows: under a window the other chunks write "empty" and exit
@@ -372,29 +427,29 @@ static int decode_plan(AttnDecodeArgs& a) {
   a.nchunks = attn_decode_chunks(a.cap);
   a.nparts = a.B * a.H * a.nchunks;
   a.group = a.H / a.Hkv;
-  const int gb = attn_decode_head_block(a.B, a.H, a.Hkv, a.cap, a.window);
+  const int gb = attn_decode_head_block(a.B, a.H, a.Hkv, a.cap, a.window, a.ring);
   a.nblk = a.group / gb;
   return gb;
 }
 
-// the split launch for head block gb; WIN: the windowed instantiations
-template <bool WIN>
+// the split launch for head block gb; WIN: the windowed instantiations, RING: the rolling ones
+template <bool WIN, bool RING = false>
 static void launch_split(int gb, dim3 grid, const AttnDecodeArgs& a, hipStream_t st) {
   switch (gb) {
-    case 1: hipLaunchKernelGGL((attn_decode_split_k<1, WIN>), grid, dim3(64), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((attn_decode_split_k<2, WIN>), grid, dim3(64), 0, st, a); break;
-    case 3: hipLaunchKernelGGL((attn_decode_split_k<3, WIN>), grid, dim3(64), 0, st, a); break;
-    default: hipLaunchKernelGGL((attn_decode_split_k<4, WIN>), grid, dim3(64), 0, st, a); break;
+    case 1: hipLaunchKernelGGL((attn_decode_split_k<1, WIN, RING>), grid, dim3(64), 0, st, a); break;
+    case 2: hipLaunchKernelGGL((attn_decode_split_k<2, WIN, RING>), grid, dim3(64), 0, st, a); break;
+    case 3: hipLaunchKernelGGL((attn_decode_split_k<3, WIN, RING>), grid, dim3(64), 0, st, a); break;
+    default: hipLaunchKernelGGL((attn_decode_split_k<4, WIN, RING>), grid, dim3(64), 0, st, a); break;
   }
 }
 
-template <bool WIN>
+template <bool WIN, bool RING = false>
 static void launch_append_split(int gb, dim3 grid, const AttnDecodeArgs& a, const AttnNewRow& n, hipStream_t st) {
   switch (gb) {
-    case 1: hipLaunchKernelGGL((attn_decode_append_split_k<1, WIN>), grid, dim3(64), 0, st, a, n); break;
-    case 2: hipLaunchKernelGGL((attn_decode_append_split_k<2, WIN>), grid, dim3(64), 0, st, a, n); break;
-    case 3: hipLaunchKernelGGL((attn_decode_append_split_k<3, WIN>), grid, dim3(64), 0, st, a, n); break;
-    default: hipLaunchKernelGGL((attn_decode_append_split_k<4, WIN>), grid, dim3(64), 0, st, a, n); break;
+    case 1: hipLaunchKernelGGL((attn_decode_append_split_k<1, WIN, RING>), grid, dim3(64), 0, st, a, n); break;
+    case 2: hipLaunchKernelGGL((attn_decode_append_split_k<2, WIN, RING>), grid, dim3(64), 0, st, a, n); break;
+    case 3: hipLaunchKernelGGL((attn_decode_append_split_k<3, WIN, RING>), grid, dim3(64), 0, st, a, n); break;
+    default: hipLaunchKernelGGL((attn_decode_append_split_k<4, WIN, RING>), grid, dim3(64), 0, st, a, n); break;
   }
 }
 
@@ -402,7 +457,8 @@ void attn_decode(const AttnDecodeArgs& a_, hipStream_t st) {
   AttnDecodeArgs a = a_;
   const int gb = decode_plan(a);
   const dim3 grid(a.nparts / gb);  // B * Hkv * nblk * nchunks
-  if (a.window > 0) launch_split<true>(gb, grid, a, st);
+  if (a.ring) launch_split<true, true>(gb, grid, a, st);
+  else if (a.window > 0) launch_split<true>(gb, grid, a, st);
   else launch_split<false>(gb, grid, a, st);
   hipLaunchKernelGGL(attn_decode_merge_k, dim3(a.B * a.H), dim3(64), 0, st, a);
 }
@@ -414,7 +470,8 @@ void attn_decode_append(const AttnDecodeArgs& a_, const uint16_t* nk, const uint
   const int gb = decode_plan(a);
   const dim3 grid(a.nparts / gb);
   const AttnNewRow n{nk, nv, snew};
-  if (a.window > 0) launch_append_split<true>(gb, grid, a, n, st);
+  if (a.ring) launch_append_split<true, true>(gb, grid, a, n, st);
+  else if (a.window > 0) launch_append_split<true>(gb, grid, a, n, st);
   else launch_append_split<false>(gb, grid, a, n, st);
   if (a.nchunks > 1) hipLaunchKernelGGL(attn_decode_merge_k, dim3(a.B * a.H), dim3(64), 0, st, a);
 }

@@ -64,6 +64,34 @@
 // non-empty split need not be split 0 -- the merge takes its maximum over all splits, and the split
 // that holds row L(b, t) - 1 is never empty for query t.  The split kernel is a template on WIN: the
 // <false> instantiation, which every call without a window takes, is the code it was.
+//
+// Rolling cache (AttnExtendArgs::ring, a host value; needs 1 <= W <= R = cap and T <= R - W + 1): the
+// cache is a ring, logical row j lives in slot j mod R, L(b, t) = max(pos[b] + t + 1, 1) is not clamped
+// to R, and for the whole call slot p holds logical row j(p), the largest j = p (mod R) below n =
+// L(b, T - 1).  Query t sees slot p iff max(0, L(b, t) - W) <= j(p) < L(b, t) -- the rule above over
+// logical rows -- which the kernel tests on the distance d(p) = n - 1 - j(p) (csrc/attn_ring.h): n -
+// L(b, t) <= d(p) < min(n, n - L(b, t) + W).  T - 1 + W <= R keeps these bounds inside one turn of the ring.
+// The loops stay over physical slots (splits and 64-slot tiles of [0, R), from the split's start: a
+// full ring hides at most R - W slots); the tile's lo / hi become the logical bounds of its 16 queries
+// as distances, dlo from the last query's upper limit and dhi from the first query's lower one, and a
+// slot outside them is treated exactly as a row outside [lo, hi) is: zero K fragment, index replaced
+// before an address is formed, zero-row V staging.  That covers the slots never written (j(p) < 0 is
+// d(p) >= n) and the stale ones.  A slot inside the tile's bounds and outside a query's own holds a
+// logical row in [max(0, L(b, q0) - W), L(b, tile's last query)): real appended data, masked to -inf,
+// an exact-zero probability in the MFMA.  In SLOT space the tile's set, and each query's, is a cyclic
+// interval: up to two intervals of [0, R).  So "visibility is a prefix / an interval of the split" does
+// not hold here and nothing below relies on it: a split is empty iff neither interval meets it
+// (ring_any); inside a live split a row may see nothing in a tile before or after one in which it sees
+// keys, and the ms guard covers both orders (m = -inf: alpha is exp2(-inf - 0) = 0 on zero acc and l; m
+// finite and the tile hidden: mn = m, alpha = 1, every p = 0); a row that sees nothing in the whole split
+// keeps m = -inf and is skipped by the merge, which takes its maximum over all splits.  The split of
+// slot (L(b, t) - 1) mod R is never empty for query t.
+//
+// Why the ring is safe: the call's T rows are appended before its first query reads, and T <= R - W + 1
+// means the row of token T - 1 replaced logical row pos + T - 1 - R <= pos - W, below the first query's
+// lower limit pos + 1 - W.  Rows past the position (pad tokens of a ragged extend, rejected rows of a
+// speculative round) are read as logical row pos + t - R by the same inequality: no later query sees it.
+#include "attn_ring.h"
 #include "common.h"
 #include "mfma_tile.h"
 #include "tbamd.h"
@@ -122,8 +150,48 @@ __device__ __forceinline__ void stage_v(uint4* tile, const uint16_t* vb, int64_t
     }
 }
 
+// What a wave of the rolling cache knows about its slots (csrc/attn_ring.h): slot p, start <= p < hi
+// (hi <= R), is loaded iff dlo <= d(p) < dhi, the union of its 16 queries' windows.
+struct RingTile {
+  int pm, dlo, dhi, R, start, hi;
+  __device__ __forceinline__ bool loads(int p) const {
+    const int d = ring_back(pm, p, R);
+    return p < hi && d >= dlo && d < dhi;
+  }
+};
+
+// load_k / stage_v of a ring: the same fragments and the same LDS tile, the per-slot test of RingTile
+__device__ __forceinline__ void load_k_ring(bf16x8_t (&kf)[4][2], const uint16_t* kb, int64_t rs, int k0,
+                                            const RingTile& rt, int fr, int fg) {
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) {
+    const int r = k0 + 16 * mt + fr;
+    const bool ok = rt.loads(r);
+    const int rr = ok ? r : rt.start;  // a hidden slot never forms an address
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      kf[mt][ks] = bf16x8_t{};
+      if (ok) kf[mt][ks] = ld_frag(kb + rr * rs + 32 * ks + 8 * fg);
+    }
+  }
+}
+
+__device__ __forceinline__ void stage_v_ring(uint4* tile, const uint16_t* vb, int64_t rs, int k0, const RingTile& rt,
+                                             int lane) {
+#pragma unroll
+  for (int w = 0; w < 4; ++w)
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int row = 32 * it + w * 8 + (lane >> 3);
+      const int r = k0 + row;
+      const int ch = (lane & 7) ^ aswz(row);
+      const void* src = rt.loads(r) ? (const void*)(vb + (int64_t)r * rs + ch * 8) : (const void*)g_tile_zero;
+      glds16(src, tile + (32 * it + w * 8) * 8);
+    }
+}
+
 // grid: B * H * nqt * nsplit one-wave workgroups, split fastest
-template <bool WIN>
+template <bool WIN, bool RING = false>
 __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
   __shared__ __attribute__((aligned(16))) uint4 lds[2 * kTileU4];  // V, double buffered: 16 KiB
   const int lane = threadIdx.x;
@@ -137,13 +205,28 @@ __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
   const int q0 = qt * kQT;
   const int start = sp * a.split;  // host: nsplit * split < 2^31
   // the tile's largest limit (L grows with t) cut to the split: workgroup-uniform
-  const int hi = min(extend_len(a.pos, b, min(q0 + kQT, a.T) - 1, a.cap), start + a.split);
+  // RING: hi is the split's end in SLOTS, lo its start; what is visible is decided per slot from the
+  // distances of RingTile, whose bounds are the tile's logical limits: dlo from its last query's upper
+  // limit, dhi from its first query's lower limit (both monotone in t)
+  RingTile rt{};
+  int64_t rn = 0;  // L(b, T - 1), unclamped
+  if constexpr (RING) {
+    rn = max((int64_t)a.pos[b] + a.T, (int64_t)1);
+    const int64_t l0 = max((int64_t)a.pos[b] + q0 + 1, (int64_t)1);
+    const int64_t l1 = max((int64_t)a.pos[b] + min(q0 + kQT, a.T), (int64_t)1);
+    rt.pm = ring_newest(rn, a.cap), rt.R = a.cap, rt.start = start, rt.hi = min(start + a.split, a.cap);
+    rt.dlo = (int)(rn - l1), rt.dhi = (int)min(rn, rn - l0 + a.window);  // 0 <= dlo < dhi <= T - 1 + W <= R
+  }
+  const int hi = RING ? rt.hi : min(extend_len(a.pos, b, min(q0 + kQT, a.T) - 1, a.cap), start + a.split);
   float* wm = a.ws + (int64_t)a.nparts * (kQT * 64);
   float* wl = wm + (int64_t)a.nparts * kQT;
   // the tile's smallest lower limit (its first query's) raised to the split: workgroup-uniform, < hi
   // in a live split
-  const int lo = WIN ? max(start, extend_len(a.pos, b, q0, a.cap) - a.window) : start;
-  if (start >= hi || (WIN && lo >= hi)) {
+  const int lo = WIN && !RING ? max(start, extend_len(a.pos, b, q0, a.cap) - a.window) : start;
+  bool empty;  // workgroup-uniform
+  if constexpr (RING) empty = !ring_any(rt.pm, rt.dlo, rt.dhi, start, hi, a.cap);
+  else empty = start >= hi || (WIN && lo >= hi);
+  if (empty) {
     if (lane < kQT) {
       wm[(int64_t)part * kQT + lane] = -INFINITY;
       wl[(int64_t)part * kQT + lane] = 0.f;
@@ -152,9 +235,18 @@ __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
   }
   const int qi = q0 + fr;
   const bool qreal = qi < a.T;
-  const int lim = min(extend_len(a.pos, b, qreal ? qi : a.T - 1, a.cap), hi);  // the lane's own query
-  // its lower limit (0 without a window): keys below it are masked
-  const int low = WIN ? extend_len(a.pos, b, qreal ? qi : a.T - 1, a.cap) - a.window : 0;
+  // the lane's own query; RING: in distances -- it sees the slots with lim <= d(p) < low (lim from its
+  // upper limit L, low from its lower one: the names keep their roles, the order flips with the distance)
+  int lim, low;
+  if constexpr (RING) {
+    const int64_t lq = max((int64_t)a.pos[b] + (qreal ? qi : a.T - 1) + 1, (int64_t)1);
+    lim = (int)(rn - lq);
+    low = (int)min(rn, rn - lq + a.window);
+  } else {
+    lim = min(extend_len(a.pos, b, qreal ? qi : a.T - 1, a.cap), hi);
+    // its lower limit (0 without a window): keys below it are masked
+    low = WIN ? extend_len(a.pos, b, qreal ? qi : a.T - 1, a.cap) - a.window : 0;
+  }
 
   // Qᵀ as the B operand: lane holds Q[q0 + fr][32 ks + 8 fg .. + 7]
   bf16x8_t qf[2];
@@ -175,9 +267,15 @@ __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
 
   bf16x8_t kn[4][2];
   // tiles run from the 64-row tile of the split that holds lo (start itself without a window)
-  const int kbeg = WIN ? start + (lo - start) / kTile * kTile : start;
-  load_k<WIN>(kn, kb, a.sk[2], kbeg, lo, hi, fr, fg);
-  stage_v<WIN>(lds, vb, a.sv[2], kbeg, lo, hi, lane);
+  // (a ring hides at most R - W slots: its tiles run from the split's start)
+  const int kbeg = WIN && !RING ? start + (lo - start) / kTile * kTile : start;
+  if constexpr (RING) {
+    load_k_ring(kn, kb, a.sk[2], kbeg, rt, fr, fg);
+    stage_v_ring(lds, vb, a.sv[2], kbeg, rt, lane);
+  } else {
+    load_k<WIN>(kn, kb, a.sk[2], kbeg, lo, hi, fr, fg);
+    stage_v<WIN>(lds, vb, a.sv[2], kbeg, lo, hi, lane);
+  }
   int buf = 0;
   for (int k0 = kbeg; k0 < hi; k0 += kTile, buf ^= 1) {
     wait_loads();
@@ -188,8 +286,13 @@ __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) kf[mt][ks] = kn[mt][ks];
     if (k0 + kTile < hi) {
-      load_k<WIN>(kn, kb, a.sk[2], k0 + kTile, lo, hi, fr, fg);
-      stage_v<WIN>(lds + (buf ^ 1) * kTileU4, vb, a.sv[2], k0 + kTile, lo, hi, lane);
+      if constexpr (RING) {
+        load_k_ring(kn, kb, a.sk[2], k0 + kTile, rt, fr, fg);
+        stage_v_ring(lds + (buf ^ 1) * kTileU4, vb, a.sv[2], k0 + kTile, rt, lane);
+      } else {
+        load_k<WIN>(kn, kb, a.sk[2], k0 + kTile, lo, hi, fr, fg);
+        stage_v<WIN>(lds + (buf ^ 1) * kTileU4, vb, a.sv[2], k0 + kTile, lo, hi, lane);
+      }
     }
     const uint4* Vt = lds + buf * kTileU4;
 
@@ -209,14 +312,23 @@ __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int key = key0 + 16 * mt + i;
-        s[mt][i] = key < lim && (!WIN || key >= low) ? s[mt][i] * c : -INFINITY;
+        bool see;
+        if constexpr (RING) {
+          const int d = ring_back(rt.pm, key, rt.R);
+          see = key < hi && d >= lim && d < low;
+        } else {
+          see = key < lim && (!WIN || key >= low);
+        }
+        s[mt][i] = see ? s[mt][i] * c : -INFINITY;
         mx = fmaxf(mx, s[mt][i]);
       }
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
     const float mn = fmaxf(m, mx);
     // a row that has seen no key yet (mn = -inf) must not form -inf - -inf (under a window that is
-    // any row whose lower limit lies past this tile, not only one that sees nothing in the split)
+    // any row whose lower limit lies past this tile, not only one that sees nothing in the split; in a
+    // ring, any row whose up to two slot intervals both lie past this tile).  A tile in which a row
+    // sees nothing AFTER it has seen a key has mn = m finite: alpha = exp2(0), every p = exp2(-inf) = 0
     const float ms = mn == -INFINITY ? 0.f : mn;
     const float alpha = __builtin_amdgcn_exp2f(m - ms);  // m = -inf: 0, and acc, l are 0 anyway
     m = mn;
@@ -345,8 +457,9 @@ void attn_extend(const AttnExtendArgs& a_, hipStream_t st) {
   a.nqt = (a.T + kQT - 1) / kQT;
   a.nparts = a.B * a.H * a.nqt * a.nsplit;
   a.group = a.H / a.Hkv;
-  hipLaunchKernelGGL(a.window > 0 ? attn_extend_split_k<true> : attn_extend_split_k<false>, dim3(a.nparts), dim3(64), 0,
-                     st, a);
+  auto* split = a.ring ? attn_extend_split_k<true, true>
+                       : (a.window > 0 ? attn_extend_split_k<true> : attn_extend_split_k<false>);
+  hipLaunchKernelGGL(split, dim3(a.nparts), dim3(64), 0, st, a);
   if (a.nsplit > 1) hipLaunchKernelGGL(attn_extend_merge_k, dim3(a.B * a.T * a.H), dim3(64), 0, st, a);
 }
 

@@ -117,6 +117,8 @@ void attn_backward(const Tensor& q, const Tensor& k, const Tensor& v, const Tens
 // kv_heads (trailing, 0 = heads) is grouped-query attention: it must divide heads, the cache must
 // have that many heads and a packed row is (H + 2*Hkv)*64 wide (bind_common.h).  window (trailing, 0 =
 // none): the sliding window of the decode / extend kernels; one that can hide nothing (>= cap) is none.
+// rolling (trailing, false = the linear cache): the cache is a ring (bind_common.h ring_window): the window
+// is required, kept as given, and lengths / positions are not clamped to the cache's rows.
 int cache_window(int64_t window, int64_t cap, const char* what) {
   TORCH_CHECK(window >= 0, what, ": window must be >= 1 (0: none)");
   return window < cap ? (int)window : 0;
@@ -143,8 +145,9 @@ const uint16_t* packed_qkv(const Tensor& t, int64_t B, int64_t H, int64_t Hkv, c
 }
 
 void attn_kv_append(const Tensor& qkv, int64_t heads, const Tensor& k_cache, const Tensor& v_cache,
-                    const Tensor& positions, int64_t kv_heads) {
+                    const Tensor& positions, int64_t kv_heads, bool rolling, const optional<Tensor>& lengths) {
   const at::DeviceGuard guard(k_cache.device());
+  TORCH_CHECK(rolling || !given(lengths), "attention decode: append lengths need a rolling cache");
   const int64_t Hkv = kv_heads_of(heads, kv_heads, "attention decode");
   check_kv_cache(k_cache, Hkv, "attention decode");
   const int64_t B = k_cache.size(0), H = heads, cap = k_cache.size(2);
@@ -162,6 +165,9 @@ void attn_kv_append(const Tensor& qkv, int64_t heads, const Tensor& k_cache, con
   TORCH_CHECK(v_cache.device() == k_cache.device(), "attention decode: caches on different devices");
   a.pos = decode_lengths(positions, "positions", k_cache, B);
   a.B = (int)B, a.T = (int)T, a.H = (int)H, a.Hkv = (int)Hkv, a.cap = (int)cap;
+  a.ring = rolling ? 1 : 0;
+  if (given(lengths)) a.len = decode_lengths(*lengths, "lengths", k_cache, B);
+  TORCH_CHECK(!rolling || T < (int64_t)INT32_MAX / 2, "attention decode: bad size");
   tbamd::attn_kv_append(a, cur_stream());
 }
 
@@ -196,7 +202,8 @@ Tensor decode_args(tbamd::AttnDecodeArgs& a, const Tensor* qkv, int64_t H, int64
 // place -> o [B, H*64].  len = clamp(lengths[b] + add, 1, cap).  workspace (optional, tests): f32,
 // at least attn_decode_workspace floats; by default it comes from the caching allocator.
 Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const Tensor& v_cache, const Tensor& lengths,
-                   int64_t add, double scale, const optional<Tensor>& workspace, int64_t kv_heads, int64_t window) {
+                   int64_t add, double scale, const optional<Tensor>& workspace, int64_t kv_heads, int64_t window,
+                   bool rolling) {
   const at::DeviceGuard guard(k_cache.device());
   const int64_t H = heads, Hkv = kv_heads_of(heads, kv_heads, "attention decode");
   const bool packed = q.dim() == 3 && q.size(1) == 1 && q.size(2) == packed_qkv_width(H, Hkv);
@@ -212,7 +219,8 @@ Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const 
   }
   Tensor ws = workspace_or_new(workspace, tbamd::attn_decode_workspace(a.B, a.H, a.cap), k_cache, "attention decode");
   a.ws = ws.data_ptr<float>();
-  a.window = cache_window(window, a.cap, "attention decode");
+  a.ring = rolling ? 1 : 0;
+  a.window = rolling ? ring_window(window, a.cap, 1, "attention decode") : cache_window(window, a.cap, "attention decode");
   tbamd::attn_decode(a, cur_stream());
   return o;
 }
@@ -221,12 +229,13 @@ Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const 
 // cache row positions[b] (dropped outside [0, cap)) and the query sees rows j <= positions[b] ->
 // o [B, H*64].  Same bits, output and caches, as attn_kv_append followed by attn_decode(add = 1).
 Tensor attn_decode_append(const Tensor& qkv, int64_t heads, const Tensor& k_cache, const Tensor& v_cache,
-                          const Tensor& positions, double scale, int64_t kv_heads, int64_t window) {
+                          const Tensor& positions, double scale, int64_t kv_heads, int64_t window, bool rolling) {
   const at::DeviceGuard guard(k_cache.device());
   const int64_t H = heads, Hkv = kv_heads_of(heads, kv_heads, "attention decode");
   tbamd::AttnDecodeArgs a{};
   Tensor o = decode_args(a, &qkv, H, Hkv, k_cache, v_cache, positions, "positions", 1, scale);
-  a.window = cache_window(window, a.cap, "attention decode");
+  a.ring = rolling ? 1 : 0;
+  a.window = rolling ? ring_window(window, a.cap, 1, "attention decode") : cache_window(window, a.cap, "attention decode");
   Tensor ws;  // a single chunk is normalised in the split kernel: no partials
   if (tbamd::attn_decode_chunks(a.cap) > 1) {
     ws = at::empty({tbamd::attn_decode_workspace(a.B, a.H, a.cap)}, k_cache.options().dtype(at::kFloat));
@@ -405,7 +414,7 @@ Tensor rope_packed(const Tensor& qkv, int64_t heads, const Tensor& table, const 
 // workspace (optional, tests): f32, at least attn_extend_workspace floats; by default it comes
 // from the caching allocator (none at all with a single key split).
 Tensor attn_extend(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& positions,
-                   double scale, const optional<Tensor>& workspace, int64_t kv_heads, int64_t window) {
+                   double scale, const optional<Tensor>& workspace, int64_t kv_heads, int64_t window, bool rolling) {
   const at::DeviceGuard guard(k_cache.device());
   TORCH_CHECK(k_cache.dim() == 4, "attention extend: cache must be [B, H, cap, 64]");
   const int64_t B = k_cache.size(0), cap = k_cache.size(2);
@@ -439,7 +448,8 @@ Tensor attn_extend(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache
   a.so[0] = T * H * 64, a.so[1] = H * 64;
   a.ws = need > 0 ? ws.data_ptr<float>() : nullptr;
   a.B = (int)B, a.T = (int)T, a.H = (int)H, a.Hkv = (int)Hkv, a.cap = (int)cap, a.scale = (float)scale;
-  a.window = cache_window(window, cap, "attention extend");
+  a.ring = rolling ? 1 : 0;
+  a.window = rolling ? ring_window(window, cap, T, "attention extend") : cache_window(window, cap, "attention extend");
   tbamd::attn_extend(a, cur_stream());
   return o;
 }
@@ -453,12 +463,13 @@ void register_attn(pybind11::module& m) {
         py::arg("lse"), py::arg("scale"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("causal") = false,
         py::arg("key_lengths") = py::none(), py::arg("window") = 0);
   m.def("attn_kv_append", &attn_kv_append, py::arg("qkv"), py::arg("heads"), py::arg("k_cache"), py::arg("v_cache"),
-        py::arg("positions"), py::arg("kv_heads") = 0);
+        py::arg("positions"), py::arg("kv_heads") = 0, py::arg("rolling") = false, py::arg("lengths") = py::none());
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("heads"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("lengths"), py::arg("add"), py::arg("scale"), py::arg("workspace") = py::none(),
-        py::arg("kv_heads") = 0, py::arg("window") = 0);
+        py::arg("kv_heads") = 0, py::arg("window") = 0, py::arg("rolling") = false);
   m.def("attn_decode_append", &attn_decode_append, py::arg("qkv"), py::arg("heads"), py::arg("k_cache"),
-        py::arg("v_cache"), py::arg("positions"), py::arg("scale"), py::arg("kv_heads") = 0, py::arg("window") = 0);
+        py::arg("v_cache"), py::arg("positions"), py::arg("scale"), py::arg("kv_heads") = 0, py::arg("window") = 0,
+        py::arg("rolling") = false);
   m.def("rows_linear", &rows_linear, py::arg("x"), py::arg("weight"), py::arg("bias") = py::none(),
         py::arg("gamma") = py::none(), py::arg("beta") = py::none(), py::arg("eps") = 0.0, py::arg("epi") = 0,
         py::arg("residual") = py::none(), py::arg("out") = py::none(), py::arg("rms") = false);
@@ -473,7 +484,8 @@ void register_attn(pybind11::module& m) {
         py::arg("positions") = py::none(), py::arg("kv_heads") = 0, py::arg("inverse") = false,
         py::arg("out") = py::none());
   m.def("attn_extend", &attn_extend, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("positions"),
-        py::arg("scale"), py::arg("workspace") = py::none(), py::arg("kv_heads") = 0, py::arg("window") = 0);
+        py::arg("scale"), py::arg("workspace") = py::none(), py::arg("kv_heads") = 0, py::arg("window") = 0,
+        py::arg("rolling") = false);
   // knobs and workspace sizes
   m.def("attn_set_head_mask", [](int64_t m) { return (int64_t)tbamd::attn_set_head_mask((int)m); });
   m.def("attn_decode_workspace", [](int64_t B, int64_t H, int64_t cap) {
@@ -487,13 +499,17 @@ void register_attn(pybind11::module& m) {
     TORCH_CHECK(n <= 4, "attn_decode_set_head_block: 0 (the default policy) or 1 .. 4");
     return (int64_t)tbamd::attn_decode_set_head_block((int)n);
   });
-  m.def("attn_decode_head_block", [](int64_t B, int64_t H, int64_t kv_heads, int64_t cap, int64_t window) {
+  m.def("attn_decode_head_block", [](int64_t B, int64_t H, int64_t kv_heads, int64_t cap, int64_t window, bool rolling) {
     const int64_t Hkv = kv_heads_of(H, kv_heads, "attn_decode_head_block");
     TORCH_CHECK(B >= 1 && cap >= 1 && B < (int64_t)INT32_MAX && H < (int64_t)INT32_MAX && cap < (int64_t)INT32_MAX / 2,
                 "attn_decode_head_block: bad size");
+    if (rolling)
+      return (int64_t)tbamd::attn_decode_head_block((int)B, (int)H, (int)Hkv, (int)cap,
+                                                    ring_window(window, cap, 1, "attn_decode_head_block"), 1);
     return (int64_t)tbamd::attn_decode_head_block((int)B, (int)H, (int)Hkv, (int)cap,
                                                   cache_window(window, cap, "attn_decode_head_block"));
-  }, py::arg("B"), py::arg("H"), py::arg("kv_heads"), py::arg("cap"), py::arg("window") = 0);
+  }, py::arg("B"), py::arg("H"), py::arg("kv_heads"), py::arg("cap"), py::arg("window") = 0,
+        py::arg("rolling") = false);
   m.def("attn_extend_splits", [](int64_t B, int64_t H, int64_t T, int64_t cap) {
     return (int64_t)tbamd::attn_extend_splits((int)B, (int)H, (int)T, (int)cap);
   });

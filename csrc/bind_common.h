@@ -92,6 +92,14 @@ inline int64_t kv_heads_of(int64_t heads, int64_t kv_heads, const char* what) {
 inline void check_kv_cache(const Tensor& cache, int64_t hkv, const char* what) {
   TORCH_CHECK(cache.dim() == 4 && cache.size(1) == hkv, what, ": cache must be [B, kv_heads = ", hkv, ", cap, 64]");
 }
+// ---- rolling cache (csrc/attn_ring.h): the cache [B, Hkv, R, 64] is a ring of R slots.  It needs a window
+// 1 <= W <= R (W == R is a real window here, not "none"), and a call that appends T rows before its first
+// query reads needs T <= R - W + 1.  Returns W.
+inline int ring_window(int64_t window, int64_t R, int64_t T, const char* what) {
+  TORCH_CHECK(window >= 1 && window <= R, what, ": a rolling cache needs a window in [1, rows = ", R, "], not ", window);
+  TORCH_CHECK(T <= R - window + 1, what, ": ", T, " new rows need a ring of at least window + ", T - 1, " rows, not ", R);
+  return (int)window;
+}
 // elements of a packed q | k | v row, head dim 64
 inline int64_t packed_qkv_width(int64_t heads, int64_t hkv) { return (heads + 2 * hkv) * 64; }
 

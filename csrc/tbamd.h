@@ -301,6 +301,12 @@ struct AttnAppendArgs {
   const int* pos;
   int B, T, H, Hkv, cap;
   int64_t sqkv[2], sk[3], sv[3];
+  // rolling cache (ring != 0; csrc/attn_ring.h): the cache is a ring of cap slots and token t goes to
+  // slot (pos[b] + t) mod cap iff pos[b] + t >= 0 and n_b - cap <= t < n_b, n_b = clamp(len[b], 1, T)
+  // (T with len null): the last cap valid rows of the call, at most one store per slot.  len: [B]
+  // int32 in device memory or null; only read with ring.
+  const int* len;
+  int ring;
 };
 void attn_kv_append(const AttnAppendArgs& a, hipStream_t st);
 // o[b][h][:] = softmax(q[b][h][:] . K[b][h / G][:len]^T * scale) . V[b][h / G][:len],
@@ -324,13 +330,17 @@ struct AttnDecodeArgs {
   // sliding window (0: none): rows below max(0, len - window) never enter arithmetic either -- chunks
   // that end at or below that row write "empty", the chunk it cuts starts there
   int window;
+  // rolling cache (ring != 0, needs 1 <= window <= cap; csrc/attn_ring.h): the cache is a ring of cap
+  // slots, len = max(klen[b] + add, 1) is NOT clamped to cap and slot p holds logical row j(p), the
+  // largest j = p (mod cap) below len; the query sees the slots with max(0, len - window) <= j(p)
+  int ring;
 };
 // query heads per wave: 0 = the default policy (the largest of 4, 3, 2 that divides G and leaves the
 // grid enough waves, else 1: a function of B, H, Hkv, cap and the chunk size only), otherwise a
 // forced size in 1 .. 4 (used where it divides G, the default policy elsewhere); n < 0 only reads
 // it.  Returns the previous value.
 int attn_decode_set_head_block(int n);
-int attn_decode_head_block(int B, int H, int Hkv, int cap, int window = 0);
+int attn_decode_head_block(int B, int H, int Hkv, int cap, int window = 0, int ring = 0);
 // keys per workgroup (a multiple of 8, >= 8); n < 0 only reads it.  Returns the previous value.
 int attn_decode_set_chunk(int n);
 int attn_decode_chunks(int cap);
@@ -426,6 +436,10 @@ struct AttnExtendArgs {
   // sliding window (0: none): query t sees rows max(0, L(b, t) - window) <= j < L(b, t); rows below
   // the lower limit of a wave's first query are not loaded
   int window;
+  // rolling cache (ring != 0, needs 1 <= window <= cap and T <= cap - window + 1; csrc/attn_ring.h):
+  // L(b, t) = max(pos[b] + t + 1, 1) is NOT clamped to cap and slot p holds logical row j(p), the largest
+  // j = p (mod cap) below L(b, T - 1); query t sees the slots with max(0, L(b, t) - window) <= j(p) < L(b, t)
+  int ring;
 };
 // keys per split: 0 = the default policy (split only when B * H * ceil(T / 16) cannot occupy the
 // chip), otherwise a forced size (a multiple of 8, >= 8; at or above cap: one split); n < 0 only

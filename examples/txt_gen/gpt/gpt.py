@@ -48,6 +48,7 @@ class Config(BaseConfig):
     norm: str = "layer"  # "rms": RMSNorm
     mlp: str = "gelu"  # "swiglu": the gated SiLU MLP
     window: int = 0  # > 0: sliding-window attention, a token sees itself and the window - 1 tokens before it
+    rolling: bool = False  # the sample's KV cache keeps only about `window` rows per layer (needs window > 0)
 
 
 def load_bytes(path: str) -> torch.Tensor:
@@ -86,7 +87,7 @@ def main(conf: Config) -> None:
         prompt = list(conf.sample_prompt.encode())[:conf.seq_len - conf.sample_tokens] or [10]
         tokens = torch.tensor([prompt], dtype=torch.int64, device=data.device)
         model.eval()
-        out, _ = net.generate(tokens, conf.sample_tokens)
+        out, _ = net.generate(tokens, conf.sample_tokens, **({"rolling": True} if conf.rolling else {}))
         text = bytes(prompt + out[0].tolist()).decode("utf-8", errors="replace")
         print(f"sample: {text!r}", flush=True)
     report_sync(model)

@@ -64,8 +64,20 @@ sequence of ``depth`` entries, each ``None`` or an int, per layer -- alternating
 (Mistral, Gemma 2 / 3, gpt-oss).  Training skips the key tiles left of the window, a decode step streams
 at most ``W`` cache rows per layer whatever the context, and ``prefill`` / ``decode_step`` / ``extend`` /
 ``generate`` (``graph=True``, ``cache=``, ``fused=True``, ``draft=`` -- whose two models may differ in
-``window``) keep their meaning.  A :class:`KVCache` is unchanged: full capacity, rows never recycled.
-``window=None`` (the default) is everything above unchanged.
+``window``) keep their meaning.  A :class:`KVCache` is by default unchanged: full capacity, rows never
+recycled.  ``window=None`` (the default) is everything above unchanged.
+
+Rolling KV cache (``KVCache(..., rolling=True, lookahead=16)``, ``generate(..., rolling=True)``): a layer with
+a window ``W`` keeps ``R = roundup8(W + lookahead - 1)`` rows instead of ``capacity`` (when that is fewer) and
+uses them as a ring -- logical row ``j`` lives in slot ``j mod R``, ``cache.positions`` keep counting tokens
+(ops/attention.py states the rule) -- so a windowed layer costs ``O(W)`` memory and ``O(W)`` work per step at
+any context length, and computes what the linear cache computes.  Layers without a window stay linear
+(``cache.rolling[i]`` tells), so local / global alternation mixes both in one cache.  ``prefill`` of a prompt
+longer than ``R`` keeps each sequence's last ``R`` valid rows; ``decode_step`` and ``generate`` (``graph=True``,
+``fused=True``, ``cache=``, ``draft=``) run at any length up to ``capacity``; ``extend`` takes at most
+``lookahead`` tokens per call on such a cache (``ValueError`` beyond: a ring has room for ``R - W + 1`` new
+rows ahead of the first query; feeding more by chunking is left to the caller).  ``rolling=False`` (the
+default) is everything above unchanged.
 """
 from __future__ import annotations
 
@@ -87,22 +99,39 @@ class KVCache:
 
     ``layers[i]`` is the ``(k, v)`` pair of block ``i``, each ``[B, kv_heads, capacity, hd]`` and uninitialised
     (``torch.empty``): rows at or past a sequence's position never enter arithmetic (ops/attention.py).
-    ``positions`` (int32 ``[B]``) is the row each sequence writes next = the number of tokens it holds."""
+    ``positions`` (int32 ``[B]``) is the row each sequence writes next = the number of tokens it holds.
+
+    ``rolling=True``: a layer whose window is ``W`` gets ``R = roundup8(W + lookahead - 1)`` rows if that is
+    below ``capacity`` and is used as a ring (module docstring): ``rolling[i]`` is then ``True`` and
+    ``layers[i]`` a ``[B, kv_heads, R, hd]`` pair.  A layer without a window, or with ``R >= capacity``, is
+    exactly the linear layer it is without ``rolling`` (``rolling[i]`` ``False``).  ``capacity`` keeps its
+    meaning -- logical tokens, ``<= max_len`` -- and ``lookahead`` (>= 1) is the most tokens one ``extend``
+    may feed.  Bytes: ``sum_i 2 * B * kv_heads * rows_i * hd * itemsize``."""
 
     def __init__(self, model: "TransformerLM", batch: int, capacity: Optional[int] = None, dtype=None,
-                 device=None) -> None:
+                 device=None, *, rolling: bool = False, lookahead: int = 16) -> None:
         capacity = model.max_len if capacity is None else int(capacity)
         if not 1 <= capacity <= model.max_len:
             raise ValueError(f"capacity {capacity} must be in [1, max_len = {model.max_len}]")
+        lookahead = int(lookahead)
+        if lookahead < 1:
+            raise ValueError(f"lookahead {lookahead} must be at least 1")
         w = model.tok.weight
         dtype = w.dtype if dtype is None else dtype
         device = w.device if device is None else device
         attn = model.blocks[0].attn
         self.capacity = capacity
+        self.lookahead = lookahead
+        rows = [capacity] * len(model.blocks)
+        if rolling:
+            for i, blk in enumerate(model.blocks):
+                if blk.attn.window is not None:
+                    rows[i] = min(capacity, (blk.attn.window + lookahead - 1 + 7) // 8 * 8)
+        self.rolling: List[bool] = [r < capacity for r in rows]
         self.layers: List[Tuple[Tensor, Tensor]] = [
-            (torch.empty(batch, attn.kv_heads, capacity, attn.hd, dtype=dtype, device=device),
-             torch.empty(batch, attn.kv_heads, capacity, attn.hd, dtype=dtype, device=device))
-            for _ in model.blocks]
+            (torch.empty(batch, attn.kv_heads, r, attn.hd, dtype=dtype, device=device),
+             torch.empty(batch, attn.kv_heads, r, attn.hd, dtype=dtype, device=device))
+            for r in rows]
         self.positions = torch.zeros(batch, dtype=torch.int32, device=device)
 
     def reset(self) -> None:
@@ -212,8 +241,12 @@ class TransformerLM(nn.Module):
                 raise ValueError(f"prompt length {N} exceeds the cache capacity {cache.capacity}")
             cache.positions.zero_()
             x, pending = self._embed(tokens), None
-            for blk, kv in zip(self.blocks, cache.layers):  # the masked self-attention plus one append
-                x, pending = blk(x, pending, lengths, cache=kv, positions=cache.positions)
+            # the masked self-attention plus one append per layer
+            for blk, kv, ring in zip(self.blocks, cache.layers, cache.rolling):
+                if ring:  # the ring append: the last R valid rows of each sequence
+                    x, pending = blk(x, pending, lengths, cache=kv, positions=cache.positions, rolling=True)
+                else:
+                    x, pending = blk(x, pending, lengths, cache=kv, positions=cache.positions)
             if lengths is None:
                 cache.positions.fill_(N)
             else:
@@ -269,11 +302,12 @@ class TransformerLM(nn.Module):
             else:
                 x = self._embed(tokens, cache.positions)
             pending = None
-            for blk, kv in zip(self.blocks, cache.layers):
+            for blk, kv, ring in zip(self.blocks, cache.layers, cache.rolling):
+                rkw = {"rolling": True} if ring else {}  # a linear layer: the calls it always made
                 if fused:
-                    x = blk.forward_rows(x, cache=kv, positions=cache.positions, extend=True)
+                    x = blk.forward_rows(x, cache=kv, positions=cache.positions, extend=True, **rkw)
                 else:
-                    x, pending = blk(x, pending, cache=kv, positions=cache.positions, extend=True)
+                    x, pending = blk(x, pending, cache=kv, positions=cache.positions, extend=True, **rkw)
             adv = None if lengths is None else lengths.clamp(1, T).to(torch.int32)
             if last_only:
                 x, pending = self._last_rows(x, pending, adv, T)
@@ -299,22 +333,27 @@ class TransformerLM(nn.Module):
         ragged prefill.  ``last_only=True`` returns ``[B, vocab]``, the logits of token
         ``clamp(lengths[b], 1, T) - 1`` alone (gathered before the final LayerNorm and the head).
         No device value is read on the host.  ``fused=True``: the few-row kernels (module docstring; native
-        while ``B * T <= 16``, the PyTorch composition of ``linear_rows`` beyond); same result to rounding."""
+        while ``B * T <= 16``, the PyTorch composition of ``linear_rows`` beyond); same result to rounding.
+        On a cache with a rolling layer ``T`` may not exceed ``cache.lookahead`` (``ValueError``)."""
         B, T = tokens.shape
         if T < 1:
             raise ValueError("extend needs at least one token per sequence")
         if T > cache.capacity:
             raise ValueError(f"{T} new tokens exceed the cache capacity {cache.capacity}")
+        if T > cache.lookahead and any(cache.rolling):
+            raise ValueError(f"{T} new tokens exceed the lookahead {cache.lookahead} of a rolling cache")
         return self._step(tokens, cache, lengths, last_only, fused)
 
     def _speculative(self, tokens: Tensor, max_new_tokens: int, lengths: Optional[Tensor], eos: Optional[int],
-                     draft: "TransformerLM", gamma: int, fused: bool = False) -> Tuple[Tensor, Tensor]:
+                     draft: "TransformerLM", gamma: int, fused: bool = False,
+                     rolling: bool = False) -> Tuple[Tensor, Tensor]:
         """Greedy speculative decoding (``generate(draft=...)``)."""
         B, N = tokens.shape
         dev = tokens.device
         cap = N + max_new_tokens + gamma
         kw = {"fused": True} if fused else {}  # fused=False makes exactly the calls it always made
-        tc, dc = KVCache(self, B, capacity=cap), KVCache(draft, B, capacity=cap)
+        rkw = {"rolling": True, "lookahead": max(16, gamma + 1)} if rolling else {}
+        tc, dc = KVCache(self, B, capacity=cap, **rkw), KVCache(draft, B, capacity=cap, **rkw)
         logits, _ = self.prefill(tokens, lengths, tc)
         draft.prefill(tokens, lengths, dc)
         # invariant at the top of a round: both caches hold the history up to, but not including, `cur`
@@ -354,7 +393,7 @@ class TransformerLM(nn.Module):
                  temperature: float = 0.0, top_k: Optional[int] = None, eos: Optional[int] = None,
                  generator=None, graph: bool = False, cache: Optional[KVCache] = None,
                  draft: Optional["TransformerLM"] = None, draft_tokens: int = 4,
-                 fused: bool = False) -> Tuple[Tensor, Tensor]:
+                 fused: bool = False, rolling: bool = False) -> Tuple[Tensor, Tensor]:
         """Continue the prompts ``tokens`` ``[B, N]`` (``lengths``: valid tokens of each, right-padded) by
         ``max_new_tokens`` tokens -> ``(out [B, max_new_tokens], out_lengths [B])``.
 
@@ -386,7 +425,12 @@ class TransformerLM(nn.Module):
 
         ``fused=True``: every ``decode_step`` / ``extend`` made here runs on the few-row kernels (module
         docstring) -- with ``cache``, with ``graph=True`` and, with ``draft``, in both models.  ``prefill`` is
-        unchanged."""
+        unchanged.
+
+        ``rolling=True``: the caches made here are rolling (:class:`KVCache`; with ``draft`` both, with
+        ``lookahead=max(16, draft_tokens + 1)``).  A caller's ``cache`` is what it was built as -- a rolling one
+        works with every option above; its ``tokens`` are fed through ``extend``, so at most
+        ``cache.lookahead`` of them per call.  The ``max_len`` checks stay as they are."""
         B, N = tokens.shape
         max_new_tokens = int(max_new_tokens)
         if max_new_tokens < 1:
@@ -408,6 +452,8 @@ class TransformerLM(nn.Module):
                 raise ValueError(f"prompt {N} + max_new_tokens {max_new_tokens} + draft_tokens {gamma} exceeds "
                                  f"max_len {min(self.max_len, draft.max_len)}")
             with torch.no_grad():
+                if rolling:
+                    return self._speculative(tokens, max_new_tokens, lengths, eos, draft, gamma, fused, True)
                 return self._speculative(tokens, max_new_tokens, lengths, eos, draft, gamma, fused)
         start = None
         kw = {"fused": True} if fused else {}  # fused=False makes exactly the calls it always made
@@ -421,7 +467,7 @@ class TransformerLM(nn.Module):
         with torch.no_grad():
             dev = tokens.device
             if cache is None:
-                cache = KVCache(self, B, capacity=N + max_new_tokens)
+                cache = KVCache(self, B, capacity=N + max_new_tokens, **({"rolling": True} if rolling else {}))
                 logits, _ = self.prefill(tokens, lengths, cache)
             else:
                 logits = self.extend(tokens, cache, lengths, last_only=True, **kw)

@@ -116,7 +116,12 @@ class Attention(nn.Module):
 
     ``window`` (an int >= 1, needs ``causal``; ``None``: nothing changes): sliding-window attention
     (ops/attention.py) -- a token sees itself and the ``window - 1`` tokens before it -- passed to every
-    attention call below: training, prefill, decode step (``fused`` or not) and extend."""
+    attention call below: training, prefill, decode step (``fused`` or not) and extend.
+
+    ``rolling`` (an argument of ``forward`` / ``cached``, not of the layer: it belongs to the cache; needs
+    ``window``): ``cache`` is a rolling pair ``[B, kv_heads, R, hd]`` (ops/attention.py) -- the decode step and
+    the extend pass ``rolling=True`` on, and the prefill's append becomes the ring append with
+    ``lengths=key_lengths``, which keeps the last ``R`` valid rows of each sequence."""
 
     def __init__(self, dim: int, heads: int, causal: bool = False, kv_heads: Optional[int] = None,
                  rope: Optional[Rope] = None, bias: bool = True, window: Optional[int] = None) -> None:
@@ -154,15 +159,16 @@ class Attention(nn.Module):
         return rope_packed(qkv, self.heads, self.rope.table(qkv), positions, kv_heads=self.kv_heads, inplace=inplace)
 
     def forward(self, x: Tensor, key_lengths: Optional[Tensor] = None, *, cache=None,
-                positions: Optional[Tensor] = None, extend: bool = False) -> Tensor:
+                positions: Optional[Tensor] = None, extend: bool = False, rolling: bool = False) -> Tensor:
         if cache is not None:
-            return self.proj(self.cached(self.qkv(x), cache, positions, key_lengths, extend=extend))
+            rkw = {"rolling": True} if rolling else {}  # a linear cache: the call it always made
+            return self.proj(self.cached(self.qkv(x), cache, positions, key_lengths, extend=extend, **rkw))
         kw = self._kw()
         return self.proj(attention_packed(self.rotate(self.qkv(x)), self.heads, 1.0 / math.sqrt(self.hd),
                                           causal=self.causal, key_lengths=key_lengths, **kw))
 
     def cached(self, qkv: Tensor, cache, positions: Optional[Tensor], key_lengths: Optional[Tensor] = None, *,
-               extend: bool = False, fused: bool = False) -> Tensor:
+               extend: bool = False, fused: bool = False, rolling: bool = False) -> Tensor:
         """The cached paths of the class docstring on the packed projection ``qkv`` ``[B, T, (H + 2*Hkv)*hd]``
         (rotated here, in place) -> ``[B, T, H*hd]``, the input of ``proj``.  ``forward`` and
         ``Block.forward_rows`` both end here; ``fused`` folds the append of a decode step into its attention
@@ -171,22 +177,28 @@ class Attention(nn.Module):
             raise ValueError("a KV cache needs causal attention")
         if positions is None:
             raise ValueError("a KV cache needs positions")
+        if rolling and self.window is None:
+            raise ValueError("a rolling cache needs a layer with a window")
         k_cache, v_cache = cache
         scale = 1.0 / math.sqrt(self.hd)
         kw = self._kw()
         one = qkv.shape[1] == 1
         # a prefill's tokens sit at 0 .. N - 1 whatever row they are appended at, a step's at positions[b] + t
         qkv = self.rotate(qkv, positions if extend or one else None, inplace=True)
-        if one:  # attention_extend_packed would make this very call
-            if fused:
-                return attention_decode_packed(qkv, self.heads, k_cache, v_cache, positions, scale, fused=True, **kw)
-            return attention_decode_packed(qkv, self.heads, k_cache, v_cache, positions, scale, **kw)
-        if extend:
+        if one or extend:
+            if rolling:
+                kw["rolling"] = True
+            if one:  # attention_extend_packed would make this very call
+                if fused:
+                    return attention_decode_packed(qkv, self.heads, k_cache, v_cache, positions, scale, fused=True,
+                                                   **kw)
+                return attention_decode_packed(qkv, self.heads, k_cache, v_cache, positions, scale, **kw)
             return attention_extend_packed(qkv, self.heads, k_cache, v_cache, positions, scale, **kw)
+        # a prefill: the masked self-attention never reads the cache; a ring keeps each sequence's last R valid rows
         kv_cache_append(k_cache, v_cache, qkv, self.heads, positions,
-                        **({} if self.kv_heads == self.heads else {"kv_heads": self.kv_heads}))
+                        **({} if self.kv_heads == self.heads else {"kv_heads": self.kv_heads}),
+                        **({"rolling": True, "lengths": key_lengths} if rolling else {}))
         return attention_packed(qkv, self.heads, scale, causal=True, key_lengths=key_lengths, **kw)
-
 
 class MLP(nn.Module):
     def __init__(self, dim: int, hidden: int, bias: bool = True) -> None:
@@ -234,32 +246,36 @@ class Block(nn.Module):
         self.mlp = SwiGLU(dim, hidden, bias) if mlp == "swiglu" else MLP(dim, hidden, bias)
 
     def forward(self, x: Tensor, pending: Optional[Tensor] = None, key_lengths: Optional[Tensor] = None, *,
-                cache=None, positions: Optional[Tensor] = None, extend: bool = False):
+                cache=None, positions: Optional[Tensor] = None, extend: bool = False, rolling: bool = False):
         """``x``: residual stream; ``pending``: a sub-block output not yet added
         to it.  Returns (stream, pending) so adds fuse into the next LayerNorm.
         ``key_lengths``: per-batch key lengths for the attention (None: every key).
-        ``cache`` / ``positions`` / ``extend``: this layer's KV cache, passed to :class:`Attention`."""
+        ``cache`` / ``positions`` / ``extend`` / ``rolling``: this layer's KV cache, passed to :class:`Attention`."""
         if pending is None:
             h = self.ln1(x)
         else:
             h, x = self.ln1(x, pending)
-        a = self.attn(h, key_lengths, cache=cache, positions=positions, extend=extend)
+        if rolling:
+            a = self.attn(h, key_lengths, cache=cache, positions=positions, extend=extend, rolling=True)
+        else:
+            a = self.attn(h, key_lengths, cache=cache, positions=positions, extend=extend)
         h, x = self.ln2(x, a)
         return x, self.mlp(h)
 
-    def forward_rows(self, x: Tensor, *, cache, positions: Tensor, extend: bool = False) -> Tensor:
+    def forward_rows(self, x: Tensor, *, cache, positions: Tensor, extend: bool = False,
+                     rolling: bool = False) -> Tensor:
         """The decoding layer on the few-row kernels (ops/linear.py ``linear_rows``; causal, forward only):
         ``x`` ``[B, T, dim]`` is the residual stream itself -- there is no ``pending`` -- and so is the
         result.  Both norms (LayerNorm or RMSNorm) run as prologues of the product behind them, bias / GELU or
         SwiGLU / residual as epilogues, and the attention is ``Attention.cached(fused=True)``: with ``T == 1`` 5 launches with a
         single-chunk cache, 6 otherwise (one more with rotary positions: the rotation of ``qkv``).
         ``T > 1`` needs ``extend=True``.  Computes what ``forward`` computes with ``cache`` / ``positions`` /
-        ``extend``, to rounding."""
+        ``extend``, to rounding.  ``rolling``: ``cache`` is a rolling pair (:class:`Attention`)."""
         at = self.attn
         if x.shape[1] != 1 and not extend:
             raise ValueError("forward_rows: more than one token per sequence needs extend=True")
         qkv = linear_rows(x, at.qkv.weight, at.qkv.bias, **norm_args(self.ln1))
-        a = at.cached(qkv, cache, positions, extend=extend, fused=True)
+        a = at.cached(qkv, cache, positions, extend=extend, fused=True, **({"rolling": True} if rolling else {}))
         x = linear_rows(a, at.proj.weight, at.proj.bias, residual=x)
         act = "swiglu" if isinstance(self.mlp, SwiGLU) else "gelu"
         h = linear_rows(x, self.mlp.fc1.weight, self.mlp.fc1.bias, **norm_args(self.ln2), act=act)

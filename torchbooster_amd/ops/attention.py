@@ -105,6 +105,29 @@ expanded to ``H`` heads.  Training and prefill (:func:`attention`, :func:`attent
 ``Hkv < H``) expand k / v to ``H`` heads -- one materialised copy -- and run the existing kernels under
 autograd, which sums dK / dV over each group; a group-aware training kernel is not part of this.
 
+Rolling KV cache (``rolling=True`` on the five cache functions, a host ``bool`` that is never inferred from a
+shape, like ``kv_heads``; csrc/attn_ring.h).  The caches are ``[B, Hkv, R, D]`` used as a RING: logical row
+``j`` (the ``j``-th token of the sequence) lives in slot ``j mod R``, and ``positions`` / ``lengths`` keep
+counting tokens, not slots -- the lower clamp to 1 stays, the upper clamp to the row count is gone.  With
+an upper limit ``n`` -- ``max(lengths[b] + add, 1)`` of a decode, ``L(b, T - 1) = max(positions[b] + T, 1)`` of
+an extend, for the whole call -- slot ``p`` holds logical row ``j(p)``, the largest ``j = p (mod R)`` with
+``j < n``; ``j(p) < 0`` is a slot that was never written and is hidden.  A query with limit ``L`` and window
+``W`` sees slot ``p`` iff ``max(0, L - W) <= j(p) < L``: over logical rows, exactly the window rule above, so
+a rolling layer computes what the linear cache of all rows computes while it keeps ``R`` rows and streams
+``R`` rows per step at any context length.  ``rolling=True`` needs a ``window`` with ``1 <= W <= R``
+(``ValueError`` otherwise; ``W == R`` is a real window here and is not turned into ``window=None``).  An
+extend appends its ``T`` rows before its first query reads, so it needs ``T <= R - W + 1``, decided on the
+host from shapes (``ValueError``): the row written for token ``T - 1`` then replaces logical row
+``positions[b] + T - 1 - R``, which lies below the first query's lower limit ``positions[b] + 1 - W``.  The
+same inequality keeps "rows past the position" harmless in a ring -- the pad tokens of a ragged extend, the
+rejected rows of a speculative round: such a stale slot is read as logical row ``pos + t - R``, which no
+later query can see.  :func:`kv_cache_append` with ``rolling=True`` stores token ``t`` to slot
+``(positions[b] + t) mod R`` iff ``positions[b] + t >= 0`` and ``n_b - R <= t < n_b``, ``n_b = clamp(lengths[b],
+1, T)`` with its ``lengths=`` (int32 ``[B]``; a ragged prefill) and ``T`` without: the last ``R`` valid rows of
+the call, no pad rows, at most one store per slot.  Hidden slots NEVER enter arithmetic on either path (not
+loaded natively; selected away before either product on the PyTorch path, which is built from the same
+``j(p)`` formula and is sync-free).  ``rolling=False``, the default, is everything above unchanged.
+
 Rotary position embeddings (csrc/rope.hip): :func:`rope_packed` rotates the q and k parts of a packed
 projection by the angles :func:`rope_table` holds, before any of the functions above reads it -- so the
 training path, the prefill, the append, the decode and the extend all see rotated q / k, a cache holds
@@ -377,6 +400,50 @@ def _decode_native(x: Tensor, k_cache: Tensor, v_cache: Tensor) -> bool:
             and x.dtype == torch.bfloat16 and _rows_ok(k_cache) and _rows_ok(v_cache))
 
 
+def _ring_rows(n: Tensor, R: int) -> Tensor:
+    """``j(p)`` of the module docstring for int64 limits ``n`` ``[B]`` (>= 1) -> int64 ``[B, R]``: the logical
+    row slot ``p`` holds, the largest ``j = p (mod R)`` below ``n``; negative where none was written."""
+    p = torch.arange(R, device=n.device)[None, :]
+    return n[:, None] - 1 - torch.remainder(n[:, None] - 1 - p, R)
+
+
+def _ring_kw(window, k_cache: Tensor, T: int = 1) -> dict:
+    """The trailing keywords of a rolling call, checked on the host from shapes: a window ``1 <= W <= R``
+    (kept as given: ``W == R`` is a window) and ``T <= R - W + 1`` rows appended ahead of the first query."""
+    window = _window(window)
+    if window is None:
+        raise ValueError("rolling=True needs a window")
+    if k_cache.dim() == 4:
+        R = k_cache.shape[2]
+        if window > R:
+            raise ValueError(f"rolling=True needs window {window} <= the cache's {R} rows")
+        if T > R - window + 1:
+            raise ValueError(f"{T} new rows with window {window} need a ring of at least {window + T - 1} rows, "
+                             f"not {R}")
+    return {"window": window, "rolling": True}
+
+
+def _append_ring_ref(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, positions: Tensor, hkv: int,
+                     lengths: Optional[Tensor]) -> None:
+    """The PyTorch path of :func:`kv_cache_append` with ``rolling=True``, seen from the ring: slot ``p`` of
+    batch ``b`` takes the one token ``t`` of ``[n_b - R, n_b)`` with ``positions[b] + t = p (mod R)`` if
+    ``t >= 0`` and ``positions[b] + t >= 0``, and keeps its bits otherwise (no host sync, no scatter)."""
+    B, T, E3 = qkv.shape
+    D = E3 // (heads + 2 * hkv)
+    R = k_cache.shape[2]
+    if T == 0:
+        return
+    pos = positions.to(torch.int64)
+    n = torch.full_like(pos, T) if lengths is None else lengths.to(torch.int64).clamp(1, T)
+    t = _ring_rows(pos + n, R) - pos[:, None]  # [B, R]: the largest t = p - pos (mod R) below n_b
+    take = ((t >= 0) & (t + pos[:, None] >= 0))[:, None, :, None]
+    idx = t.clamp(0, T - 1)[:, :, None, None].expand(B, R, hkv, D)
+    kv = qkv[..., heads * D:].reshape(B, T, 2, hkv, D)  # the k | v parts
+    for cache, i in ((k_cache, 0), (v_cache, 1)):
+        rows = kv[:, :, i].gather(1, idx).permute(0, 2, 1, 3).to(cache.dtype)  # [B, Hkv, R, D]
+        cache.copy_(torch.where(take, rows, cache))
+
+
 def _append_ref(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, positions: Tensor,
                 hkv: Optional[int] = None) -> None:
     """The PyTorch path of :func:`kv_cache_append`: seen from the cache, row j of batch b takes token
@@ -396,17 +463,23 @@ def _append_ref(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, posit
 
 
 def _decode_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tensor, scale: float,
-                window: Optional[int] = None) -> Tensor:
+                window: Optional[int] = None, rolling: bool = False) -> Tensor:
     """The PyTorch path of :func:`attention_decode` (softmax in fp32, or fp64 for fp64 inputs).  Hidden
     rows -- at or past the length, and below ``len - window`` -- are selected away before either product:
     a masked score is -inf whatever k held, and v is zeroed there because 0 * NaN is NaN.  A cache of
-    ``Hkv < H`` heads is grouped-query attention."""
+    ``Hkv < H`` heads is grouped-query attention.  ``rolling``: the same over the logical rows ``j(p)`` of the
+    ring's slots (module docstring), with the length not clamped to the row count."""
     cap = k_cache.shape[2]
-    n = lengths.to(torch.int64).clamp(1, cap)  # the kernels' clamp
-    j = torch.arange(cap, device=q.device)[None, :]
-    vis = j < n[:, None]
-    if window is not None:
-        vis = vis & (j >= n[:, None] - window)
+    if rolling:
+        n = lengths.to(torch.int64).clamp_min(1)
+        j = _ring_rows(n, cap)  # < n by construction
+        vis = (j >= 0) & (j >= n[:, None] - window)
+    else:
+        n = lengths.to(torch.int64).clamp(1, cap)  # the kernels' clamp
+        j = torch.arange(cap, device=q.device)[None, :]
+        vis = j < n[:, None]
+        if window is not None:
+            vis = vis & (j >= n[:, None] - window)
     vis = vis[:, None, :]  # [B, 1, cap]
     ct = torch.float64 if q.dtype == torch.float64 else torch.float32
     v = torch.where(vis[..., None], v_cache, torch.zeros((), dtype=v_cache.dtype, device=q.device)).to(ct)
@@ -422,17 +495,36 @@ def _decode_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tensor, sc
 
 
 def kv_cache_append(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, positions: Tensor, *,
-                    kv_heads: Optional[int] = None) -> None:
+                    kv_heads: Optional[int] = None, rolling: bool = False,
+                    lengths: Optional[Tensor] = None) -> None:
     """Write the k / v rows of the packed ``qkv`` ``[B, T, (H + 2*Hkv)*D]`` into ``k_cache`` / ``v_cache``
     ``[B, Hkv, cap, D]`` at rows ``positions[b] + t`` (int32 ``[B]``); rows outside ``[0, cap)`` are dropped.
-    ``kv_heads``: ``Hkv`` of grouped-query attention (module docstring); ``None`` is ``H``."""
+    ``kv_heads``: ``Hkv`` of grouped-query attention (module docstring); ``None`` is ``H``.
+
+    ``rolling=True``: the caches are a ring of ``R = cap`` slots (module docstring) and token ``t`` goes to
+    slot ``(positions[b] + t) mod R`` iff ``positions[b] + t >= 0`` and ``n_b - R <= t < n_b``, where ``n_b =
+    clamp(lengths[b], 1, T)`` with ``lengths`` (int32 ``[B]``: the valid tokens of a right-padded batch) and
+    ``T`` without: the last ``R`` valid rows, no pad rows.  ``lengths`` without ``rolling`` raises
+    ``ValueError``."""
+    if lengths is not None and not rolling:
+        raise ValueError("kv_cache_append: lengths needs rolling=True")
     _forward_only(qkv, k_cache, v_cache)
     hkv, B, _, D, _ = _packed_dims(qkv, heads, kv_heads)
+    if rolling and lengths is not None and (lengths.dtype != torch.int32 or lengths.shape != (B,)
+                                            or lengths.device != k_cache.device):
+        raise RuntimeError("lengths must be an int32 tensor of shape [B] on the device of the cache")
     with torch.no_grad():
         if _decode_native(qkv, k_cache, v_cache):
+            if rolling:
+                native().attn_kv_append(_rows(qkv), heads, k_cache, v_cache, positions, hkv, rolling=True,
+                                        lengths=None if lengths is None else lengths.contiguous())
+                return
             native().attn_kv_append(_rows(qkv), heads, k_cache, v_cache, positions, hkv)
             return
         _check_cache(k_cache, v_cache, B, hkv, D, positions, "positions")
+        if rolling:
+            _append_ring_ref(k_cache, v_cache, qkv, heads, positions, hkv, lengths)
+            return
         _append_ref(k_cache, v_cache, qkv, heads, positions, hkv)
 
 
@@ -445,17 +537,19 @@ def _cache_window(window, k_cache: Tensor) -> dict:
 
 def attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tensor,
                      scale: Optional[float] = None, *, kv_heads: Optional[int] = None,
-                     window: Optional[int] = None) -> Tensor:
+                     window: Optional[int] = None, rolling: bool = False) -> Tensor:
     """One query per (batch, head): ``q`` ``[B, H, D]`` against the first ``len = clamp(lengths[b], 1, cap)``
     rows of ``k_cache`` / ``v_cache`` ``[B, Hkv, cap, D]`` -> ``[B, H, D]``.  ``kv_heads``: ``Hkv`` of
     grouped-query attention (module docstring); ``None`` is ``H``.  ``window``: only the rows
-    ``max(0, len - window) <= j < len`` (module docstring); ``window >= cap`` is ``window=None``."""
+    ``max(0, len - window) <= j < len`` (module docstring); ``window >= cap`` is ``window=None``.
+    ``rolling=True`` (needs ``1 <= window <= cap``): the caches are a ring, ``len = max(lengths[b], 1)`` counts
+    tokens and the query sees the slots whose logical row is in the window (module docstring)."""
     _forward_only(q, k_cache, v_cache)
     if q.dim() != 3:
         raise RuntimeError("q must be [B, H, D]")
     B, H, D = q.shape
     hkv = _kv_heads(H, kv_heads)
-    wkw = _cache_window(window, k_cache)
+    wkw = _ring_kw(window, k_cache) if rolling else _cache_window(window, k_cache)
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     with torch.no_grad():
         if _decode_native(q, k_cache, v_cache):
@@ -467,7 +561,8 @@ def attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tenso
 
 def attention_decode_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
                             scale: Optional[float] = None, *, fused: bool = False,
-                            kv_heads: Optional[int] = None, window: Optional[int] = None) -> Tensor:
+                            kv_heads: Optional[int] = None, window: Optional[int] = None,
+                            rolling: bool = False) -> Tensor:
     """One decode step on the packed ``[B, 1, (H + 2*Hkv)*D]`` projection of the new token: append its k / v
     at row ``positions[b]``, then attend to keys ``j <= positions[b]`` -> ``[B, 1, H*D]``.  ``kv_heads``:
     ``Hkv`` of grouped-query attention (module docstring); ``None`` is ``H``.  ``window``: as
@@ -477,44 +572,60 @@ def attention_decode_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: T
     ``fused=True`` (native path): the append is folded into the split kernel -- the wave whose chunk
     holds row ``positions[b]`` takes it from ``qkv`` and stores it to the cache -- and a cache of a single
     chunk is normalised there too, so a step is one or two launches instead of three.  Output and caches
-    have the bits of ``fused=False``."""
+    have the bits of ``fused=False``.
+
+    ``rolling=True`` (needs ``1 <= window <= cap``): the caches are a ring -- the row goes to slot
+    ``positions[b] mod cap`` (dropped when ``positions[b] < 0``) and ``len = max(positions[b] + 1, 1)``."""
     _forward_only(qkv, k_cache, v_cache)
     hkv, B, _, D, scale = _packed_dims(qkv, heads, kv_heads, scale, T="1")
-    wkw = _cache_window(window, k_cache)
+    wkw = _ring_kw(window, k_cache) if rolling else _cache_window(window, k_cache)
+    akw = {"rolling": True} if rolling else {}  # the append's; no ring: the calls it always made
     with torch.no_grad():
         if _decode_native(qkv, k_cache, v_cache):
             qkv, C = _rows(qkv), native()
             if fused:
                 return C.attn_decode_append(qkv, heads, k_cache, v_cache, positions, scale,
                                             hkv, **wkw).view(B, 1, heads * D)
-            C.attn_kv_append(qkv, heads, k_cache, v_cache, positions, hkv)
+            C.attn_kv_append(qkv, heads, k_cache, v_cache, positions, hkv, **akw)
             return C.attn_decode(qkv, heads, k_cache, v_cache, positions, 1, scale, None,
                                  hkv, **wkw).view(B, 1, heads * D)
         _check_cache(k_cache, v_cache, B, hkv, D, positions, "positions")
-        _append_ref(k_cache, v_cache, qkv, heads, positions, hkv)
+        if rolling:
+            _append_ring_ref(k_cache, v_cache, qkv, heads, positions, hkv, None)
+        else:
+            _append_ref(k_cache, v_cache, qkv, heads, positions, hkv)
         q = qkv[:, 0, :heads * D].reshape(B, heads, D)
         return _decode_ref(q, k_cache, v_cache, positions.to(torch.int64) + 1, scale,
                            **wkw).reshape(B, 1, heads * D)
 
 
 def _extend_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor, scale: float,
-                window: Optional[int] = None) -> Tensor:
+                window: Optional[int] = None, rolling: bool = False) -> Tensor:
     """The PyTorch path of :func:`attention_extend` (softmax in fp32, or fp64 for fp64 inputs), sync-free.
     ``q`` ``[B, T, H, D]`` -> ``[B, T, H, D]``.  Scores are masked to -inf by ``L(b, t)``; v is zeroed at
     rows ``>= clamp(positions[b] + T, 1, cap)`` before the product because 0 * NaN is NaN.  Rows between
     a query's limit and that bound (this call's tokens) are multiplied by an exact-zero probability.
     A cache of ``Hkv < H`` heads is grouped-query attention.  ``window``: scores below ``L(b, t) - window``
-    are masked as well, and v is also zeroed below the first query's lower limit ``L(b, 0) - window``."""
+    are masked as well, and v is also zeroed below the first query's lower limit ``L(b, 0) - window``.
+    ``rolling``: the same over the logical rows ``j(p)`` of the ring's slots for the limit ``L(b, T - 1)``
+    (module docstring), with no limit clamped to the row count; never-written slots are zeroed too."""
     B, T, H, D = q.shape
     cap = k_cache.shape[2]
     pos = positions.to(torch.int64)
-    lim = (pos[:, None] + torch.arange(1, T + 1, device=q.device)[None, :]).clamp(1, cap)  # L(b, t): [B, T]
-    j = torch.arange(cap, device=q.device)
-    vis = j[None, None, :] < lim[:, :, None]  # [B, T, cap]
-    held = j[None, :] < (pos + T).clamp(1, cap)[:, None]  # [B, cap]
-    if window is not None:
-        vis = vis & (j[None, None, :] >= lim[:, :, None] - window)
-        held = held & (j[None, :] >= lim[:, :1] - window)
+    lim = pos[:, None] + torch.arange(1, T + 1, device=q.device)[None, :]  # L(b, t): [B, T]
+    if rolling:
+        lim = lim.clamp_min(1)
+        j = _ring_rows(lim[:, -1], cap)  # [B, cap], < L(b, T - 1) by construction
+        vis = (j[:, None, :] < lim[:, :, None]) & (j[:, None, :] >= lim[:, :, None] - window) & (j[:, None, :] >= 0)
+        held = (j >= 0) & (j >= lim[:, :1] - window)
+    else:
+        lim = lim.clamp(1, cap)
+        j = torch.arange(cap, device=q.device)
+        vis = j[None, None, :] < lim[:, :, None]  # [B, T, cap]
+        held = j[None, :] < (pos + T).clamp(1, cap)[:, None]  # [B, cap]
+        if window is not None:
+            vis = vis & (j[None, None, :] >= lim[:, :, None] - window)
+            held = held & (j[None, :] >= lim[:, :1] - window)
     vis, held = vis[:, None], held[:, None, :, None]  # [B, 1, T, cap], [B, 1, cap, 1]
     ct = torch.float64 if q.dtype == torch.float64 else torch.float32
     v = torch.where(held, v_cache, torch.zeros((), dtype=v_cache.dtype, device=q.device)).to(ct)
@@ -530,7 +641,7 @@ def _extend_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor, 
 
 def attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
                      scale: Optional[float] = None, *, kv_heads: Optional[int] = None,
-                     window: Optional[int] = None) -> Tensor:
+                     window: Optional[int] = None, rolling: bool = False) -> Tensor:
     """``T`` queries per (batch, head): ``q`` ``[B, T, H, D]`` (any view with a contiguous last dim), whose
     k / v rows are already in ``k_cache`` / ``v_cache`` ``[B, Hkv, cap, D]`` at rows ``positions[b] + t``.
     Query ``t`` sees rows ``j < clamp(positions[b] + t + 1, 1, cap)`` -> ``[B, T, H, D]``.  ``kv_heads``:
@@ -539,13 +650,16 @@ def attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Ten
     Cache rows at or past ``clamp(positions[b] + T, 1, cap)`` never enter arithmetic; rows between a
     query's own limit and that bound are this call's tokens (real finite data) and may be multiplied by
     an exact-zero probability.  ``window``: query ``t`` sees only the rows at or past ``L(b, t) - window``
-    (module docstring, which also says what may enter arithmetic); ``window >= cap`` is ``window=None``."""
+    (module docstring, which also says what may enter arithmetic); ``window >= cap`` is ``window=None``.
+    ``rolling=True`` (needs ``1 <= window <= cap`` and ``T <= cap - window + 1``): the caches are a ring, the
+    rows sit in slots ``(positions[b] + t) mod cap`` and ``L(b, t) = max(positions[b] + t + 1, 1)`` counts
+    tokens (module docstring)."""
     _forward_only(q, k_cache, v_cache)
     if q.dim() != 4 or q.shape[1] < 1:
         raise RuntimeError("q must be [B, T >= 1, H, D]")
     B, T, H, D = q.shape
     hkv = _kv_heads(H, kv_heads)
-    wkw = _cache_window(window, k_cache)
+    wkw = _ring_kw(window, k_cache, T) if rolling else _cache_window(window, k_cache)
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     with torch.no_grad():
         if _decode_native(q, k_cache, v_cache):
@@ -557,15 +671,18 @@ def attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Ten
 
 def attention_extend_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
                             scale: Optional[float] = None, *, kv_heads: Optional[int] = None,
-                            window: Optional[int] = None) -> Tensor:
+                            window: Optional[int] = None, rolling: bool = False) -> Tensor:
     """``T`` new tokens on their packed ``[B, T, (H + 2*Hkv)*D]`` projection: append their k / v at rows
     ``positions[b] + t`` (rows outside ``[0, cap)`` are dropped), then query ``t`` attends to rows
     ``j < clamp(positions[b] + t + 1, 1, cap)`` -> ``[B, T, H*D]``.  ``T == 1`` is
     :func:`attention_decode_packed`.  What may enter arithmetic: see :func:`attention_extend`.
     ``kv_heads``: ``Hkv`` of grouped-query attention (module docstring); ``None`` is ``H``.  ``window``: as
-    :func:`attention_extend` (``T == 1``: the same window in :func:`attention_decode_packed`)."""
+    :func:`attention_extend` (``T == 1``: the same window in :func:`attention_decode_packed`).
+    ``rolling=True``: the ring of :func:`kv_cache_append` and :func:`attention_extend` (``T <= cap - window +
+    1``, or ``ValueError`` before anything is written)."""
     dims = _packed_dims(qkv, heads, kv_heads, scale, T="T >= 1")
-    wkw = _cache_window(window, k_cache)
+    wkw = _ring_kw(window, k_cache, dims[2]) if rolling else _cache_window(window, k_cache)
+    akw = {"rolling": True} if rolling else {}  # the append's; no ring: the calls it always made
     if dims[2] == 1:
         return attention_decode_packed(qkv, heads, k_cache, v_cache, positions, scale, kv_heads=kv_heads, **wkw)
     _forward_only(qkv, k_cache, v_cache)
@@ -573,11 +690,14 @@ def attention_extend_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: T
     with torch.no_grad():
         if _decode_native(qkv, k_cache, v_cache):
             qkv, C = _rows(qkv), native()
-            C.attn_kv_append(qkv, heads, k_cache, v_cache, positions, hkv)
+            C.attn_kv_append(qkv, heads, k_cache, v_cache, positions, hkv, **akw)
             q = qkv[..., :heads * D].view(B, T, heads, D)
             return C.attn_extend(q, k_cache, v_cache, positions, scale, None, hkv, **wkw)
         _check_cache(k_cache, v_cache, B, hkv, D, positions, "positions")
-        _append_ref(k_cache, v_cache, qkv, heads, positions, hkv)
+        if rolling:
+            _append_ring_ref(k_cache, v_cache, qkv, heads, positions, hkv, None)
+        else:
+            _append_ref(k_cache, v_cache, qkv, heads, positions, hkv)
         q = qkv[..., :heads * D].reshape(B, T, heads, D)
         return _extend_ref(q, k_cache, v_cache, positions, scale, **wkw).reshape(B, T, heads * D)
 
