@@ -81,6 +81,25 @@
 // and -- R consecutive t -- at most one store per slot per launch, so there is no write race.  A negative
 // position still never becomes an address.  RING is a template parameter next to WIN: every call without
 // `ring` takes the instantiations that existed before.
+//
+// FP8 cache (AttnDecodeArgs::fp8 / AttnAppendArgs::fp8, host values; csrc/attn_fp8.h): kc / vc hold OCP e4m3
+// codes, a cache row is 64 B and the strides count bytes.  attn_kv_append_k<.., true> still gives one lane 16 B
+// of qkv (8 bf16); the lane quantises them -- clamp(f32(x) * inv, -448, 448), NaN passed through, then
+// v_cvt_pk_fp8_f32 -- and stores 8 B; placement, ring or linear, is the same statement.  The split kernels keep
+// the (row group, c) lane map with an 8-B load per lane, so a wave load is one aligned 512 B, and unpack the
+// codes with v_cvt_pk_f32_fp8 where the bf16 halves were shifted.  The scales never meet an element: k_scale is
+// inside a.scale (sc = scale * k_scale * log2e, the first product an f32 one on the host), P.V accumulates the
+// unscaled codes and acc is multiplied by vscale once per head after the 8 row groups are merged, ahead of the
+// partial or of the single-chunk normalised store -- so the merge kernel and the workspace are those of bf16.
+// The fused append quantises the step's row from qkv in EVERY wave that meets it and multiplies the codes; head
+// block 0 stores them: fused and unfused calls have the same bits, output and cache.  Hidden rows are the zero
+// code without a load, as they were the zero bf16: the cache may hold the NaN code there.  The lane map and
+// kUnroll are those of bf16 (profiles/kv_fp8/README.md has the measurements).  FP8 is a template parameter next
+// to WIN and RING: every call on a bf16 cache takes the instantiations that existed before
+// (profiles/kv_fp8/resources.txt).
+#include <type_traits>
+
+#include "attn_fp8.h"
 #include "attn_ring.h"
 #include "common.h"
 #include "tbamd.h"
@@ -112,9 +131,9 @@ __device__ __forceinline__ int decode_len(const int* klen, int b, int add, int c
   return (int)(l < 1 ? 1 : (l > cap ? cap : l));
 }
 
-template <bool RING>
+template <bool RING, bool FP8 = false>
 __global__ __launch_bounds__(256) void attn_kv_append_k(AttnAppendArgs a) {
-  // one lane per 16 B: (b, t, k|v, h, c)
+  // one lane per 16 B of qkv: (b, t, k|v, h, c); FP8: the 8 values leave as 8 B of codes
   const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t total = (int64_t)a.B * a.T * 2 * a.Hkv * 8;
   if (id >= total) return;
@@ -136,6 +155,12 @@ __global__ __launch_bounds__(256) void attn_kv_append_k(AttnAppendArgs a) {
     return;  // dropped: a bad position never moves an address
   }
   const uint16_t* src = a.qkv + b * a.sqkv[0] + t * a.sqkv[1] + (int64_t)(a.H + which * a.Hkv) * 64 + h * 64 + c * 8;
+  if constexpr (FP8) {  // the cache strides count codes (bytes)
+    uint8_t* dst = which ? reinterpret_cast<uint8_t*>(a.vc) + b * a.sv[0] + h * a.sv[1] + row * a.sv[2] + c * 8
+                         : reinterpret_cast<uint8_t*>(a.kc) + b * a.sk[0] + h * a.sk[1] + row * a.sk[2] + c * 8;
+    *reinterpret_cast<uint2*>(dst) = fp8_quant8(*reinterpret_cast<const uint4*>(src), which ? a.vinv : a.kinv);
+    return;
+  }
   uint16_t* dst = which ? a.vc + b * a.sv[0] + h * a.sv[1] + row * a.sv[2] + c * 8
                         : a.kc + b * a.sk[0] + h * a.sk[1] + row * a.sk[2] + c * 8;
   *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
@@ -157,8 +182,16 @@ struct AttnNewRow {
 // to the cache: exactly one store per row, and no wave reads that cache row.  p outside [0, cap)
 // equals no visible row index: nothing is stored.  With one chunk the wave finishes each head with
 // the merge kernel's own arithmetic (M - M, fma by exp2 of it, divide) and writes bf16.
-template <bool FUSED, int GB, bool WIN, bool RING>
+//
+// FP8 (csrc/attn_fp8.h): a cache row is 64 codes, a lane's piece of it 8 B (the same (row group, c) lane
+// map: a wave load is one aligned 512 B) converted by v_cvt_pk_f32_fp8 where the bf16 halves were shifted;
+// a.scale carries k_scale, and acc is multiplied by v_scale once, after the 8 row groups are merged.  The
+// fused append quantises the step's row from qkv and uses the codes: what head block 0 stores is what every
+// wave multiplies.
+template <bool FUSED, int GB, bool WIN, bool RING, bool FP8>
 __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, const AttnNewRow& n) {
+  using Row = typename std::conditional<FP8, uint2, uint4>::type;   // a lane's 8 values of a cache row
+  using Elt = typename std::conditional<FP8, uint8_t, uint16_t>::type;  // what the cache strides count
   const int lane = threadIdx.x;
   const int g = lane >> 3, c = lane & 7;
   const int ck = blockIdx.x % a.nchunks;
@@ -201,8 +234,8 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
   for (int j = 0; j < GB; ++j)
     unpack8(*reinterpret_cast<const uint4*>(a.q + b * a.sq[0] + (h0 + j) * a.sq[1] + c * 8), q[j]);
   const float sc = a.scale * kLog2e;
-  const uint16_t* kb = a.k + b * a.sk[0] + hk * a.sk[1] + c * 8;
-  const uint16_t* vb = a.v + b * a.sv[0] + hk * a.sv[1] + c * 8;
+  const Elt* kb = reinterpret_cast<const Elt*>(a.k) + b * a.sk[0] + hk * a.sk[1] + c * 8;
+  const Elt* vb = reinterpret_cast<const Elt*>(a.v) + b * a.sv[0] + hk * a.sv[1] + c * 8;
   // RING: the step's row is logical row klen[b] = n - 1 when that is >= 0: slot pm; -1 meets no slot
   const int64_t p = FUSED ? (RING ? ((int64_t)a.klen[b] >= 0 ? (int64_t)pm : -1) : (int64_t)a.klen[b]) : -1;
 
@@ -215,7 +248,7 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
   }
 
   for (int r0 = first + g; r0 < end; r0 += 8 * kUnroll) {
-    uint4 kr[kUnroll], vr[kUnroll];
+    Row kr[kUnroll], vr[kUnroll];
     bool ok[kUnroll];
 #pragma unroll
     for (int u = 0; u < kUnroll; ++u) {
@@ -223,18 +256,28 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
       if constexpr (RING) ok[u] = r < end && ring_back(pm, r, len) < wv;
       else ok[u] = r < end && (!WIN || r >= lo);
       const int rr = ok[u] ? r : vis;  // a hidden row never forms an address
-      kr[u] = make_uint4(0, 0, 0, 0);
-      vr[u] = make_uint4(0, 0, 0, 0);
+      if constexpr (FP8) {
+        kr[u] = make_uint2(0, 0);  // the code of +0
+        vr[u] = make_uint2(0, 0);
+      } else {
+        kr[u] = make_uint4(0, 0, 0, 0);
+        vr[u] = make_uint4(0, 0, 0, 0);
+      }
       if (FUSED && ok[u] && (int64_t)r == p) {  // 0 <= r < len <= cap: the store is inside the cache
-        kr[u] = *reinterpret_cast<const uint4*>(n.k + b * n.s + hk * 64 + c * 8);
-        vr[u] = *reinterpret_cast<const uint4*>(n.v + b * n.s + hk * 64 + c * 8);
+        if constexpr (FP8) {
+          kr[u] = fp8_quant8(*reinterpret_cast<const uint4*>(n.k + b * n.s + hk * 64 + c * 8), a.kinv);
+          vr[u] = fp8_quant8(*reinterpret_cast<const uint4*>(n.v + b * n.s + hk * 64 + c * 8), a.vinv);
+        } else {
+          kr[u] = *reinterpret_cast<const uint4*>(n.k + b * n.s + hk * 64 + c * 8);
+          vr[u] = *reinterpret_cast<const uint4*>(n.v + b * n.s + hk * 64 + c * 8);
+        }
         if (hb == 0) {  // wave-uniform: one storing wave per (batch, kv head)
-          *reinterpret_cast<uint4*>(const_cast<uint16_t*>(kb) + rr * a.sk[2]) = kr[u];
-          *reinterpret_cast<uint4*>(const_cast<uint16_t*>(vb) + rr * a.sv[2]) = vr[u];
+          *reinterpret_cast<Row*>(const_cast<Elt*>(kb) + rr * a.sk[2]) = kr[u];
+          *reinterpret_cast<Row*>(const_cast<Elt*>(vb) + rr * a.sv[2]) = vr[u];
         }
       } else if (ok[u]) {
-        kr[u] = *reinterpret_cast<const uint4*>(kb + rr * a.sk[2]);
-        vr[u] = *reinterpret_cast<const uint4*>(vb + rr * a.sv[2]);
+        kr[u] = *reinterpret_cast<const Row*>(kb + rr * a.sk[2]);
+        vr[u] = *reinterpret_cast<const Row*>(vb + rr * a.sv[2]);
       }
     }
     // from here on: GB copies of one head's arithmetic on the same rows
@@ -245,7 +288,8 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
 #pragma unroll
     for (int u = 0; u < kUnroll; ++u) {
       float kf[8];
-      unpack8(kr[u], kf);
+      if constexpr (FP8) fp8_unpack8(kr[u], kf);
+      else unpack8(kr[u], kf);
 #pragma unroll
       for (int j = 0; j < GB; ++j) {
         float d = 0.f;
@@ -271,7 +315,8 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
 #pragma unroll
     for (int u = 0; u < kUnroll; ++u) {
       float vf[8];
-      unpack8(vr[u], vf);  // zeros where !ok
+      if constexpr (FP8) fp8_unpack8(vr[u], vf);
+      else unpack8(vr[u], vf);  // zeros where !ok
 #pragma unroll
       for (int j = 0; j < GB; ++j) {
         const float p = ok[u] ? __builtin_amdgcn_exp2f(s[j][u] - mn[j]) : 0.f;
@@ -301,6 +346,10 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
 #pragma unroll
       for (int i = 0; i < 8; ++i) acc[j][i] += __shfl_xor(acc[j][i], o, 64);
     }
+    if constexpr (FP8) {  // P.V ran on the unscaled codes
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc[j][i] *= a.vscale;
+    }
     if (FUSED && a.nchunks == 1) {  // what attn_decode_merge_k computes from this one partial
       if (g == 0) {
         const float f = __builtin_amdgcn_exp2f(M - M);
@@ -325,14 +374,14 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
   }
 }
 
-template <int GB, bool WIN, bool RING = false>
+template <int GB, bool WIN, bool RING = false, bool FP8 = false>
 __global__ __launch_bounds__(64) void attn_decode_split_k(AttnDecodeArgs a) {
-  attn_decode_split_body<false, GB, WIN, RING>(a, AttnNewRow{nullptr, nullptr, 0});
+  attn_decode_split_body<false, GB, WIN, RING, FP8>(a, AttnNewRow{nullptr, nullptr, 0});
 }
 
-template <int GB, bool WIN, bool RING = false>
+template <int GB, bool WIN, bool RING = false, bool FP8 = false>
 __global__ __launch_bounds__(64) void attn_decode_append_split_k(AttnDecodeArgs a, AttnNewRow n) {
-  attn_decode_split_body<true, GB, WIN, RING>(a, n);
+  attn_decode_split_body<true, GB, WIN, RING, FP8>(a, n);
 }
 
 // grid: B * H one-wave workgroups; lane = output dim
@@ -384,8 +433,14 @@ void attn_kv_append(const AttnAppendArgs& a, hipStream_t st) {
   const int64_t total = (int64_t)a.B * a.T * 2 * a.Hkv * 8;
   if (total == 0) return;
   const dim3 grid((unsigned)((total + 255) / 256));
-  if (a.ring) hipLaunchKernelGGL(attn_kv_append_k<true>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(attn_kv_append_k<false>, grid, dim3(256), 0, st, a);
+  if (a.fp8) {
+    if (a.ring) hipLaunchKernelGGL((attn_kv_append_k<true, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((attn_kv_append_k<false, true>), grid, dim3(256), 0, st, a);
+  } else if (a.ring) {
+    hipLaunchKernelGGL(attn_kv_append_k<true>, grid, dim3(256), 0, st, a);
+  } else {
+    hipLaunchKernelGGL(attn_kv_append_k<false>, grid, dim3(256), 0, st, a);
+  }
 }
 
 // Query heads per wave.  A head block of GB loads a K / V row G / GB times instead of G times, and
@@ -432,24 +487,25 @@ static int decode_plan(AttnDecodeArgs& a) {
   return gb;
 }
 
-// the split launch for head block gb; WIN: the windowed instantiations, RING: the rolling ones
-template <bool WIN, bool RING = false>
+// the split launch for head block gb; WIN: the windowed instantiations, RING: the rolling ones, FP8: the
+// e4m3-cache ones
+template <bool WIN, bool RING = false, bool FP8 = false>
 static void launch_split(int gb, dim3 grid, const AttnDecodeArgs& a, hipStream_t st) {
   switch (gb) {
-    case 1: hipLaunchKernelGGL((attn_decode_split_k<1, WIN, RING>), grid, dim3(64), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((attn_decode_split_k<2, WIN, RING>), grid, dim3(64), 0, st, a); break;
-    case 3: hipLaunchKernelGGL((attn_decode_split_k<3, WIN, RING>), grid, dim3(64), 0, st, a); break;
-    default: hipLaunchKernelGGL((attn_decode_split_k<4, WIN, RING>), grid, dim3(64), 0, st, a); break;
+    case 1: hipLaunchKernelGGL((attn_decode_split_k<1, WIN, RING, FP8>), grid, dim3(64), 0, st, a); break;
+    case 2: hipLaunchKernelGGL((attn_decode_split_k<2, WIN, RING, FP8>), grid, dim3(64), 0, st, a); break;
+    case 3: hipLaunchKernelGGL((attn_decode_split_k<3, WIN, RING, FP8>), grid, dim3(64), 0, st, a); break;
+    default: hipLaunchKernelGGL((attn_decode_split_k<4, WIN, RING, FP8>), grid, dim3(64), 0, st, a); break;
   }
 }
 
-template <bool WIN, bool RING = false>
+template <bool WIN, bool RING = false, bool FP8 = false>
 static void launch_append_split(int gb, dim3 grid, const AttnDecodeArgs& a, const AttnNewRow& n, hipStream_t st) {
   switch (gb) {
-    case 1: hipLaunchKernelGGL((attn_decode_append_split_k<1, WIN, RING>), grid, dim3(64), 0, st, a, n); break;
-    case 2: hipLaunchKernelGGL((attn_decode_append_split_k<2, WIN, RING>), grid, dim3(64), 0, st, a, n); break;
-    case 3: hipLaunchKernelGGL((attn_decode_append_split_k<3, WIN, RING>), grid, dim3(64), 0, st, a, n); break;
-    default: hipLaunchKernelGGL((attn_decode_append_split_k<4, WIN, RING>), grid, dim3(64), 0, st, a, n); break;
+    case 1: hipLaunchKernelGGL((attn_decode_append_split_k<1, WIN, RING, FP8>), grid, dim3(64), 0, st, a, n); break;
+    case 2: hipLaunchKernelGGL((attn_decode_append_split_k<2, WIN, RING, FP8>), grid, dim3(64), 0, st, a, n); break;
+    case 3: hipLaunchKernelGGL((attn_decode_append_split_k<3, WIN, RING, FP8>), grid, dim3(64), 0, st, a, n); break;
+    default: hipLaunchKernelGGL((attn_decode_append_split_k<4, WIN, RING, FP8>), grid, dim3(64), 0, st, a, n); break;
   }
 }
 
@@ -457,7 +513,11 @@ void attn_decode(const AttnDecodeArgs& a_, hipStream_t st) {
   AttnDecodeArgs a = a_;
   const int gb = decode_plan(a);
   const dim3 grid(a.nparts / gb);  // B * Hkv * nblk * nchunks
-  if (a.ring) launch_split<true, true>(gb, grid, a, st);
+  if (a.fp8) {
+    if (a.ring) launch_split<true, true, true>(gb, grid, a, st);
+    else if (a.window > 0) launch_split<true, false, true>(gb, grid, a, st);
+    else launch_split<false, false, true>(gb, grid, a, st);
+  } else if (a.ring) launch_split<true, true>(gb, grid, a, st);
   else if (a.window > 0) launch_split<true>(gb, grid, a, st);
   else launch_split<false>(gb, grid, a, st);
   hipLaunchKernelGGL(attn_decode_merge_k, dim3(a.B * a.H), dim3(64), 0, st, a);
@@ -470,7 +530,11 @@ void attn_decode_append(const AttnDecodeArgs& a_, const uint16_t* nk, const uint
   const int gb = decode_plan(a);
   const dim3 grid(a.nparts / gb);
   const AttnNewRow n{nk, nv, snew};
-  if (a.ring) launch_append_split<true, true>(gb, grid, a, n, st);
+  if (a.fp8) {
+    if (a.ring) launch_append_split<true, true, true>(gb, grid, a, n, st);
+    else if (a.window > 0) launch_append_split<true, false, true>(gb, grid, a, n, st);
+    else launch_append_split<false, false, true>(gb, grid, a, n, st);
+  } else if (a.ring) launch_append_split<true, true>(gb, grid, a, n, st);
   else if (a.window > 0) launch_append_split<true>(gb, grid, a, n, st);
   else launch_append_split<false>(gb, grid, a, n, st);
   if (a.nchunks > 1) hipLaunchKernelGGL(attn_decode_merge_k, dim3(a.B * a.H), dim3(64), 0, st, a);

@@ -91,6 +91,19 @@
 // means the row of token T - 1 replaced logical row pos + T - 1 - R <= pos - W, below the first query's
 // lower limit pos + 1 - W.  Rows past the position (pad tokens of a ragged extend, rejected rows of a
 // speculative round) are read as logical row pos + t - R by the same inequality: no later query sees it.
+//
+// FP8 cache (AttnExtendArgs::fp8, a host value; csrc/attn_fp8.h): the caches hold OCP e4m3 codes, 64 B a row,
+// strides in bytes.  A lane's K fragment is an 8-B load converted to bf16x8 (v_cvt_pk_f32_fp8, then the upper
+// halves: exact, a code has 4 significant bits), so the MFMA operands ARE the dequantised codes; the score factor
+// carries k_scale (a.scale, an f32 product on the host).  V cannot take the direct global->LDS path, which moves
+// 16 B of bf16: a lane loads 8 x 8 B of codes into registers (a wave load is 8 rows x 64 B), converts them and
+// writes the same swizzled bf16 tile, so tr_frag and P.V are untouched.  The double buffering stays: the K
+// fragments and V codes of tile i + 1 are in flight during tile i's products, and tile i's codes are converted
+// and written to its LDS buffer at the top of its iteration, ahead of the barrier.  Hidden rows are decided by the
+// predicates above (RowsLoaded) and become the zero code without forming an address.  The accumulator is
+// multiplied by vscale once, before the store or the partial; the merge kernel is unchanged.  FP8 is a template
+// parameter next to WIN and RING: bf16 caches take the instantiations that existed (profiles/kv_fp8/resources.txt).
+#include "attn_fp8.h"
 #include "attn_ring.h"
 #include "common.h"
 #include "mfma_tile.h"
@@ -190,8 +203,56 @@ __device__ __forceinline__ void stage_v_ring(uint4* tile, const uint16_t* vb, in
     }
 }
 
+// FP8 cache (csrc/attn_fp8.h): a row is 64 codes.  Which rows a wave loads is decided exactly as above --
+// by [lo, hi) (lo = the split's start without a window) or by RingTile -- through one predicate:
+struct RowsLoaded {
+  bool win, ring;
+  int lo, hi;
+  RingTile rt;
+  __device__ __forceinline__ bool operator()(int r) const { return ring ? rt.loads(r) : (r < hi && (!win || r >= lo)); }
+  __device__ __forceinline__ int first() const { return ring ? rt.start : lo; }  // what a hidden row's index becomes
+};
+
+// load_k on codes: a lane's 8 B of a key row, converted (exactly) to the bf16x8 fragment the MFMA takes
+__device__ __forceinline__ void load_k_fp8(bf16x8_t (&kf)[4][2], const uint8_t* kb, int64_t rs, int k0,
+                                           const RowsLoaded& see, int fr, int fg) {
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) {
+    const int r = k0 + 16 * mt + fr;
+    const bool ok = see(r);
+    const int rr = ok ? r : see.first();  // a hidden row never forms an address
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      uint2 c = make_uint2(0, 0);  // the code of +0: a zero fragment
+      if (ok) c = *reinterpret_cast<const uint2*>(kb + rr * rs + 32 * ks + 8 * fg);
+      kf[mt][ks] = __builtin_bit_cast(bf16x8_t, fp8_to_bf16x8(c));
+    }
+  }
+}
+
+// V rows k0 .. k0 + 63 as codes into registers: pass j holds row 8 j + (lane >> 3), dims 8 (lane & 7) .. + 7
+// (a wave load is 8 rows x 64 B); hidden rows are the zero code and form no address
+__device__ __forceinline__ void load_v_fp8(uint2 (&vn)[8], const uint8_t* vb, int64_t rs, int k0,
+                                           const RowsLoaded& see, int lane) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int r = k0 + 8 * j + (lane >> 3);
+    vn[j] = make_uint2(0, 0);
+    if (see(r)) vn[j] = *reinterpret_cast<const uint2*>(vb + (int64_t)r * rs + (lane & 7) * 8);
+  }
+}
+
+// ... and from there to the swizzled bf16 tile stage_tile would have filled: chunk c of row r at c ^ aswz(r)
+__device__ __forceinline__ void store_v_fp8(uint4* tile, const uint2 (&vn)[8], int lane) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int row = 8 * j + (lane >> 3);
+    tile[row * 8 + ((lane & 7) ^ aswz(row))] = fp8_to_bf16x8(vn[j]);
+  }
+}
+
 // grid: B * H * nqt * nsplit one-wave workgroups, split fastest
-template <bool WIN, bool RING = false>
+template <bool WIN, bool RING = false, bool FP8 = false>
 __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
   __shared__ __attribute__((aligned(16))) uint4 lds[2 * kTileU4];  // V, double buffered: 16 KiB
   const int lane = threadIdx.x;
@@ -269,7 +330,17 @@ __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
   // tiles run from the 64-row tile of the split that holds lo (start itself without a window)
   // (a ring hides at most R - W slots: its tiles run from the split's start)
   const int kbeg = WIN && !RING ? start + (lo - start) / kTile * kTile : start;
-  if constexpr (RING) {
+  // FP8: K fragments and V codes of tile i + 1 are loaded into registers ahead of tile i's products (the
+  // double buffering of the bf16 path, in registers where that one's V goes straight to LDS); tile i's V
+  // codes are converted and written to its LDS buffer at the top of its iteration
+  [[maybe_unused]] uint2 vn[8];
+  [[maybe_unused]] const RowsLoaded see{WIN, RING, lo, hi, rt};
+  [[maybe_unused]] const uint8_t* kb8 = reinterpret_cast<const uint8_t*>(a.k) + b * a.sk[0] + hk * a.sk[1];
+  [[maybe_unused]] const uint8_t* vb8 = reinterpret_cast<const uint8_t*>(a.v) + b * a.sv[0] + hk * a.sv[1];
+  if constexpr (FP8) {
+    load_k_fp8(kn, kb8, a.sk[2], kbeg, see, fr, fg);
+    load_v_fp8(vn, vb8, a.sv[2], kbeg, see, lane);
+  } else if constexpr (RING) {
     load_k_ring(kn, kb, a.sk[2], kbeg, rt, fr, fg);
     stage_v_ring(lds, vb, a.sv[2], kbeg, rt, lane);
   } else {
@@ -278,7 +349,8 @@ __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
   }
   int buf = 0;
   for (int k0 = kbeg; k0 < hi; k0 += kTile, buf ^= 1) {
-    wait_loads();
+    if constexpr (FP8) store_v_fp8(lds + buf * kTileU4, vn, lane);  // the buffer's last reads: two tiles ago
+    else wait_loads();
     __syncthreads();  // tile k0 landed (registers and LDS); the other buffer's reads are done
     bf16x8_t kf[4][2];
 #pragma unroll
@@ -286,7 +358,10 @@ __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) kf[mt][ks] = kn[mt][ks];
     if (k0 + kTile < hi) {
-      if constexpr (RING) {
+      if constexpr (FP8) {
+        load_k_fp8(kn, kb8, a.sk[2], k0 + kTile, see, fr, fg);
+        load_v_fp8(vn, vb8, a.sv[2], k0 + kTile, see, lane);
+      } else if constexpr (RING) {
         load_k_ring(kn, kb, a.sk[2], k0 + kTile, rt, fr, fg);
         stage_v_ring(lds + (buf ^ 1) * kTileU4, vb, a.sv[2], k0 + kTile, rt, lane);
       } else {
@@ -355,6 +430,10 @@ __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
   l += __shfl_xor(l, 16, 64);
   l += __shfl_xor(l, 32, 64);
   // acc[dt][i] = Oᵀ[16 dt + 4 fg + i][fr]
+  if constexpr (FP8) {  // P.V ran on the unscaled codes
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) acc[dt] *= a.vscale;
+  }
   if (a.nsplit == 1) {
     if (qreal) {  // the one split holds row L(b, t) - 1: l > 0
       const float inv = 1.f / l;
@@ -459,6 +538,9 @@ void attn_extend(const AttnExtendArgs& a_, hipStream_t st) {
   a.group = a.H / a.Hkv;
   auto* split = a.ring ? attn_extend_split_k<true, true>
                        : (a.window > 0 ? attn_extend_split_k<true> : attn_extend_split_k<false>);
+  if (a.fp8)
+    split = a.ring ? attn_extend_split_k<true, true, true>
+                   : (a.window > 0 ? attn_extend_split_k<true, false, true> : attn_extend_split_k<false, false, true>);
   hipLaunchKernelGGL(split, dim3(a.nparts), dim3(64), 0, st, a);
   if (a.nsplit > 1) hipLaunchKernelGGL(attn_extend_merge_k, dim3(a.B * a.T * a.H), dim3(64), 0, st, a);
 }

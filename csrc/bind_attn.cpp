@@ -1,5 +1,7 @@
 // Bindings of the attention kernels (attention.hip, attention_decode.hip, attention_extend.hip), of
 // the rotary position embedding (rope.hip) and of the few-row decode products (rows_gemm.hip).
+#include <cmath>
+
 #include "bind_common.h"
 
 namespace {
@@ -117,8 +119,42 @@ void attn_backward(const Tensor& q, const Tensor& k, const Tensor& v, const Tens
 // kv_heads (trailing, 0 = heads) is grouped-query attention: it must divide heads, the cache must
 // have that many heads and a packed row is (H + 2*Hkv)*64 wide (bind_common.h).  window (trailing, 0 =
 // none): the sliding window of the decode / extend kernels; one that can hide nothing (>= cap) is none.
+// k_scale / v_scale (trailing, 1.0): the scales of an fp8 cache pair -- both caches float8_e4m3fn (csrc/attn_fp8.h);
+// with bf16 caches they must stay 1.0.  The workspaces and the grids do not depend on the cache's type.
 // rolling (trailing, false = the linear cache): the cache is a ring (bind_common.h ring_window): the window
 // is required, kept as given, and lengths / positions are not clamped to the cache's rows.
+// A cache tensor of a decode / extend call: bf16 (attn_view) or, with fp8, float8_e4m3fn codes [B, Hkv, cap, 64]
+// with a unit last stride, the other strides multiples of 16 bytes and a 16-B aligned base (the conditions of
+// attn_view, in bytes).  The strides returned count elements of the cache's own type.
+void cache_view(const Tensor& t, const char* name, int64_t B, int64_t H, int64_t N, bool fp8, const uint16_t** p,
+                int64_t* s) {
+  if (!fp8) return attn_view(t, name, B, H, N, p, s);
+  check_cuda(t, name);
+  TORCH_CHECK(t.scalar_type() == at::kFloat8_e4m3fn && t.dim() == 4, "attention: ", name,
+              " must be float8_e4m3fn [B, H, N, D] like the other cache");
+  TORCH_CHECK(t.size(0) == B && t.size(1) == H && t.size(2) == N && t.size(3) == 64 && t.stride(3) == 1,
+              "attention: ", name, " shape/stride mismatch (head dim 64, unit stride)");
+  for (int i = 0; i < 3; ++i) {
+    TORCH_CHECK(t.stride(i) % 16 == 0 || t.size(i) == 1, "attention: ", name, " strides must be multiples of 16");
+    s[i] = t.stride(i);
+  }
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, "attention: ", name, " not 16-B aligned");
+  *p = reinterpret_cast<const uint16_t*>(t.data_ptr());
+}
+
+// Is the cache pair fp8?  Both float8_e4m3fn: yes, and the two scales must be finite and > 0; otherwise the
+// scales must be the defaults (a bf16 pair has none) and attn_view rejects anything that is not bf16.
+bool cache_fp8(const Tensor& k_cache, const Tensor& v_cache, double k_scale, double v_scale, const char* what) {
+  const bool fp8 = k_cache.scalar_type() == at::kFloat8_e4m3fn && v_cache.scalar_type() == at::kFloat8_e4m3fn;
+  if (fp8) {
+    TORCH_CHECK(std::isfinite(k_scale) && k_scale > 0 && std::isfinite(v_scale) && v_scale > 0, what,
+                ": the scales of an fp8 cache must be finite and > 0");
+  } else {
+    TORCH_CHECK(k_scale == 1.0 && v_scale == 1.0, what, ": k_scale / v_scale need float8_e4m3fn caches");
+  }
+  return fp8;
+}
+
 int cache_window(int64_t window, int64_t cap, const char* what) {
   TORCH_CHECK(window >= 0, what, ": window must be >= 1 (0: none)");
   return window < cap ? (int)window : 0;
@@ -145,8 +181,10 @@ const uint16_t* packed_qkv(const Tensor& t, int64_t B, int64_t H, int64_t Hkv, c
 }
 
 void attn_kv_append(const Tensor& qkv, int64_t heads, const Tensor& k_cache, const Tensor& v_cache,
-                    const Tensor& positions, int64_t kv_heads, bool rolling, const optional<Tensor>& lengths) {
+                    const Tensor& positions, int64_t kv_heads, bool rolling, const optional<Tensor>& lengths,
+                    double k_scale, double v_scale) {
   const at::DeviceGuard guard(k_cache.device());
+  const bool fp8 = cache_fp8(k_cache, v_cache, k_scale, v_scale, "attention decode");
   TORCH_CHECK(rolling || !given(lengths), "attention decode: append lengths need a rolling cache");
   const int64_t Hkv = kv_heads_of(heads, kv_heads, "attention decode");
   check_kv_cache(k_cache, Hkv, "attention decode");
@@ -158,10 +196,11 @@ void attn_kv_append(const Tensor& qkv, int64_t heads, const Tensor& k_cache, con
   tbamd::AttnAppendArgs a{};
   a.qkv = packed_qkv(qkv, B, H, Hkv, k_cache, a.sqkv);
   const uint16_t* p;
-  attn_view(k_cache, "k_cache", B, Hkv, cap, &p, a.sk);
+  cache_view(k_cache, "k_cache", B, Hkv, cap, fp8, &p, a.sk);
   a.kc = const_cast<uint16_t*>(p);
-  attn_view(v_cache, "v_cache", B, Hkv, cap, &p, a.sv);
+  cache_view(v_cache, "v_cache", B, Hkv, cap, fp8, &p, a.sv);
   a.vc = const_cast<uint16_t*>(p);
+  if (fp8) a.fp8 = 1, a.kinv = (float)(1.0 / k_scale), a.vinv = (float)(1.0 / v_scale);
   TORCH_CHECK(v_cache.device() == k_cache.device(), "attention decode: caches on different devices");
   a.pos = decode_lengths(positions, "positions", k_cache, B);
   a.B = (int)B, a.T = (int)T, a.H = (int)H, a.Hkv = (int)Hkv, a.cap = (int)cap;
@@ -175,8 +214,10 @@ void attn_kv_append(const Tensor& qkv, int64_t heads, const Tensor& k_cache, con
 // lengths and the output o [B, H*64], which is returned.  qkv: the packed [B, 1, (H + 2*Hkv)*64] whose q
 // part is read in place (a.sq[0] is its batch stride); null leaves a.q / a.sq to the caller.  a.ws too.
 Tensor decode_args(tbamd::AttnDecodeArgs& a, const Tensor* qkv, int64_t H, int64_t Hkv, const Tensor& k_cache,
-                   const Tensor& v_cache, const Tensor& lengths, const char* lengths_name, int64_t add, double scale) {
+                   const Tensor& v_cache, const Tensor& lengths, const char* lengths_name, int64_t add, double scale,
+                   double k_scale, double v_scale) {
   check_kv_cache(k_cache, Hkv, "attention decode");
+  const bool fp8 = cache_fp8(k_cache, v_cache, k_scale, v_scale, "attention decode");
   const int64_t B = k_cache.size(0), cap = k_cache.size(2);
   TORCH_CHECK(B >= 1 && cap >= 1 && cap < (int64_t)INT32_MAX / 2 && add >= -cap && add <= cap,
               "attention decode: bad size");
@@ -187,14 +228,18 @@ Tensor decode_args(tbamd::AttnDecodeArgs& a, const Tensor* qkv, int64_t H, int64
     a.q = packed_qkv(*qkv, B, H, Hkv, k_cache, a.sq);
     a.sq[1] = 64;  // from head to head, not packed_qkv's token stride
   }
-  attn_view(k_cache, "k_cache", B, Hkv, cap, &a.k, a.sk);
-  attn_view(v_cache, "v_cache", B, Hkv, cap, &a.v, a.sv);
+  cache_view(k_cache, "k_cache", B, Hkv, cap, fp8, &a.k, a.sk);
+  cache_view(v_cache, "v_cache", B, Hkv, cap, fp8, &a.v, a.sv);
   TORCH_CHECK(v_cache.device() == k_cache.device(), "attention decode: caches on different devices");
   a.klen = decode_lengths(lengths, lengths_name, k_cache, B);
-  Tensor o = at::empty({B, H * 64}, k_cache.options());
+  Tensor o = at::empty({B, H * 64}, k_cache.options().dtype(at::kBFloat16));
   a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
   a.so[0] = H * 64, a.so[1] = 64;
   a.B = (int)B, a.H = (int)H, a.Hkv = (int)Hkv, a.cap = (int)cap, a.add = (int)add, a.scale = (float)scale;
+  if (fp8) {  // k_scale rides in the score factor: one f32 product here
+    a.fp8 = 1, a.scale = (float)scale * (float)k_scale, a.vscale = (float)v_scale;
+    a.kinv = (float)(1.0 / k_scale), a.vinv = (float)(1.0 / v_scale);
+  }
   return o;
 }
 
@@ -203,12 +248,13 @@ Tensor decode_args(tbamd::AttnDecodeArgs& a, const Tensor* qkv, int64_t H, int64
 // at least attn_decode_workspace floats; by default it comes from the caching allocator.
 Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const Tensor& v_cache, const Tensor& lengths,
                    int64_t add, double scale, const optional<Tensor>& workspace, int64_t kv_heads, int64_t window,
-                   bool rolling) {
+                   bool rolling, double k_scale, double v_scale) {
   const at::DeviceGuard guard(k_cache.device());
   const int64_t H = heads, Hkv = kv_heads_of(heads, kv_heads, "attention decode");
   const bool packed = q.dim() == 3 && q.size(1) == 1 && q.size(2) == packed_qkv_width(H, Hkv);
   tbamd::AttnDecodeArgs a{};
-  Tensor o = decode_args(a, packed ? &q : nullptr, H, Hkv, k_cache, v_cache, lengths, "lengths", add, scale);
+  Tensor o = decode_args(a, packed ? &q : nullptr, H, Hkv, k_cache, v_cache, lengths, "lengths", add, scale, k_scale,
+                         v_scale);
   if (!packed) {
     check_cuda(q, "q");
     TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.dim() == 3 && q.size(0) == a.B && q.size(1) == H &&
@@ -229,11 +275,12 @@ Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const 
 // cache row positions[b] (dropped outside [0, cap)) and the query sees rows j <= positions[b] ->
 // o [B, H*64].  Same bits, output and caches, as attn_kv_append followed by attn_decode(add = 1).
 Tensor attn_decode_append(const Tensor& qkv, int64_t heads, const Tensor& k_cache, const Tensor& v_cache,
-                          const Tensor& positions, double scale, int64_t kv_heads, int64_t window, bool rolling) {
+                          const Tensor& positions, double scale, int64_t kv_heads, int64_t window, bool rolling,
+                          double k_scale, double v_scale) {
   const at::DeviceGuard guard(k_cache.device());
   const int64_t H = heads, Hkv = kv_heads_of(heads, kv_heads, "attention decode");
   tbamd::AttnDecodeArgs a{};
-  Tensor o = decode_args(a, &qkv, H, Hkv, k_cache, v_cache, positions, "positions", 1, scale);
+  Tensor o = decode_args(a, &qkv, H, Hkv, k_cache, v_cache, positions, "positions", 1, scale, k_scale, v_scale);
   a.ring = rolling ? 1 : 0;
   a.window = rolling ? ring_window(window, a.cap, 1, "attention decode") : cache_window(window, a.cap, "attention decode");
   Tensor ws;  // a single chunk is normalised in the split kernel: no partials
@@ -414,9 +461,11 @@ Tensor rope_packed(const Tensor& qkv, int64_t heads, const Tensor& table, const 
 // workspace (optional, tests): f32, at least attn_extend_workspace floats; by default it comes
 // from the caching allocator (none at all with a single key split).
 Tensor attn_extend(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& positions,
-                   double scale, const optional<Tensor>& workspace, int64_t kv_heads, int64_t window, bool rolling) {
+                   double scale, const optional<Tensor>& workspace, int64_t kv_heads, int64_t window, bool rolling,
+                   double k_scale, double v_scale) {
   const at::DeviceGuard guard(k_cache.device());
   TORCH_CHECK(k_cache.dim() == 4, "attention extend: cache must be [B, H, cap, 64]");
+  const bool fp8 = cache_fp8(k_cache, v_cache, k_scale, v_scale, "attention extend");
   const int64_t B = k_cache.size(0), cap = k_cache.size(2);
   check_cuda(q, "q");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.dim() == 4 && q.size(0) == B && q.size(2) >= 1 &&
@@ -431,8 +480,8 @@ Tensor attn_extend(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache
   TORCH_CHECK(q.device() == k_cache.device(), "attention extend: q must be on the device of the cache");
   tbamd::AttnExtendArgs a{};
   a.q = aligned_rows(q, 3, a.sq, "attention extend", "q");
-  attn_view(k_cache, "k_cache", B, Hkv, cap, &a.k, a.sk);
-  attn_view(v_cache, "v_cache", B, Hkv, cap, &a.v, a.sv);
+  cache_view(k_cache, "k_cache", B, Hkv, cap, fp8, &a.k, a.sk);
+  cache_view(v_cache, "v_cache", B, Hkv, cap, fp8, &a.v, a.sv);
   TORCH_CHECK(v_cache.device() == k_cache.device(), "attention extend: caches on different devices");
   a.pos = decode_lengths(positions, "positions", k_cache, B);
   // the split kernel's grid (one workgroup per partial) and the merge kernel's (one per output row)
@@ -443,11 +492,12 @@ Tensor attn_extend(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache
               "attention extend: bad size");
   const int64_t need = tbamd::attn_extend_workspace((int)B, (int)H, (int)T, (int)cap);
   Tensor ws = workspace_or_new(workspace, need, k_cache, "attention extend");
-  Tensor o = at::empty({B, T, H * 64}, k_cache.options());
+  Tensor o = at::empty({B, T, H * 64}, k_cache.options().dtype(at::kBFloat16));
   a.o = reinterpret_cast<uint16_t*>(o.data_ptr());
   a.so[0] = T * H * 64, a.so[1] = H * 64;
   a.ws = need > 0 ? ws.data_ptr<float>() : nullptr;
   a.B = (int)B, a.T = (int)T, a.H = (int)H, a.Hkv = (int)Hkv, a.cap = (int)cap, a.scale = (float)scale;
+  if (fp8) a.fp8 = 1, a.scale = (float)scale * (float)k_scale, a.vscale = (float)v_scale;
   a.ring = rolling ? 1 : 0;
   a.window = rolling ? ring_window(window, cap, T, "attention extend") : cache_window(window, cap, "attention extend");
   tbamd::attn_extend(a, cur_stream());
@@ -463,13 +513,15 @@ void register_attn(pybind11::module& m) {
         py::arg("lse"), py::arg("scale"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("causal") = false,
         py::arg("key_lengths") = py::none(), py::arg("window") = 0);
   m.def("attn_kv_append", &attn_kv_append, py::arg("qkv"), py::arg("heads"), py::arg("k_cache"), py::arg("v_cache"),
-        py::arg("positions"), py::arg("kv_heads") = 0, py::arg("rolling") = false, py::arg("lengths") = py::none());
+        py::arg("positions"), py::arg("kv_heads") = 0, py::arg("rolling") = false, py::arg("lengths") = py::none(),
+        py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0);
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("heads"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("lengths"), py::arg("add"), py::arg("scale"), py::arg("workspace") = py::none(),
-        py::arg("kv_heads") = 0, py::arg("window") = 0, py::arg("rolling") = false);
+        py::arg("kv_heads") = 0, py::arg("window") = 0, py::arg("rolling") = false, py::arg("k_scale") = 1.0,
+        py::arg("v_scale") = 1.0);
   m.def("attn_decode_append", &attn_decode_append, py::arg("qkv"), py::arg("heads"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("positions"), py::arg("scale"), py::arg("kv_heads") = 0, py::arg("window") = 0,
-        py::arg("rolling") = false);
+        py::arg("rolling") = false, py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0);
   m.def("rows_linear", &rows_linear, py::arg("x"), py::arg("weight"), py::arg("bias") = py::none(),
         py::arg("gamma") = py::none(), py::arg("beta") = py::none(), py::arg("eps") = 0.0, py::arg("epi") = 0,
         py::arg("residual") = py::none(), py::arg("out") = py::none(), py::arg("rms") = false);
@@ -485,7 +537,7 @@ void register_attn(pybind11::module& m) {
         py::arg("out") = py::none());
   m.def("attn_extend", &attn_extend, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("positions"),
         py::arg("scale"), py::arg("workspace") = py::none(), py::arg("kv_heads") = 0, py::arg("window") = 0,
-        py::arg("rolling") = false);
+        py::arg("rolling") = false, py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0);
   // knobs and workspace sizes
   m.def("attn_set_head_mask", [](int64_t m) { return (int64_t)tbamd::attn_set_head_mask((int)m); });
   m.def("attn_decode_workspace", [](int64_t B, int64_t H, int64_t cap) {

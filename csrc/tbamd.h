@@ -307,6 +307,10 @@ struct AttnAppendArgs {
   // int32 in device memory or null; only read with ring.
   const int* len;
   int ring;
+  // fp8 cache (fp8 != 0; csrc/attn_fp8.h): kc / vc hold e4m3 codes, sk / sv count bytes, and a row is stored
+  // as rne_e4m3(clamp(f32(x) * kinv | vinv, -448, 448)); kinv / vinv = float32(1 / scale), from the host
+  int fp8;
+  float kinv, vinv;
 };
 void attn_kv_append(const AttnAppendArgs& a, hipStream_t st);
 // o[b][h][:] = softmax(q[b][h][:] . K[b][h / G][:len]^T * scale) . V[b][h / G][:len],
@@ -334,6 +338,11 @@ struct AttnDecodeArgs {
   // slots, len = max(klen[b] + add, 1) is NOT clamped to cap and slot p holds logical row j(p), the
   // largest j = p (mod cap) below len; the query sees the slots with max(0, len - window) <= j(p)
   int ring;
+  // fp8 cache (fp8 != 0; csrc/attn_fp8.h): k / v hold e4m3 codes and sk / sv count bytes; `scale` already
+  // carries k_scale (f32 product on the host) and the accumulator is multiplied by vscale before it is
+  // written.  kinv / vinv: the quantiser's factors for the row attn_decode_append takes from qkv.
+  int fp8;
+  float vscale, kinv, vinv;
 };
 // query heads per wave: 0 = the default policy (the largest of 4, 3, 2 that divides G and leaves the
 // grid enough waves, else 1: a function of B, H, Hkv, cap and the chunk size only), otherwise a
@@ -440,6 +449,10 @@ struct AttnExtendArgs {
   // L(b, t) = max(pos[b] + t + 1, 1) is NOT clamped to cap and slot p holds logical row j(p), the largest
   // j = p (mod cap) below L(b, T - 1); query t sees the slots with max(0, L(b, t) - window) <= j(p) < L(b, t)
   int ring;
+  // fp8 cache (fp8 != 0; csrc/attn_fp8.h): as AttnDecodeArgs -- codes, byte strides, k_scale inside `scale`,
+  // the accumulator times vscale before the store or the partial
+  int fp8;
+  float vscale;
 };
 // keys per split: 0 = the default policy (split only when B * H * ceil(T / 16) cannot occupy the
 // chip), otherwise a forced size (a multiple of 8, >= 8; at or above cap: one split); n < 0 only

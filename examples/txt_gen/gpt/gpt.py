@@ -49,6 +49,7 @@ class Config(BaseConfig):
     mlp: str = "gelu"  # "swiglu": the gated SiLU MLP
     window: int = 0  # > 0: sliding-window attention, a token sees itself and the window - 1 tokens before it
     rolling: bool = False  # the sample's KV cache keeps only about `window` rows per layer (needs window > 0)
+    kv_dtype: str = ""  # "fp8": the sample's KV cache holds e4m3 codes, scales calibrated on the prompt
 
 
 def load_bytes(path: str) -> torch.Tensor:
@@ -87,7 +88,12 @@ def main(conf: Config) -> None:
         prompt = list(conf.sample_prompt.encode())[:conf.seq_len - conf.sample_tokens] or [10]
         tokens = torch.tensor([prompt], dtype=torch.int64, device=data.device)
         model.eval()
-        out, _ = net.generate(tokens, conf.sample_tokens, **({"rolling": True} if conf.rolling else {}))
+        kw = {"rolling": True} if conf.rolling else {}
+        if conf.kv_dtype:
+            if conf.kv_dtype != "fp8":
+                raise ValueError(f"kv_dtype must be 'fp8' or empty, not {conf.kv_dtype!r}")
+            kw.update(kv_dtype=torch.float8_e4m3fn, kv_scales=gpt.kv_scales(net, tokens, margin=2.0))
+        out, _ = net.generate(tokens, conf.sample_tokens, **kw)
         text = bytes(prompt + out[0].tolist()).decode("utf-8", errors="replace")
         print(f"sample: {text!r}", flush=True)
     report_sync(model)

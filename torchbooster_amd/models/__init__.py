@@ -9,7 +9,7 @@ torchvision layout from stock modules + local pretrained weights: ``tv`` (``load
 """
 from torchbooster_amd.models import gpt
 from torchbooster_amd.models.dcgan import DCGANDiscriminator, DCGANGenerator, dcgan128
-from torchbooster_amd.models.gpt import KVCache, TransformerLM, gpt2_small, gpt_tiny
+from torchbooster_amd.models.gpt import KVCache, TransformerLM, gpt2_small, gpt_tiny, kv_scales
 from torchbooster_amd.models.resnet import ResNet, resnet18, resnet34, resnet50, resnet101, resnet152
 from torchbooster_amd.models.small import VAE, LeNet, MLPDiscriminator, MLPGenerator, lenet
 from torchbooster_amd.models.style import AdaINDecoder, StyleNet

@@ -78,6 +78,14 @@ longer than ``R`` keeps each sequence's last ``R`` valid rows; ``decode_step`` a
 ``lookahead`` tokens per call on such a cache (``ValueError`` beyond: a ring has room for ``R - W + 1`` new
 rows ahead of the first query; feeding more by chunking is left to the caller).  ``rolling=False`` (the
 default) is everything above unchanged.
+
+FP8 KV cache (``KVCache(..., dtype=torch.float8_e4m3fn, scales=None)``, ``generate(..., kv_dtype=, kv_scales=)``):
+the cache holds e4m3 codes, half the bytes of bf16, with two host floats ``(k_scale, v_scale)`` per layer
+(``cache.scales``; :func:`kv_scales` calibrates them on a prompt).  Rows are quantised as they are appended and
+every query sees them dequantised -- a step's own row included, so ``fused=True`` keeps the bits of ``fused=False`` --
+while ``prefill`` attends to its own unquantised projection (ops/attention.py states the rule).  It composes with
+``kv_heads``, ``window`` and ``rolling`` and with every ``generate`` option above; any other cache dtype adds nothing
+to any call.
 """
 from __future__ import annotations
 
@@ -87,10 +95,32 @@ import torch
 from torch import Tensor, nn
 
 from torchbooster_amd.models.vit import Block, Rope, make_norm, norm_args
+from torchbooster_amd.ops.attention import _check_scale
 from torchbooster_amd.ops.linear import Linear, embed_rows, linear_rows
 from torchbooster_amd.ops.loss import linear_cross_entropy
 
-__all__ = ["TransformerLM", "KVCache", "gpt_tiny", "gpt2_small"]
+__all__ = ["TransformerLM", "KVCache", "kv_scales", "gpt_tiny", "gpt2_small"]
+
+_FP8 = torch.float8_e4m3fn
+
+
+def _layer_scales(scales, depth: int) -> List[Tuple[float, float]]:
+    """``scales`` of :class:`KVCache` as ``depth`` checked ``(k_scale, v_scale)`` pairs."""
+    def pair(p) -> Tuple[float, float]:
+        try:
+            k, v = p
+        except (TypeError, ValueError):
+            raise ValueError(f"a KV-cache scale entry must be a (k_scale, v_scale) pair, not {p!r}") from None
+        return (_check_scale(k), _check_scale(v))
+
+    if scales is None:
+        return [(1.0, 1.0)] * depth
+    scales = list(scales)
+    if len(scales) == 2 and all(isinstance(x, (int, float)) for x in scales):
+        return [pair(scales)] * depth
+    if len(scales) != depth:
+        raise ValueError(f"scales has {len(scales)} entries, the model {depth} layers")
+    return [pair(p) for p in scales]
 
 
 class KVCache:
@@ -106,10 +136,16 @@ class KVCache:
     ``layers[i]`` a ``[B, kv_heads, R, hd]`` pair.  A layer without a window, or with ``R >= capacity``, is
     exactly the linear layer it is without ``rolling`` (``rolling[i]`` ``False``).  ``capacity`` keeps its
     meaning -- logical tokens, ``<= max_len`` -- and ``lookahead`` (>= 1) is the most tokens one ``extend``
-    may feed.  Bytes: ``sum_i 2 * B * kv_heads * rows_i * hd * itemsize``."""
+    may feed.  Bytes: ``sum_i 2 * B * kv_heads * rows_i * hd * itemsize``.
+
+    ``dtype=torch.float8_e4m3fn``: an fp8 cache (ops/attention.py: rows are quantised as they are appended and
+    every query sees them dequantised), half the bytes of bf16.  ``scales``: ``None`` (1.0 everywhere), one
+    ``(k_scale, v_scale)`` pair for every layer or a sequence of ``depth`` pairs (:func:`kv_scales` calibrates
+    them); host floats, finite and ``> 0``.  ``cache.scales`` is the list of ``depth`` pairs, or of ``depth``
+    ``None`` for any other dtype, with which ``scales`` raise ``ValueError``."""
 
     def __init__(self, model: "TransformerLM", batch: int, capacity: Optional[int] = None, dtype=None,
-                 device=None, *, rolling: bool = False, lookahead: int = 16) -> None:
+                 device=None, *, rolling: bool = False, lookahead: int = 16, scales=None) -> None:
         capacity = model.max_len if capacity is None else int(capacity)
         if not 1 <= capacity <= model.max_len:
             raise ValueError(f"capacity {capacity} must be in [1, max_len = {model.max_len}]")
@@ -119,6 +155,12 @@ class KVCache:
         w = model.tok.weight
         dtype = w.dtype if dtype is None else dtype
         device = w.device if device is None else device
+        if dtype == _FP8:
+            self.scales: List[Optional[Tuple[float, float]]] = _layer_scales(scales, len(model.blocks))
+        elif scales is not None:
+            raise ValueError(f"scales need dtype=torch.float8_e4m3fn, not {dtype}")
+        else:
+            self.scales = [None] * len(model.blocks)
         attn = model.blocks[0].attn
         self.capacity = capacity
         self.lookahead = lookahead
@@ -242,8 +284,11 @@ class TransformerLM(nn.Module):
             cache.positions.zero_()
             x, pending = self._embed(tokens), None
             # the masked self-attention plus one append per layer
-            for blk, kv, ring in zip(self.blocks, cache.layers, cache.rolling):
-                if ring:  # the ring append: the last R valid rows of each sequence
+            for blk, kv, ring, sc in zip(self.blocks, cache.layers, cache.rolling, cache.scales):
+                if sc is not None:  # an fp8 layer: the append quantises
+                    x, pending = blk(x, pending, lengths, cache=kv, positions=cache.positions,
+                                     **({"rolling": True} if ring else {}), kv_scales=sc)
+                elif ring:  # the ring append: the last R valid rows of each sequence
                     x, pending = blk(x, pending, lengths, cache=kv, positions=cache.positions, rolling=True)
                 else:
                     x, pending = blk(x, pending, lengths, cache=kv, positions=cache.positions)
@@ -302,8 +347,10 @@ class TransformerLM(nn.Module):
             else:
                 x = self._embed(tokens, cache.positions)
             pending = None
-            for blk, kv, ring in zip(self.blocks, cache.layers, cache.rolling):
+            for blk, kv, ring, sc in zip(self.blocks, cache.layers, cache.rolling, cache.scales):
                 rkw = {"rolling": True} if ring else {}  # a linear layer: the calls it always made
+                if sc is not None:  # an fp8 layer; any other: likewise
+                    rkw["kv_scales"] = sc
                 if fused:
                     x = blk.forward_rows(x, cache=kv, positions=cache.positions, extend=True, **rkw)
                 else:
@@ -346,14 +393,16 @@ class TransformerLM(nn.Module):
 
     def _speculative(self, tokens: Tensor, max_new_tokens: int, lengths: Optional[Tensor], eos: Optional[int],
                      draft: "TransformerLM", gamma: int, fused: bool = False,
-                     rolling: bool = False) -> Tuple[Tensor, Tensor]:
+                     rolling: bool = False, kv_dtype=None, kv_scales=None) -> Tuple[Tensor, Tensor]:
         """Greedy speculative decoding (``generate(draft=...)``)."""
         B, N = tokens.shape
         dev = tokens.device
         cap = N + max_new_tokens + gamma
         kw = {"fused": True} if fused else {}  # fused=False makes exactly the calls it always made
         rkw = {"rolling": True, "lookahead": max(16, gamma + 1)} if rolling else {}
-        tc, dc = KVCache(self, B, capacity=cap, **rkw), KVCache(draft, B, capacity=cap, **rkw)
+        dkw = {} if kv_dtype is None else {"dtype": kv_dtype}  # the draft's cache: the dtype, scales of 1
+        tkw = dict(dkw) if kv_scales is None else {**dkw, "scales": kv_scales}
+        tc, dc = KVCache(self, B, capacity=cap, **rkw, **tkw), KVCache(draft, B, capacity=cap, **rkw, **dkw)
         logits, _ = self.prefill(tokens, lengths, tc)
         draft.prefill(tokens, lengths, dc)
         # invariant at the top of a round: both caches hold the history up to, but not including, `cur`
@@ -393,7 +442,8 @@ class TransformerLM(nn.Module):
                  temperature: float = 0.0, top_k: Optional[int] = None, eos: Optional[int] = None,
                  generator=None, graph: bool = False, cache: Optional[KVCache] = None,
                  draft: Optional["TransformerLM"] = None, draft_tokens: int = 4,
-                 fused: bool = False, rolling: bool = False) -> Tuple[Tensor, Tensor]:
+                 fused: bool = False, rolling: bool = False, kv_dtype=None,
+                 kv_scales=None) -> Tuple[Tensor, Tensor]:
         """Continue the prompts ``tokens`` ``[B, N]`` (``lengths``: valid tokens of each, right-padded) by
         ``max_new_tokens`` tokens -> ``(out [B, max_new_tokens], out_lengths [B])``.
 
@@ -430,7 +480,12 @@ class TransformerLM(nn.Module):
         ``rolling=True``: the caches made here are rolling (:class:`KVCache`; with ``draft`` both, with
         ``lookahead=max(16, draft_tokens + 1)``).  A caller's ``cache`` is what it was built as -- a rolling one
         works with every option above; its ``tokens`` are fed through ``extend``, so at most
-        ``cache.lookahead`` of them per call.  The ``max_len`` checks stay as they are."""
+        ``cache.lookahead`` of them per call.  The ``max_len`` checks stay as they are.
+
+        ``kv_dtype`` / ``kv_scales``: the ``dtype`` and ``scales`` of the caches made here (:class:`KVCache`;
+        ``torch.float8_e4m3fn`` is the fp8 cache, ``kv_scales`` as its ``scales``).  With ``draft`` the draft's
+        cache gets ``kv_dtype`` and scales of 1.  A caller's ``cache`` brings its own and takes neither
+        (``ValueError``).  Works with ``graph=True``, ``fused=True`` and ``rolling=True``."""
         B, N = tokens.shape
         max_new_tokens = int(max_new_tokens)
         if max_new_tokens < 1:
@@ -452,12 +507,17 @@ class TransformerLM(nn.Module):
                 raise ValueError(f"prompt {N} + max_new_tokens {max_new_tokens} + draft_tokens {gamma} exceeds "
                                  f"max_len {min(self.max_len, draft.max_len)}")
             with torch.no_grad():
+                if kv_dtype is not None or kv_scales is not None:
+                    return self._speculative(tokens, max_new_tokens, lengths, eos, draft, gamma, fused, bool(rolling),
+                                             kv_dtype, kv_scales)
                 if rolling:
                     return self._speculative(tokens, max_new_tokens, lengths, eos, draft, gamma, fused, True)
                 return self._speculative(tokens, max_new_tokens, lengths, eos, draft, gamma, fused)
         start = None
         kw = {"fused": True} if fused else {}  # fused=False makes exactly the calls it always made
         if cache is not None:
+            if kv_dtype is not None or kv_scales is not None:
+                raise ValueError("kv_dtype / kv_scales are for the caches generate makes: a cache brings its own")
             if cache.positions.shape[0] != B:
                 raise ValueError(f"the cache holds {cache.positions.shape[0]} sequences, tokens {B}")
             held = int(cache.positions.max())
@@ -467,7 +527,12 @@ class TransformerLM(nn.Module):
         with torch.no_grad():
             dev = tokens.device
             if cache is None:
-                cache = KVCache(self, B, capacity=N + max_new_tokens, **({"rolling": True} if rolling else {}))
+                ckw = {"rolling": True} if rolling else {}
+                if kv_dtype is not None:
+                    ckw["dtype"] = kv_dtype
+                if kv_scales is not None:
+                    ckw["scales"] = kv_scales
+                cache = KVCache(self, B, capacity=N + max_new_tokens, **ckw)
                 logits, _ = self.prefill(tokens, lengths, cache)
             else:
                 logits = self.extend(tokens, cache, lengths, last_only=True, **kw)
@@ -510,6 +575,29 @@ class TransformerLM(nn.Module):
             if start is not None:  # a caller's cache: keep every emitted token but the last
                 cache.positions.copy_(start + (out_lengths - 1).to(torch.int32))
             return out, out_lengths
+
+
+def kv_scales(model: TransformerLM, tokens: Tensor, lengths: Optional[Tensor] = None, *,
+              margin: float = 1.0) -> List[Tuple[float, float]]:
+    """Calibrate the scales of an fp8 :class:`KVCache` on a prompt: one ``prefill`` of ``tokens`` ``[B, N]``
+    (``lengths``: the valid tokens of a right-padded batch) into a temporary cache of the model's dtype, then
+    per layer ``(amax_k / 448 * margin, amax_v / 448 * margin)`` with ``amax`` the largest magnitude over the
+    VALID cached rows -- pad rows do not count -- so those rows quantise without saturating (``margin > 1``
+    leaves headroom for later tokens).  A layer whose rows are all zero gets 1.0.  Reads the device once."""
+    margin = float(margin)
+    if not (margin > 0 and margin < float("inf")):
+        raise ValueError(f"margin must be a finite float > 0, not {margin!r}")
+    B, N = tokens.shape
+    with torch.no_grad():
+        _, cache = model.prefill(tokens, lengths, KVCache(model, B, capacity=N))
+        n = cache.positions.to(torch.int64)  # the clamped lengths
+        valid = torch.arange(N, device=n.device)[None, :] < n[:, None]  # [B, N]
+        amax = torch.stack([torch.stack([c.float().abs().amax(dim=(1, 3)).masked_fill(~valid, 0).max() for c in kv])
+                            for kv in cache.layers]).to(torch.float64)
+    out = []
+    for k, v in amax.tolist():  # the one host read
+        out.append(tuple(a / 448.0 * margin if a > 0 else 1.0 for a in (k, v)))
+    return out
 
 
 def gpt_tiny(vocab: int = 256, max_len: int = 128, pos: str = "learned", *, norm: str = "layer", mlp: str = "gelu",

@@ -121,7 +121,11 @@ class Attention(nn.Module):
     ``rolling`` (an argument of ``forward`` / ``cached``, not of the layer: it belongs to the cache; needs
     ``window``): ``cache`` is a rolling pair ``[B, kv_heads, R, hd]`` (ops/attention.py) -- the decode step and
     the extend pass ``rolling=True`` on, and the prefill's append becomes the ring append with
-    ``lengths=key_lengths``, which keeps the last ``R`` valid rows of each sequence."""
+    ``lengths=key_lengths``, which keeps the last ``R`` valid rows of each sequence.
+
+    ``kv_scales`` (likewise an argument of ``forward`` / ``cached``: the ``(k_scale, v_scale)`` of an fp8 cache
+    pair, ops/attention.py; ``None``: nothing is added to any call): passed to the append of a prefill and to
+    the decode step and the extend.  A prefill's own attention reads its unquantised ``qkv``."""
 
     def __init__(self, dim: int, heads: int, causal: bool = False, kv_heads: Optional[int] = None,
                  rope: Optional[Rope] = None, bias: bool = True, window: Optional[int] = None) -> None:
@@ -159,16 +163,19 @@ class Attention(nn.Module):
         return rope_packed(qkv, self.heads, self.rope.table(qkv), positions, kv_heads=self.kv_heads, inplace=inplace)
 
     def forward(self, x: Tensor, key_lengths: Optional[Tensor] = None, *, cache=None,
-                positions: Optional[Tensor] = None, extend: bool = False, rolling: bool = False) -> Tensor:
+                positions: Optional[Tensor] = None, extend: bool = False, rolling: bool = False,
+                kv_scales=None) -> Tensor:
         if cache is not None:
             rkw = {"rolling": True} if rolling else {}  # a linear cache: the call it always made
+            if kv_scales is not None:  # likewise a cache that is not fp8
+                rkw["kv_scales"] = kv_scales
             return self.proj(self.cached(self.qkv(x), cache, positions, key_lengths, extend=extend, **rkw))
         kw = self._kw()
         return self.proj(attention_packed(self.rotate(self.qkv(x)), self.heads, 1.0 / math.sqrt(self.hd),
                                           causal=self.causal, key_lengths=key_lengths, **kw))
 
     def cached(self, qkv: Tensor, cache, positions: Optional[Tensor], key_lengths: Optional[Tensor] = None, *,
-               extend: bool = False, fused: bool = False, rolling: bool = False) -> Tensor:
+               extend: bool = False, fused: bool = False, rolling: bool = False, kv_scales=None) -> Tensor:
         """The cached paths of the class docstring on the packed projection ``qkv`` ``[B, T, (H + 2*Hkv)*hd]``
         (rotated here, in place) -> ``[B, T, H*hd]``, the input of ``proj``.  ``forward`` and
         ``Block.forward_rows`` both end here; ``fused`` folds the append of a decode step into its attention
@@ -182,12 +189,14 @@ class Attention(nn.Module):
         k_cache, v_cache = cache
         scale = 1.0 / math.sqrt(self.hd)
         kw = self._kw()
+        skw = {} if kv_scales is None else {"kv_scales": kv_scales}  # not fp8: the calls it always made
         one = qkv.shape[1] == 1
         # a prefill's tokens sit at 0 .. N - 1 whatever row they are appended at, a step's at positions[b] + t
         qkv = self.rotate(qkv, positions if extend or one else None, inplace=True)
         if one or extend:
             if rolling:
                 kw["rolling"] = True
+            kw.update(skw)
             if one:  # attention_extend_packed would make this very call
                 if fused:
                     return attention_decode_packed(qkv, self.heads, k_cache, v_cache, positions, scale, fused=True,
@@ -197,7 +206,7 @@ class Attention(nn.Module):
         # a prefill: the masked self-attention never reads the cache; a ring keeps each sequence's last R valid rows
         kv_cache_append(k_cache, v_cache, qkv, self.heads, positions,
                         **({} if self.kv_heads == self.heads else {"kv_heads": self.kv_heads}),
-                        **({"rolling": True, "lengths": key_lengths} if rolling else {}))
+                        **({"rolling": True, "lengths": key_lengths} if rolling else {}), **skw)
         return attention_packed(qkv, self.heads, scale, causal=True, key_lengths=key_lengths, **kw)
 
 class MLP(nn.Module):
@@ -246,16 +255,21 @@ class Block(nn.Module):
         self.mlp = SwiGLU(dim, hidden, bias) if mlp == "swiglu" else MLP(dim, hidden, bias)
 
     def forward(self, x: Tensor, pending: Optional[Tensor] = None, key_lengths: Optional[Tensor] = None, *,
-                cache=None, positions: Optional[Tensor] = None, extend: bool = False, rolling: bool = False):
+                cache=None, positions: Optional[Tensor] = None, extend: bool = False, rolling: bool = False,
+                kv_scales=None):
         """``x``: residual stream; ``pending``: a sub-block output not yet added
         to it.  Returns (stream, pending) so adds fuse into the next LayerNorm.
         ``key_lengths``: per-batch key lengths for the attention (None: every key).
-        ``cache`` / ``positions`` / ``extend`` / ``rolling``: this layer's KV cache, passed to :class:`Attention`."""
+        ``cache`` / ``positions`` / ``extend`` / ``rolling`` / ``kv_scales``: this layer's KV cache, passed to
+        :class:`Attention`."""
         if pending is None:
             h = self.ln1(x)
         else:
             h, x = self.ln1(x, pending)
-        if rolling:
+        if kv_scales is not None:  # an fp8 cache
+            a = self.attn(h, key_lengths, cache=cache, positions=positions, extend=extend,
+                          **({"rolling": True} if rolling else {}), kv_scales=kv_scales)
+        elif rolling:
             a = self.attn(h, key_lengths, cache=cache, positions=positions, extend=extend, rolling=True)
         else:
             a = self.attn(h, key_lengths, cache=cache, positions=positions, extend=extend)
@@ -263,19 +277,21 @@ class Block(nn.Module):
         return x, self.mlp(h)
 
     def forward_rows(self, x: Tensor, *, cache, positions: Tensor, extend: bool = False,
-                     rolling: bool = False) -> Tensor:
+                     rolling: bool = False, kv_scales=None) -> Tensor:
         """The decoding layer on the few-row kernels (ops/linear.py ``linear_rows``; causal, forward only):
         ``x`` ``[B, T, dim]`` is the residual stream itself -- there is no ``pending`` -- and so is the
         result.  Both norms (LayerNorm or RMSNorm) run as prologues of the product behind them, bias / GELU or
         SwiGLU / residual as epilogues, and the attention is ``Attention.cached(fused=True)``: with ``T == 1`` 5 launches with a
         single-chunk cache, 6 otherwise (one more with rotary positions: the rotation of ``qkv``).
         ``T > 1`` needs ``extend=True``.  Computes what ``forward`` computes with ``cache`` / ``positions`` /
-        ``extend``, to rounding.  ``rolling``: ``cache`` is a rolling pair (:class:`Attention`)."""
+        ``extend``, to rounding.  ``rolling``: ``cache`` is a rolling pair (:class:`Attention`);
+        ``kv_scales``: it is an fp8 pair with these scales."""
         at = self.attn
         if x.shape[1] != 1 and not extend:
             raise ValueError("forward_rows: more than one token per sequence needs extend=True")
         qkv = linear_rows(x, at.qkv.weight, at.qkv.bias, **norm_args(self.ln1))
-        a = at.cached(qkv, cache, positions, extend=extend, fused=True, **({"rolling": True} if rolling else {}))
+        a = at.cached(qkv, cache, positions, extend=extend, fused=True, **({"rolling": True} if rolling else {}),
+                      **({} if kv_scales is None else {"kv_scales": kv_scales}))
         x = linear_rows(a, at.proj.weight, at.proj.bias, residual=x)
         act = "swiglu" if isinstance(self.mlp, SwiGLU) else "gelu"
         h = linear_rows(x, self.mlp.fc1.weight, self.mlp.fc1.bias, **norm_args(self.ln2), act=act)

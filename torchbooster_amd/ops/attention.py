@@ -128,6 +128,29 @@ the call, no pad rows, at most one store per slot.  Hidden slots NEVER enter ari
 loaded natively; selected away before either product on the PyTorch path, which is built from the same
 ``j(p)`` formula and is sync-free).  ``rolling=False``, the default, is everything above unchanged.
 
+FP8 KV cache (``kv_scales=`` on the five cache functions; csrc/attn_fp8.h).  A cache pair whose two tensors are
+``torch.float8_e4m3fn`` (OCP e4m3: 254 finite codes, maximum 448, no infinities) holds CODES, with two host floats
+``(k_scale, v_scale)`` per layer -- never device values, like ``window``; ``None`` is ``(1.0, 1.0)``; each must be
+finite and ``> 0`` and scales with any other pair raise ``ValueError``.  One rule on every path: a row is stored as
+``code = rne_e4m3(clamp(f32(x) * inv, -448, 448))`` with ``inv = float32(1 / scale)`` formed on the host in double
+-- the clamp is an explicit f32 min / max ahead of the conversion, so ±inf saturate to ±448 and nothing depends on
+a conversion's overflow mode; NaN stays a NaN code -- and read as ``f32(code) * f32(scale)``.  :func:`kv_quantize`
+and :func:`kv_dequantize` are that rule in PyTorch, for any device.  EVERY query that reads the cache sees the
+dequantised codes, the step's own row included: a decode step or an extend quantises its new rows, stores the codes
+and attends to them, so ``fused=True`` stays bit-equal to ``fused=False`` in output and cache bytes; only
+:func:`attention_packed`, the prefill's attention, reads unquantised ``qkv``.  Everything else above holds as
+stated -- which rows are visible, the clamps, positions read on the device, no host sync, capturability, the ring and
+its ``T <= R - W + 1`` -- and hidden rows are never loaded and never dequantised: the NaN code ``0x7F`` in a hidden
+row cannot reach an output.  Natively (CUDA, ``D == 64``, both caches e4m3 with 16-byte row conditions, bf16 ``q`` /
+``qkv``) the kernels are the ``FP8`` instantiations of the append, decode and extend kernels: rows of 64 B, converted
+by the packed hardware conversions; ``k_scale`` rides in the score factor (``scale * k_scale`` is one f32 product on
+the host), ``P·V`` accumulates the unscaled codes and the f32 accumulator is multiplied by ``v_scale`` once, before
+the partial or the output is written; the merge kernels, the workspaces and the grids are those of bf16.  The extend
+kernel feeds the dequantised codes -- exact in bf16 -- to the bf16 MFMA.  Mixed dtypes, ``float8_e5m2``, CPU tensors,
+other head dims and ``TBAMD_FORCE_REFERENCE=1`` take the PyTorch path, which dequantises the pair by the rule
+(what stock PyTorch does with a pair that is not e4m3 / e4m3 is unchanged).  With bf16 caches every call is the call
+it was.
+
 Rotary position embeddings (csrc/rope.hip): :func:`rope_packed` rotates the q and k parts of a packed
 projection by the angles :func:`rope_table` holds, before any of the functions above reads it -- so the
 training path, the prefill, the append, the decode and the extend all see rotated q / k, a cache holds
@@ -138,7 +161,7 @@ rotation), forward-only in place.
 from __future__ import annotations
 
 import math
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -149,7 +172,7 @@ from torchbooster_amd.ops._ext import native, use_native
 
 __all__ = ["attention", "attention_packed", "attention_ref", "native_supported", "kv_cache_append",
            "attention_decode", "attention_decode_packed", "attention_extend", "attention_extend_packed",
-           "rope_table", "rope_packed"]
+           "rope_table", "rope_packed", "kv_quantize", "kv_dequantize"]
 
 
 def _window(window, limit: Optional[int] = None) -> Optional[int]:
@@ -395,9 +418,92 @@ def _check_cache(k_cache: Tensor, v_cache: Tensor, B: int, H: int, D: int, pos: 
         raise RuntimeError(f"{name} must be an int32 tensor of shape [B] on the device of the cache")
 
 
+_FP8 = torch.float8_e4m3fn
+_FP8_MAX = 448.0
+
+
+def _f32(x: float) -> float:
+    """``x`` rounded to float32, as a Python float."""
+    return float(torch.tensor(x, dtype=torch.float64).to(torch.float32))
+
+
+def _check_scale(scale) -> float:
+    ok = isinstance(scale, (int, float)) and not isinstance(scale, bool) and math.isfinite(scale) and scale > 0
+    if not ok:
+        raise ValueError(f"an fp8 KV-cache scale must be a finite float > 0, not {scale!r}")
+    return float(scale)
+
+
+def kv_quantize(x: Tensor, scale: float = 1.0) -> Tensor:
+    """The quantiser of an fp8 KV cache (module docstring): ``rne_e4m3(clamp(f32(x) * inv, -448, 448))`` with
+    ``inv = float32(1 / scale)`` -> ``torch.float8_e4m3fn`` of ``x``'s shape.  ±inf saturate to ±448, NaN stays a
+    NaN code.  Any device; the native append computes the same bytes."""
+    inv = _f32(1.0 / _check_scale(scale))
+    return (x.to(torch.float32) * inv).clamp(-_FP8_MAX, _FP8_MAX).to(_FP8)
+
+
+def kv_dequantize(c: Tensor, scale: float = 1.0, dtype: torch.dtype = torch.bfloat16) -> Tensor:
+    """``f32(code) * f32(scale)`` of an fp8 KV cache (module docstring), one float32 product, -> ``dtype``
+    (``torch.float64`` holds that float32 value exactly).  The NaN codes give NaN."""
+    if c.dtype != _FP8:
+        raise ValueError(f"kv_dequantize takes a torch.float8_e4m3fn tensor, not {c.dtype}")
+    return (c.to(torch.float32) * _f32(_check_scale(scale))).to(dtype)
+
+
+def _kv_scales(kv_scales, k_cache: Tensor, v_cache: Tensor) -> Optional[Tuple[float, float]]:
+    """The ``(k_scale, v_scale)`` of an fp8 cache pair (``None`` given: ``(1.0, 1.0)``), checked; ``None`` for
+    any other pair, with which scales raise ``ValueError``."""
+    if k_cache.dtype != _FP8 or v_cache.dtype != _FP8:
+        if kv_scales is not None:
+            raise ValueError("kv_scales need float8_e4m3fn caches")
+        return None
+    if kv_scales is None:
+        return (1.0, 1.0)
+    try:
+        ks, vs = kv_scales
+    except (TypeError, ValueError):
+        raise ValueError(f"kv_scales must be a (k_scale, v_scale) pair, not {kv_scales!r}") from None
+    return (_check_scale(ks), _check_scale(vs))
+
+
+def _scale_kw(sc: Optional[Tuple[float, float]]):
+    """The trailing keywords of the native calls and of the PyTorch paths for the scales of :func:`_kv_scales`;
+    a cache that is not fp8 adds nothing: the calls they always made."""
+    if sc is None:
+        return {}, {}
+    return {"k_scale": sc[0], "v_scale": sc[1]}, {"kv_scales": sc}
+
+
+def _rows_ok_bytes(t: Tensor) -> bool:
+    """:func:`_rows_ok` for a one-byte element type: the same 16-B conditions, in bytes."""
+    return t.stride(-1) == 1 and all(s % 16 == 0 for s in t.stride()[:-1]) and t.data_ptr() % 16 == 0
+
+
 def _decode_native(x: Tensor, k_cache: Tensor, v_cache: Tensor) -> bool:
+    if k_cache.dtype == _FP8:  # the fp8 instantiations: both caches e4m3, bf16 q / qkv
+        return (v_cache.dtype == _FP8 and k_cache.is_cuda and v_cache.is_cuda and k_cache.shape[-1] == 64
+                and use_native(k_cache) and x.is_cuda and x.dtype == torch.bfloat16
+                and _rows_ok_bytes(k_cache) and _rows_ok_bytes(v_cache))
     return (native_supported(k_cache) and v_cache.dtype == torch.bfloat16 and v_cache.is_cuda and x.is_cuda
             and x.dtype == torch.bfloat16 and _rows_ok(k_cache) and _rows_ok(v_cache))
+
+
+def _put_rows(cache: Tensor, take: Tensor, rows: Tensor, scale: Optional[float]) -> None:
+    """``cache`` <- ``rows`` where ``take``, its own bits elsewhere; ``scale``: the cache is fp8 and the rows are
+    quantised by the rule (selected as bytes, so untouched rows keep theirs)."""
+    if scale is None:
+        cache.copy_(torch.where(take, rows.to(cache.dtype), cache))
+        return
+    c8 = cache.view(torch.uint8)
+    c8.copy_(torch.where(take, kv_quantize(rows, scale).view(torch.uint8), c8))
+
+
+def _dequant_pair(k_cache: Tensor, v_cache: Tensor, kv_scales, ct: torch.dtype):
+    """The caches as the PyTorch paths multiply them: dequantised (:func:`kv_dequantize`) to ``ct`` with
+    ``kv_scales``, themselves without."""
+    if kv_scales is None:
+        return k_cache, v_cache
+    return kv_dequantize(k_cache, kv_scales[0], ct), kv_dequantize(v_cache, kv_scales[1], ct)
 
 
 def _ring_rows(n: Tensor, R: int) -> Tensor:
@@ -424,7 +530,7 @@ def _ring_kw(window, k_cache: Tensor, T: int = 1) -> dict:
 
 
 def _append_ring_ref(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, positions: Tensor, hkv: int,
-                     lengths: Optional[Tensor]) -> None:
+                     lengths: Optional[Tensor], kv_scales=None) -> None:
     """The PyTorch path of :func:`kv_cache_append` with ``rolling=True``, seen from the ring: slot ``p`` of
     batch ``b`` takes the one token ``t`` of ``[n_b - R, n_b)`` with ``positions[b] + t = p (mod R)`` if
     ``t >= 0`` and ``positions[b] + t >= 0``, and keeps its bits otherwise (no host sync, no scatter)."""
@@ -440,12 +546,12 @@ def _append_ring_ref(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, 
     idx = t.clamp(0, T - 1)[:, :, None, None].expand(B, R, hkv, D)
     kv = qkv[..., heads * D:].reshape(B, T, 2, hkv, D)  # the k | v parts
     for cache, i in ((k_cache, 0), (v_cache, 1)):
-        rows = kv[:, :, i].gather(1, idx).permute(0, 2, 1, 3).to(cache.dtype)  # [B, Hkv, R, D]
-        cache.copy_(torch.where(take, rows, cache))
+        rows = kv[:, :, i].gather(1, idx).permute(0, 2, 1, 3)  # [B, Hkv, R, D]
+        _put_rows(cache, take, rows, None if kv_scales is None else kv_scales[i])
 
 
 def _append_ref(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, positions: Tensor,
-                hkv: Optional[int] = None) -> None:
+                hkv: Optional[int] = None, kv_scales=None) -> None:
     """The PyTorch path of :func:`kv_cache_append`: seen from the cache, row j of batch b takes token
     j - positions[b] if that is one of the T tokens and keeps its bits otherwise (no host sync, no
     duplicate scatter indices, out-of-range rows simply have no cache row that asks for them)."""
@@ -458,12 +564,12 @@ def _append_ref(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, posit
     idx = t.clamp(0, max(T - 1, 0))[:, :, None, None].expand(B, cap, hkv, D)
     kv = qkv[..., heads * D:].reshape(B, T, 2, hkv, D)  # the k | v parts
     for cache, i in ((k_cache, 0), (v_cache, 1)):
-        rows = kv[:, :, i].gather(1, idx).permute(0, 2, 1, 3).to(cache.dtype)  # [B, Hkv, cap, D]
-        cache.copy_(torch.where(take, rows, cache))
+        rows = kv[:, :, i].gather(1, idx).permute(0, 2, 1, 3)  # [B, Hkv, cap, D]
+        _put_rows(cache, take, rows, None if kv_scales is None else kv_scales[i])
 
 
 def _decode_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tensor, scale: float,
-                window: Optional[int] = None, rolling: bool = False) -> Tensor:
+                window: Optional[int] = None, rolling: bool = False, kv_scales=None) -> Tensor:
     """The PyTorch path of :func:`attention_decode` (softmax in fp32, or fp64 for fp64 inputs).  Hidden
     rows -- at or past the length, and below ``len - window`` -- are selected away before either product:
     a masked score is -inf whatever k held, and v is zeroed there because 0 * NaN is NaN.  A cache of
@@ -482,6 +588,7 @@ def _decode_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tensor, sc
             vis = vis & (j >= n[:, None] - window)
     vis = vis[:, None, :]  # [B, 1, cap]
     ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    k_cache, v_cache = _dequant_pair(k_cache, v_cache, kv_scales, ct)  # an fp8 pair: what the queries see
     v = torch.where(vis[..., None], v_cache, torch.zeros((), dtype=v_cache.dtype, device=q.device)).to(ct)
     B, H, D = q.shape
     if k_cache.shape[1] != H:  # query head h reads kv head h // G
@@ -496,7 +603,8 @@ def _decode_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tensor, sc
 
 def kv_cache_append(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, positions: Tensor, *,
                     kv_heads: Optional[int] = None, rolling: bool = False,
-                    lengths: Optional[Tensor] = None) -> None:
+                    lengths: Optional[Tensor] = None,
+                    kv_scales: Optional[Tuple[float, float]] = None) -> None:
     """Write the k / v rows of the packed ``qkv`` ``[B, T, (H + 2*Hkv)*D]`` into ``k_cache`` / ``v_cache``
     ``[B, Hkv, cap, D]`` at rows ``positions[b] + t`` (int32 ``[B]``); rows outside ``[0, cap)`` are dropped.
     ``kv_heads``: ``Hkv`` of grouped-query attention (module docstring); ``None`` is ``H``.
@@ -505,11 +613,16 @@ def kv_cache_append(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, p
     slot ``(positions[b] + t) mod R`` iff ``positions[b] + t >= 0`` and ``n_b - R <= t < n_b``, where ``n_b =
     clamp(lengths[b], 1, T)`` with ``lengths`` (int32 ``[B]``: the valid tokens of a right-padded batch) and
     ``T`` without: the last ``R`` valid rows, no pad rows.  ``lengths`` without ``rolling`` raises
-    ``ValueError``."""
+    ``ValueError``.
+
+    ``kv_scales`` (``float8_e4m3fn`` caches only; ``None``: ``(1.0, 1.0)``): the rows are quantised by
+    :func:`kv_quantize` with ``k_scale`` / ``v_scale`` as they are stored (module docstring)."""
     if lengths is not None and not rolling:
         raise ValueError("kv_cache_append: lengths needs rolling=True")
     _forward_only(qkv, k_cache, v_cache)
     hkv, B, _, D, _ = _packed_dims(qkv, heads, kv_heads)
+    sc = _kv_scales(kv_scales, k_cache, v_cache)
+    nkw, skw = _scale_kw(sc)
     if rolling and lengths is not None and (lengths.dtype != torch.int32 or lengths.shape != (B,)
                                             or lengths.device != k_cache.device):
         raise RuntimeError("lengths must be an int32 tensor of shape [B] on the device of the cache")
@@ -517,15 +630,15 @@ def kv_cache_append(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, p
         if _decode_native(qkv, k_cache, v_cache):
             if rolling:
                 native().attn_kv_append(_rows(qkv), heads, k_cache, v_cache, positions, hkv, rolling=True,
-                                        lengths=None if lengths is None else lengths.contiguous())
+                                        lengths=None if lengths is None else lengths.contiguous(), **nkw)
                 return
-            native().attn_kv_append(_rows(qkv), heads, k_cache, v_cache, positions, hkv)
+            native().attn_kv_append(_rows(qkv), heads, k_cache, v_cache, positions, hkv, **nkw)
             return
         _check_cache(k_cache, v_cache, B, hkv, D, positions, "positions")
         if rolling:
-            _append_ring_ref(k_cache, v_cache, qkv, heads, positions, hkv, lengths)
+            _append_ring_ref(k_cache, v_cache, qkv, heads, positions, hkv, lengths, **skw)
             return
-        _append_ref(k_cache, v_cache, qkv, heads, positions, hkv)
+        _append_ref(k_cache, v_cache, qkv, heads, positions, hkv, **skw)
 
 
 def _cache_window(window, k_cache: Tensor) -> dict:
@@ -537,32 +650,37 @@ def _cache_window(window, k_cache: Tensor) -> dict:
 
 def attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tensor,
                      scale: Optional[float] = None, *, kv_heads: Optional[int] = None,
-                     window: Optional[int] = None, rolling: bool = False) -> Tensor:
+                     window: Optional[int] = None, rolling: bool = False,
+                     kv_scales: Optional[Tuple[float, float]] = None) -> Tensor:
     """One query per (batch, head): ``q`` ``[B, H, D]`` against the first ``len = clamp(lengths[b], 1, cap)``
     rows of ``k_cache`` / ``v_cache`` ``[B, Hkv, cap, D]`` -> ``[B, H, D]``.  ``kv_heads``: ``Hkv`` of
     grouped-query attention (module docstring); ``None`` is ``H``.  ``window``: only the rows
     ``max(0, len - window) <= j < len`` (module docstring); ``window >= cap`` is ``window=None``.
     ``rolling=True`` (needs ``1 <= window <= cap``): the caches are a ring, ``len = max(lengths[b], 1)`` counts
-    tokens and the query sees the slots whose logical row is in the window (module docstring)."""
+    tokens and the query sees the slots whose logical row is in the window (module docstring).
+    ``kv_scales`` (``float8_e4m3fn`` caches only; ``None``: ``(1.0, 1.0)``): the query sees the visible rows
+    dequantised, ``f32(code) * scale`` (module docstring)."""
     _forward_only(q, k_cache, v_cache)
     if q.dim() != 3:
         raise RuntimeError("q must be [B, H, D]")
     B, H, D = q.shape
     hkv = _kv_heads(H, kv_heads)
     wkw = _ring_kw(window, k_cache) if rolling else _cache_window(window, k_cache)
+    nkw, skw = _scale_kw(_kv_scales(kv_scales, k_cache, v_cache))
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     with torch.no_grad():
         if _decode_native(q, k_cache, v_cache):
             return native().attn_decode(_rows(q), H, k_cache, v_cache, lengths, 0, scale, None, hkv,
-                                        **wkw).view(B, H, D)
+                                        **wkw, **nkw).view(B, H, D)
         _check_cache(k_cache, v_cache, B, hkv, D, lengths, "lengths")
-        return _decode_ref(q, k_cache, v_cache, lengths, scale, **wkw)
+        return _decode_ref(q, k_cache, v_cache, lengths, scale, **wkw, **skw)
 
 
 def attention_decode_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
                             scale: Optional[float] = None, *, fused: bool = False,
                             kv_heads: Optional[int] = None, window: Optional[int] = None,
-                            rolling: bool = False) -> Tensor:
+                            rolling: bool = False,
+                            kv_scales: Optional[Tuple[float, float]] = None) -> Tensor:
     """One decode step on the packed ``[B, 1, (H + 2*Hkv)*D]`` projection of the new token: append its k / v
     at row ``positions[b]``, then attend to keys ``j <= positions[b]`` -> ``[B, 1, H*D]``.  ``kv_heads``:
     ``Hkv`` of grouped-query attention (module docstring); ``None`` is ``H``.  ``window``: as
@@ -575,32 +693,36 @@ def attention_decode_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: T
     have the bits of ``fused=False``.
 
     ``rolling=True`` (needs ``1 <= window <= cap``): the caches are a ring -- the row goes to slot
-    ``positions[b] mod cap`` (dropped when ``positions[b] < 0``) and ``len = max(positions[b] + 1, 1)``."""
+    ``positions[b] mod cap`` (dropped when ``positions[b] < 0``) and ``len = max(positions[b] + 1, 1)``.
+
+    ``kv_scales`` (``float8_e4m3fn`` caches only; ``None``: ``(1.0, 1.0)``): the new row is quantised as it is
+    stored and the query sees it dequantised like every other row, ``fused`` or not (module docstring)."""
     _forward_only(qkv, k_cache, v_cache)
     hkv, B, _, D, scale = _packed_dims(qkv, heads, kv_heads, scale, T="1")
     wkw = _ring_kw(window, k_cache) if rolling else _cache_window(window, k_cache)
     akw = {"rolling": True} if rolling else {}  # the append's; no ring: the calls it always made
+    nkw, skw = _scale_kw(_kv_scales(kv_scales, k_cache, v_cache))
     with torch.no_grad():
         if _decode_native(qkv, k_cache, v_cache):
             qkv, C = _rows(qkv), native()
             if fused:
                 return C.attn_decode_append(qkv, heads, k_cache, v_cache, positions, scale,
-                                            hkv, **wkw).view(B, 1, heads * D)
-            C.attn_kv_append(qkv, heads, k_cache, v_cache, positions, hkv, **akw)
+                                            hkv, **wkw, **nkw).view(B, 1, heads * D)
+            C.attn_kv_append(qkv, heads, k_cache, v_cache, positions, hkv, **akw, **nkw)
             return C.attn_decode(qkv, heads, k_cache, v_cache, positions, 1, scale, None,
-                                 hkv, **wkw).view(B, 1, heads * D)
+                                 hkv, **wkw, **nkw).view(B, 1, heads * D)
         _check_cache(k_cache, v_cache, B, hkv, D, positions, "positions")
         if rolling:
-            _append_ring_ref(k_cache, v_cache, qkv, heads, positions, hkv, None)
+            _append_ring_ref(k_cache, v_cache, qkv, heads, positions, hkv, None, **skw)
         else:
-            _append_ref(k_cache, v_cache, qkv, heads, positions, hkv)
+            _append_ref(k_cache, v_cache, qkv, heads, positions, hkv, **skw)
         q = qkv[:, 0, :heads * D].reshape(B, heads, D)
         return _decode_ref(q, k_cache, v_cache, positions.to(torch.int64) + 1, scale,
-                           **wkw).reshape(B, 1, heads * D)
+                           **wkw, **skw).reshape(B, 1, heads * D)
 
 
 def _extend_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor, scale: float,
-                window: Optional[int] = None, rolling: bool = False) -> Tensor:
+                window: Optional[int] = None, rolling: bool = False, kv_scales=None) -> Tensor:
     """The PyTorch path of :func:`attention_extend` (softmax in fp32, or fp64 for fp64 inputs), sync-free.
     ``q`` ``[B, T, H, D]`` -> ``[B, T, H, D]``.  Scores are masked to -inf by ``L(b, t)``; v is zeroed at
     rows ``>= clamp(positions[b] + T, 1, cap)`` before the product because 0 * NaN is NaN.  Rows between
@@ -628,6 +750,7 @@ def _extend_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor, 
             held = held & (j[None, :] >= lim[:, :1] - window)
     vis, held = vis[:, None], held[:, None, :, None]  # [B, 1, T, cap], [B, 1, cap, 1]
     ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    k_cache, v_cache = _dequant_pair(k_cache, v_cache, kv_scales, ct)  # an fp8 pair: what the queries see
     v = torch.where(held, v_cache, torch.zeros((), dtype=v_cache.dtype, device=q.device)).to(ct)
     if k_cache.shape[1] != H:  # query head h reads kv head h // G
         qg = q.to(ct).reshape(B, T, k_cache.shape[1], -1, D)
@@ -641,7 +764,8 @@ def _extend_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor, 
 
 def attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
                      scale: Optional[float] = None, *, kv_heads: Optional[int] = None,
-                     window: Optional[int] = None, rolling: bool = False) -> Tensor:
+                     window: Optional[int] = None, rolling: bool = False,
+                     kv_scales: Optional[Tuple[float, float]] = None) -> Tensor:
     """``T`` queries per (batch, head): ``q`` ``[B, T, H, D]`` (any view with a contiguous last dim), whose
     k / v rows are already in ``k_cache`` / ``v_cache`` ``[B, Hkv, cap, D]`` at rows ``positions[b] + t``.
     Query ``t`` sees rows ``j < clamp(positions[b] + t + 1, 1, cap)`` -> ``[B, T, H, D]``.  ``kv_heads``:
@@ -653,25 +777,28 @@ def attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Ten
     (module docstring, which also says what may enter arithmetic); ``window >= cap`` is ``window=None``.
     ``rolling=True`` (needs ``1 <= window <= cap`` and ``T <= cap - window + 1``): the caches are a ring, the
     rows sit in slots ``(positions[b] + t) mod cap`` and ``L(b, t) = max(positions[b] + t + 1, 1)`` counts
-    tokens (module docstring)."""
+    tokens (module docstring).  ``kv_scales`` (``float8_e4m3fn`` caches only; ``None``: ``(1.0, 1.0)``): the
+    queries see the rows dequantised (module docstring)."""
     _forward_only(q, k_cache, v_cache)
     if q.dim() != 4 or q.shape[1] < 1:
         raise RuntimeError("q must be [B, T >= 1, H, D]")
     B, T, H, D = q.shape
     hkv = _kv_heads(H, kv_heads)
     wkw = _ring_kw(window, k_cache, T) if rolling else _cache_window(window, k_cache)
+    nkw, skw = _scale_kw(_kv_scales(kv_scales, k_cache, v_cache))
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     with torch.no_grad():
         if _decode_native(q, k_cache, v_cache):
             return native().attn_extend(_rows(q), k_cache, v_cache, positions, scale, None, hkv,
-                                        **wkw).view(B, T, H, D)
+                                        **wkw, **nkw).view(B, T, H, D)
         _check_cache(k_cache, v_cache, B, hkv, D, positions, "positions")
-        return _extend_ref(q, k_cache, v_cache, positions, scale, **wkw)
+        return _extend_ref(q, k_cache, v_cache, positions, scale, **wkw, **skw)
 
 
 def attention_extend_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
                             scale: Optional[float] = None, *, kv_heads: Optional[int] = None,
-                            window: Optional[int] = None, rolling: bool = False) -> Tensor:
+                            window: Optional[int] = None, rolling: bool = False,
+                            kv_scales: Optional[Tuple[float, float]] = None) -> Tensor:
     """``T`` new tokens on their packed ``[B, T, (H + 2*Hkv)*D]`` projection: append their k / v at rows
     ``positions[b] + t`` (rows outside ``[0, cap)`` are dropped), then query ``t`` attends to rows
     ``j < clamp(positions[b] + t + 1, 1, cap)`` -> ``[B, T, H*D]``.  ``T == 1`` is
@@ -679,27 +806,32 @@ def attention_extend_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: T
     ``kv_heads``: ``Hkv`` of grouped-query attention (module docstring); ``None`` is ``H``.  ``window``: as
     :func:`attention_extend` (``T == 1``: the same window in :func:`attention_decode_packed`).
     ``rolling=True``: the ring of :func:`kv_cache_append` and :func:`attention_extend` (``T <= cap - window +
-    1``, or ``ValueError`` before anything is written)."""
+    1``, or ``ValueError`` before anything is written).  ``kv_scales`` (``float8_e4m3fn`` caches only): as
+    :func:`kv_cache_append` and :func:`attention_extend`; every query, a token's own included, sees quantised
+    rows."""
     dims = _packed_dims(qkv, heads, kv_heads, scale, T="T >= 1")
     wkw = _ring_kw(window, k_cache, dims[2]) if rolling else _cache_window(window, k_cache)
     akw = {"rolling": True} if rolling else {}  # the append's; no ring: the calls it always made
+    sc = _kv_scales(kv_scales, k_cache, v_cache)
+    nkw, skw = _scale_kw(sc)
     if dims[2] == 1:
-        return attention_decode_packed(qkv, heads, k_cache, v_cache, positions, scale, kv_heads=kv_heads, **wkw)
+        return attention_decode_packed(qkv, heads, k_cache, v_cache, positions, scale, kv_heads=kv_heads, **wkw,
+                                       **skw)
     _forward_only(qkv, k_cache, v_cache)
     hkv, B, T, D, scale = dims
     with torch.no_grad():
         if _decode_native(qkv, k_cache, v_cache):
             qkv, C = _rows(qkv), native()
-            C.attn_kv_append(qkv, heads, k_cache, v_cache, positions, hkv, **akw)
+            C.attn_kv_append(qkv, heads, k_cache, v_cache, positions, hkv, **akw, **nkw)
             q = qkv[..., :heads * D].view(B, T, heads, D)
-            return C.attn_extend(q, k_cache, v_cache, positions, scale, None, hkv, **wkw)
+            return C.attn_extend(q, k_cache, v_cache, positions, scale, None, hkv, **wkw, **nkw)
         _check_cache(k_cache, v_cache, B, hkv, D, positions, "positions")
         if rolling:
-            _append_ring_ref(k_cache, v_cache, qkv, heads, positions, hkv, None)
+            _append_ring_ref(k_cache, v_cache, qkv, heads, positions, hkv, None, **skw)
         else:
-            _append_ref(k_cache, v_cache, qkv, heads, positions, hkv)
+            _append_ref(k_cache, v_cache, qkv, heads, positions, hkv, **skw)
         q = qkv[..., :heads * D].reshape(B, T, heads, D)
-        return _extend_ref(q, k_cache, v_cache, positions, scale, **wkw).reshape(B, T, heads * D)
+        return _extend_ref(q, k_cache, v_cache, positions, scale, **wkw, **skw).reshape(B, T, heads * D)
 
 
 # ---------------------------------------------------------------- rotary position embedding
