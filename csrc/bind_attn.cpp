@@ -456,6 +456,100 @@ Tensor rope_packed(const Tensor& qkv, int64_t heads, const Tensor& table, const 
   return y;
 }
 
+// ---- QK-norm + rotary embedding in one pass (csrc/qk_norm_rope.hip).  qkv, positions, out: as rope_packed;
+// q_weight / k_weight: f32 [64] on the device of qkv; table: as rope_packed, or none (no rotation).
+const float* qk_weight(const Tensor& w, const char* name, const Tensor& qkv) {
+  check_cuda(w, name);
+  TORCH_CHECK(w.scalar_type() == at::kFloat && w.dim() == 1 && w.size(0) == 64 && w.is_contiguous() &&
+                  w.device() == qkv.device(),
+              "qk_norm_rope: ", name, " must be contiguous f32 [64] on the device of qkv");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0, "qk_norm_rope: ", name, " not 16-B aligned");
+  return w.data_ptr<float>();
+}
+
+// the table pointer and its length (null and 1 without a table)
+const float* qk_table(const optional<Tensor>& table, const Tensor& qkv, int* max_len) {
+  *max_len = 1;
+  if (!given(table)) return nullptr;
+  const Tensor& t = *table;
+  check_cuda(t, "table");
+  TORCH_CHECK(t.scalar_type() == at::kFloat && t.dim() == 3 && t.size(1) == 2 && t.size(2) == 32 && t.is_contiguous() &&
+                  t.size(0) >= 1 && t.size(0) < (int64_t)INT32_MAX / 64 && t.device() == qkv.device(),
+              "qk_norm_rope: table must be contiguous f32 [max_len, 2, 32] on the device of qkv");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, "qk_norm_rope: table not 16-B aligned");
+  *max_len = (int)t.size(0);
+  return t.data_ptr<float>();
+}
+
+void qk_sizes(const Tensor& qkv, int64_t H, int64_t Hkv) {
+  TORCH_CHECK(qkv.dim() == 3, "qk_norm_rope: qkv must be bf16 [B, T, (H + 2*Hkv)*64]");
+  TORCH_CHECK(qkv.size(0) * qkv.size(1) * (H + 2 * Hkv) < (int64_t)1 << 34 && qkv.size(0) < (int64_t)INT32_MAX &&
+                  qkv.size(1) < (int64_t)INT32_MAX && H + 2 * Hkv < (int64_t)1 << 20,
+              "qk_norm_rope: bad size");
+}
+
+Tensor qk_norm_rope_packed(const Tensor& qkv, int64_t heads, const Tensor& q_weight, const Tensor& k_weight,
+                           double eps, const optional<Tensor>& table, const optional<Tensor>& positions,
+                           int64_t kv_heads, const optional<Tensor>& out) {
+  const at::DeviceGuard guard = on_device_of(qkv, "qkv");
+  const int64_t H = heads, Hkv = kv_heads_of(heads, kv_heads, "qk_norm_rope");
+  qk_sizes(qkv, H, Hkv);
+  const int64_t B = qkv.size(0), T = qkv.size(1);
+  tbamd::QkNormRopeArgs a{};
+  a.x = packed_qkv(qkv, B, H, Hkv, qkv, a.sx);
+  a.qw = qk_weight(q_weight, "q_weight", qkv);
+  a.kw = qk_weight(k_weight, "k_weight", qkv);
+  a.tab = qk_table(table, qkv, &a.max_len);
+  Tensor y;
+  if (given(out)) {
+    TORCH_CHECK(out->is_same(qkv), "qk_norm_rope: out must be qkv itself (in place)");
+    y = *out;
+    a.sy[0] = a.sx[0], a.sy[1] = a.sx[1];
+    a.copy_v = 0;
+  } else {
+    y = at::empty({B, T, qkv.size(2)}, qkv.options().memory_format(at::MemoryFormat::Contiguous));
+    a.sy[0] = T * qkv.size(2), a.sy[1] = qkv.size(2);
+    a.copy_v = 1;
+  }
+  a.y = reinterpret_cast<uint16_t*>(y.data_ptr());
+  if (given(positions)) a.pos = decode_lengths(*positions, "positions", qkv, B);
+  a.B = (int)B, a.T = (int)T, a.H = (int)H, a.Hkv = (int)Hkv, a.eps = (float)eps;
+  tbamd::qk_norm_rope_packed(a, cur_stream());
+  return y;
+}
+
+// qkv: the forward's input; grad: dL/dy, packed like qkv -> (dqkv, a new contiguous tensor whose value part
+// is grad's; dq_weight, dk_weight f32 [64]).  The partials come from the caching allocator.
+std::tuple<Tensor, Tensor, Tensor> qk_norm_rope_packed_bwd(const Tensor& qkv, const Tensor& grad, int64_t heads,
+                                                           const Tensor& q_weight, const Tensor& k_weight, double eps,
+                                                           const optional<Tensor>& table,
+                                                           const optional<Tensor>& positions, int64_t kv_heads) {
+  const at::DeviceGuard guard = on_device_of(qkv, "qkv");
+  const int64_t H = heads, Hkv = kv_heads_of(heads, kv_heads, "qk_norm_rope");
+  qk_sizes(qkv, H, Hkv);
+  const int64_t B = qkv.size(0), T = qkv.size(1);
+  TORCH_CHECK(grad.dim() == 3 && grad.size(1) == T, "qk_norm_rope: grad must have the shape of qkv");
+  tbamd::QkNormRopeBwdArgs a{};
+  a.x = packed_qkv(qkv, B, H, Hkv, qkv, a.sx);
+  a.g = packed_qkv(grad, B, H, Hkv, qkv, a.sg);
+  a.qw = qk_weight(q_weight, "q_weight", qkv);
+  a.kw = qk_weight(k_weight, "k_weight", qkv);
+  a.tab = qk_table(table, qkv, &a.max_len);
+  if (given(positions)) a.pos = decode_lengths(*positions, "positions", qkv, B);
+  Tensor dx = at::empty({B, T, qkv.size(2)}, qkv.options().memory_format(at::MemoryFormat::Contiguous));
+  a.dx = reinterpret_cast<uint16_t*>(dx.data_ptr());
+  a.sdx[0] = T * qkv.size(2), a.sdx[1] = qkv.size(2);
+  const int64_t nblk = tbamd::qk_norm_rope_bwd_blocks(B * T * (H + Hkv));
+  Tensor part = at::empty({2 * nblk * 64}, q_weight.options());
+  Tensor dw = at::empty({2, 64}, q_weight.options());
+  a.part = part.data_ptr<float>();
+  a.dqw = dw.data_ptr<float>();
+  a.dkw = a.dqw + 64;
+  a.B = (int)B, a.T = (int)T, a.H = (int)H, a.Hkv = (int)Hkv, a.eps = (float)eps;
+  tbamd::qk_norm_rope_packed_bwd(a, cur_stream());
+  return {dx, dw[0], dw[1]};
+}
+
 // q: [B, T, H, 64] (any batch / token / head strides; the q part of a packed [B, T, (H + 2*Hkv)*64] is
 // such a view) -> o [B, T, H*64].  H is q's; the caches hold kv_heads (0 = H) heads.  Query t sees cache rows j < clamp(positions[b] + t + 1, 1, cap).
 // workspace (optional, tests): f32, at least attn_extend_workspace floats; by default it comes
@@ -535,6 +629,12 @@ void register_attn(pybind11::module& m) {
   m.def("rope_packed", &rope_packed, py::arg("qkv"), py::arg("heads"), py::arg("table"),
         py::arg("positions") = py::none(), py::arg("kv_heads") = 0, py::arg("inverse") = false,
         py::arg("out") = py::none());
+  m.def("qk_norm_rope_packed", &qk_norm_rope_packed, py::arg("qkv"), py::arg("heads"), py::arg("q_weight"),
+        py::arg("k_weight"), py::arg("eps"), py::arg("table") = py::none(), py::arg("positions") = py::none(),
+        py::arg("kv_heads") = 0, py::arg("out") = py::none());
+  m.def("qk_norm_rope_packed_bwd", &qk_norm_rope_packed_bwd, py::arg("qkv"), py::arg("grad"), py::arg("heads"),
+        py::arg("q_weight"), py::arg("k_weight"), py::arg("eps"), py::arg("table") = py::none(),
+        py::arg("positions") = py::none(), py::arg("kv_heads") = 0);
   m.def("attn_extend", &attn_extend, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("positions"),
         py::arg("scale"), py::arg("workspace") = py::none(), py::arg("kv_heads") = 0, py::arg("window") = 0,
         py::arg("rolling") = false, py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0);

@@ -447,6 +447,10 @@ __global__ __launch_bounds__(64 * kColRG) void col_sum2_k(const float* __restric
   }
 }
 
+void col_sum2(const float* a, const float* b, int nblk, int C, float* oa, float* ob, hipStream_t st) {
+  col_sum2_k<<<cdiv(C, 64), 64 * kColRG, 0, st>>>(a, b, nblk, C, oa, ob);
+}
+
 // (R rows per wave-iteration, NCH 16-B chunks per lane): smallest R whose
 // R*C/8 chunks tile the 64 lanes exactly with >= 2 chunks per lane (<= 8); else
 // one row per iteration with ceil(C/512) chunks.

@@ -102,6 +102,9 @@ void gn_backward(int dt, const void* dy, const void* y, const void* x, const voi
 
 // ---- LayerNorm (rows [M, C], C % 8 == 0) ----
 int ln_bwd_blocks(int64_t M);
+// oa[c] = sum_i a[i][c], ob[c] = sum_i b[i][c] over the nblk rows of two [nblk][C] f32 partial arrays, in
+// a fixed order (the merge of the weight-gradient partials; b / oa / ob may be null)
+void col_sum2(const float* a, const float* b, int nblk, int C, float* oa, float* ob, hipStream_t st);
 void ln_forward(int dt, const void* x, const void* res, const float* gamma, const float* beta, int64_t M, int C,
                 float eps, void* y, void* xsum, float* mean, float* rstd, hipStream_t st);
 void ln_backward(int dt, const void* dy, const void* x, const void* dadd, const float* gamma, const float* mean,
@@ -421,6 +424,38 @@ struct RopeArgs {
   int64_t sx[2], sy[2];
 };
 void rope_packed(const RopeArgs& a, hipStream_t st);
+// QK-norm in the same pass (one more instantiation of the kernel): each of the H + Hkv head vectors is
+// first normalised in f32, n = x * rsqrt(mean(x^2) + eps) * w with w = qw (a query head) or kw (a key
+// head), f32 [64], 16-B aligned, and n goes into the rotation unrounded.  tab null: no rotation, y = n
+// (max_len is then not used).  inverse is not used.
+struct QkNormRopeArgs : RopeArgs {
+  const float* qw;
+  const float* kw;
+  float eps;
+};
+void qk_norm_rope_packed(const QkNormRopeArgs& a, hipStream_t st);
+// Its backward from the saved input x and g = dL/dy (both packed rows, strides sx / sg): u = the inverse
+// rotation of g (g itself without a table), x^ = x * rstd (rstd recomputed), gw = u * w,
+//   dx = rstd * (gw - x^ * mean(gw * x^))       dqw / dkw[d] = sum over query / key heads of u[d] * x^[d].
+// The value part of g is copied to dx bit for bit in the same launch.  part: the workspace,
+// 2 * qk_norm_rope_bwd_blocks(B * T * (H + Hkv)) * 64 floats; dqw, dkw: f32 [64], every element written.
+struct QkNormRopeBwdArgs {
+  const uint16_t* x;
+  const uint16_t* g;
+  uint16_t* dx;
+  const float* tab;
+  const int* pos;
+  const float* qw;
+  const float* kw;
+  float* part;
+  float* dqw;
+  float* dkw;
+  int B, T, H, Hkv, max_len;
+  float eps;
+  int64_t sx[2], sg[2], sdx[2];
+};
+int qk_norm_rope_bwd_blocks(int64_t nvec);
+void qk_norm_rope_packed_bwd(const QkNormRopeBwdArgs& a, hipStream_t st);
 
 // ---- KV-cache extend attention (csrc/attention_extend.hip; head dim 64, bf16) ----
 // T new queries per (batch, head) against the cache AFTER their own k / v rows were appended at

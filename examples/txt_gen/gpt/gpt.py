@@ -50,6 +50,7 @@ class Config(BaseConfig):
     window: int = 0  # > 0: sliding-window attention, a token sees itself and the window - 1 tokens before it
     rolling: bool = False  # the sample's KV cache keeps only about `window` rows per layer (needs window > 0)
     kv_dtype: str = ""  # "fp8": the sample's KV cache holds e4m3 codes, scales calibrated on the prompt
+    qk_norm: bool = False  # an RMSNorm over every query and key head ahead of the rotation (models/gpt.py)
 
 
 def load_bytes(path: str) -> torch.Tensor:
@@ -65,7 +66,7 @@ def main(conf: Config) -> None:
     if data.numel() <= conf.seq_len:
         raise ValueError(f"{conf.text or 'README.md'}: {data.numel()} bytes, need more than seq_len = {conf.seq_len}")
     net = getattr(gpt, conf.arch)(vocab=256, max_len=conf.seq_len, pos=conf.pos, norm=conf.norm, mlp=conf.mlp,
-                                  window=conf.window or None)
+                                  window=conf.window or None, qk_norm=conf.qk_norm)
     model = prepare_model(net, conf, channels_last=False)
     net = getattr(model, "module", model)
     optim = conf.optim.make(model.parameters())

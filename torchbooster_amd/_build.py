@@ -32,6 +32,9 @@ OUT = ROOT / "torchbooster_amd" / "_C.so"
 BUILD_BOUNDS = ROOT / "build_bounds"
 OUT_BOUNDS = ROOT / "torchbooster_amd" / "_C_bounds.so"
 ARCH = os.environ.get("TBAMD_ARCH", "gfx950")
+# extra hipcc flags of single kernel files, by file name: qk_norm_rope.hip is built without packed f32
+# instructions (v_pk_mul_f32 / v_pk_fma_f32), plain f32 ones instead
+HIP_EXTRA = {"qk_norm_rope.hip": "-Xclang -target-feature -Xclang -packed-fp32-ops"}
 
 
 def _torch_paths():
@@ -90,6 +93,9 @@ def write_ninja(debug: bool = False, bounds: bool = False) -> Path:
         "rule hip",
         "  command = $hipcc $hipflags -x hip -c $in -o $out",
         "  description = HIP $in",
+        "rule hip_extra",
+        "  command = $hipcc $hipflags $extra -x hip -c $in -o $out",
+        "  description = HIP $in",
         "rule cpp",
         "  command = $hipcc -x c++ $cppflags -c $in -o $out",
         "  description = CXX $in",
@@ -102,7 +108,11 @@ def write_ninja(debug: bool = False, bounds: bool = False) -> Path:
     for s in hip_srcs:
         o = build_dir / (s.stem + ".hip.o")
         objs.append(o)
-        lines.append(f"build {o}: hip {s} | {hdeps}")
+        if s.name in HIP_EXTRA:
+            lines.append(f"build {o}: hip_extra {s} | {hdeps}")
+            lines.append(f"  extra = {HIP_EXTRA[s.name]}")
+        else:
+            lines.append(f"build {o}: hip {s} | {hdeps}")
     for s in cpp_srcs:
         o = build_dir / (s.stem + ".cpp.o")
         objs.append(o)

@@ -86,6 +86,13 @@ every query sees them dequantised -- a step's own row included, so ``fused=True`
 while ``prefill`` attends to its own unquantised projection (ops/attention.py states the rule).  It composes with
 ``kv_heads``, ``window`` and ``rolling`` and with every ``generate`` option above; any other cache dtype adds nothing
 to any call.
+
+QK-norm (``TransformerLM(..., qk_norm=True)``; Qwen 3, Gemma 3, OLMo 2): every layer normalises each query and
+key head vector (RMSNorm over the head dim, eps 1e-6, one f32 weight ``[hd]`` for the query heads and one for
+the key heads: ``blocks[i].attn.q_norm.weight`` / ``k_norm.weight``) ahead of the rotation, in the launch that
+rotates (``ops.attention.qk_norm_rope_packed``, csrc/qk_norm_rope.hip) -- so ``pos="rope"`` models pay no
+launch for it on any path, ``pos="learned"`` ones one per layer -- and everything above keeps its meaning: a
+cache holds normalised, rotated keys.  ``qk_norm=False`` (the default) is everything above unchanged.
 """
 from __future__ import annotations
 
@@ -196,8 +203,10 @@ class TransformerLM(nn.Module):
     def __init__(self, vocab: int, dim: int, depth: int, heads: int, max_len: int, mlp_ratio: float = 4.0,
                  kv_heads: Optional[int] = None, *, pos: str = "learned", rope_base: float = 10000.0,
                  norm: str = "layer", mlp: str = "gelu", bias: bool = True,
-                 window: Union[None, int, Sequence[Optional[int]]] = None) -> None:
+                 window: Union[None, int, Sequence[Optional[int]]] = None, qk_norm: bool = False) -> None:
         super().__init__()
+        if not isinstance(qk_norm, bool):
+            raise ValueError(f"qk_norm must be a bool, not {qk_norm!r}")
         if pos not in ("learned", "rope"):
             raise ValueError(f"pos must be 'learned' or 'rope', not {pos!r}")
         if window is None or isinstance(window, int):
@@ -216,6 +225,8 @@ class TransformerLM(nn.Module):
         kw = {} if self.rope is None else {"rope": self.rope}  # learned: the calls it always made
         if (norm, mlp, bias) != ("layer", "gelu", True):  # likewise the GPT-2 block
             kw.update(norm=norm, mlp=mlp, bias=bias)
+        if qk_norm:
+            kw["qk_norm"] = True
         # (no window: the calls it always made)
         self.blocks = nn.ModuleList([Block(dim, heads, mlp_ratio, causal=True, kv_heads=kv_heads, **kw,
                                            **({} if w is None else {"window": w})) for w in windows])
@@ -601,13 +612,14 @@ def kv_scales(model: TransformerLM, tokens: Tensor, lengths: Optional[Tensor] = 
 
 
 def gpt_tiny(vocab: int = 256, max_len: int = 128, pos: str = "learned", *, norm: str = "layer", mlp: str = "gelu",
-             bias: bool = True, kv_heads: Optional[int] = None, mlp_ratio: float = 4.0, window=None) -> TransformerLM:
+             bias: bool = True, kv_heads: Optional[int] = None, mlp_ratio: float = 4.0, window=None,
+             qk_norm: bool = False) -> TransformerLM:
     return TransformerLM(vocab, 128, 2, 2, max_len, mlp_ratio, kv_heads, pos=pos, norm=norm, mlp=mlp, bias=bias,
-                         window=window)
+                         window=window, qk_norm=qk_norm)
 
 
 def gpt2_small(vocab: int = 50257, max_len: int = 1024, pos: str = "learned", *, norm: str = "layer",
                mlp: str = "gelu", bias: bool = True, kv_heads: Optional[int] = None,
-               mlp_ratio: float = 4.0, window=None) -> TransformerLM:
+               mlp_ratio: float = 4.0, window=None, qk_norm: bool = False) -> TransformerLM:
     return TransformerLM(vocab, 768, 12, 12, max_len, mlp_ratio, kv_heads, pos=pos, norm=norm, mlp=mlp, bias=bias,
-                         window=window)
+                         window=window, qk_norm=qk_norm)

@@ -20,7 +20,7 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from torchbooster_amd.ops.attention import (attention_decode_packed, attention_extend_packed, attention_packed,
-                                            kv_cache_append, rope_packed, rope_table)
+                                            kv_cache_append, qk_norm_rope_packed, rope_packed, rope_table)
 from torchbooster_amd.ops.conv import Conv2d
 
 from torchbooster_amd.ops.act import swiglu
@@ -125,11 +125,20 @@ class Attention(nn.Module):
 
     ``kv_scales`` (likewise an argument of ``forward`` / ``cached``: the ``(k_scale, v_scale)`` of an fp8 cache
     pair, ops/attention.py; ``None``: nothing is added to any call): passed to the append of a prefill and to
-    the decode step and the extend.  A prefill's own attention reads its unquantised ``qkv``."""
+    the decode step and the extend.  A prefill's own attention reads its unquantised ``qkv``.
+
+    ``qk_norm`` (``False``: nothing changes): an RMSNorm over every query and key head vector, with
+    ``qk_eps``, ahead of the rotation -- ``q_norm`` / ``k_norm`` (:class:`~torchbooster_amd.ops.norm.RMSNorm`
+    of the head dim) only hold the two weights, f32 under dtype casts and initialised to ones without an RNG
+    draw.  It runs inside :meth:`rotate` (``ops.attention.qk_norm_rope_packed``: one launch for norm and
+    rotation, the norm alone without ``rope``), hence on every path, and a cache holds normalised keys."""
 
     def __init__(self, dim: int, heads: int, causal: bool = False, kv_heads: Optional[int] = None,
-                 rope: Optional[Rope] = None, bias: bool = True, window: Optional[int] = None) -> None:
+                 rope: Optional[Rope] = None, bias: bool = True, window: Optional[int] = None,
+                 qk_norm: bool = False, qk_eps: float = 1e-6) -> None:
         super().__init__()
+        if not isinstance(qk_norm, bool):
+            raise ValueError(f"qk_norm must be a bool, not {qk_norm!r}")
         if window is not None:
             if isinstance(window, bool) or not isinstance(window, int) or window < 1:
                 raise ValueError(f"window must be None or an int >= 1, not {window!r}")
@@ -147,6 +156,10 @@ class Attention(nn.Module):
         self.rope = rope
         self.qkv = Linear(dim, 3 * dim if kv_heads is None else (heads + 2 * self.kv_heads) * self.hd, bias=bias)
         self.proj = Linear(dim, dim, bias=bias)
+        self.qk_norm = qk_norm
+        if qk_norm:
+            self.q_norm = RMSNorm(self.hd, float(qk_eps))
+            self.k_norm = RMSNorm(self.hd, float(qk_eps))
 
     def _kw(self) -> dict:
         """``kv_heads`` / ``window`` where the layer has them: plain MHA without a window makes the calls it
@@ -157,7 +170,12 @@ class Attention(nn.Module):
         return kw
 
     def rotate(self, qkv: Tensor, positions: Optional[Tensor] = None, inplace: bool = False) -> Tensor:
-        """The packed projection with q and k rotated; ``qkv`` itself without ``rope``."""
+        """The packed projection with q and k normalised (``qk_norm``) and rotated (``rope``); ``qkv`` itself
+        without either."""
+        if self.qk_norm:
+            return qk_norm_rope_packed(qkv, self.heads, self.q_norm.weight, self.k_norm.weight, self.q_norm.eps,
+                                       None if self.rope is None else self.rope.table(qkv), positions,
+                                       kv_heads=self.kv_heads, inplace=inplace)
         if self.rope is None:
             return qkv
         return rope_packed(qkv, self.heads, self.rope.table(qkv), positions, kv_heads=self.kv_heads, inplace=inplace)
@@ -240,16 +258,18 @@ class Block(nn.Module):
     ``norm="rms"``: ``ln1`` / ``ln2`` are :class:`~torchbooster_amd.ops.norm.RMSNorm` (the attribute names
     stay: the ``(x, pending)`` protocol of ``forward`` is the same); ``mlp="swiglu"``: ``self.mlp`` is a
     :class:`SwiGLU` of hidden width ``int(dim * mlp_ratio)``; ``bias=False``: no bias in ``qkv``, ``proj`` and
-    the MLP's linears -- together the Llama-style block.  ``window``: the sliding window of :class:`Attention`."""
+    the MLP's linears -- together the Llama-style block.  ``window``: the sliding window of :class:`Attention`; ``qk_norm``: its QK-norm."""
 
     def __init__(self, dim: int, heads: int, mlp_ratio: float = 4.0, causal: bool = False,
                  kv_heads: Optional[int] = None, rope: Optional[Rope] = None, norm: str = "layer",
-                 mlp: str = "gelu", bias: bool = True, window: Optional[int] = None) -> None:
+                 mlp: str = "gelu", bias: bool = True, window: Optional[int] = None,
+                 qk_norm: bool = False) -> None:
         super().__init__()
         if mlp not in ("gelu", "swiglu"):
             raise ValueError(f"mlp must be 'gelu' or 'swiglu', not {mlp!r}")
         self.ln1 = make_norm(norm, dim)
-        self.attn = Attention(dim, heads, causal, kv_heads, rope, bias=bias, window=window)
+        self.attn = Attention(dim, heads, causal, kv_heads, rope, bias=bias, window=window,
+                              **({"qk_norm": qk_norm} if qk_norm is not False else {}))
         self.ln2 = make_norm(norm, dim)
         hidden = int(dim * mlp_ratio)
         self.mlp = SwiGLU(dim, hidden, bias) if mlp == "swiglu" else MLP(dim, hidden, bias)
@@ -282,7 +302,8 @@ class Block(nn.Module):
         ``x`` ``[B, T, dim]`` is the residual stream itself -- there is no ``pending`` -- and so is the
         result.  Both norms (LayerNorm or RMSNorm) run as prologues of the product behind them, bias / GELU or
         SwiGLU / residual as epilogues, and the attention is ``Attention.cached(fused=True)``: with ``T == 1`` 5 launches with a
-        single-chunk cache, 6 otherwise (one more with rotary positions: the rotation of ``qkv``).
+        single-chunk cache, 6 otherwise (one more with rotary positions or ``qk_norm`` or both: the one launch
+        that normalises and rotates ``qkv``).
         ``T > 1`` needs ``extend=True``.  Computes what ``forward`` computes with ``cache`` / ``positions`` /
         ``extend``, to rounding.  ``rolling``: ``cache`` is a rolling pair (:class:`Attention`);
         ``kv_scales``: it is an fp8 pair with these scales."""

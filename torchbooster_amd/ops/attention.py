@@ -157,6 +157,11 @@ training path, the prefill, the append, the decode and the extend all see rotate
 rotated keys, and none of the attention kernels knows.  Positions follow the clamp rule of
 ``embed_rows`` and are read on the device.  Differentiable out of place (the gradient is the inverse
 rotation), forward-only in place.
+
+QK-norm (csrc/qk_norm_rope.hip): :func:`qk_norm_rope_packed` is that rotation with an RMSNorm of every query and
+key head vector in front of it -- two f32 weights ``[D]``, one for the query heads and one for the key heads --
+in the same launch and with one rounding; without a table it is the norm alone.  Differentiable out of place
+w.r.t. the projection and both weights (one backward kernel, deterministic), forward-only in place.
 """
 from __future__ import annotations
 
@@ -172,7 +177,7 @@ from torchbooster_amd.ops._ext import native, use_native
 
 __all__ = ["attention", "attention_packed", "attention_ref", "native_supported", "kv_cache_append",
            "attention_decode", "attention_decode_packed", "attention_extend", "attention_extend_packed",
-           "rope_table", "rope_packed", "kv_quantize", "kv_dequantize"]
+           "rope_table", "rope_packed", "qk_norm_rope_packed", "kv_quantize", "kv_dequantize"]
 
 
 def _window(window, limit: Optional[int] = None) -> Optional[int]:
@@ -953,3 +958,118 @@ def rope_packed(qkv: Tensor, heads: int, table: Tensor, positions: Optional[Tens
         return _RopeFn.apply(qkv, heads, hkv, table, positions, bool(inverse))
     with torch.no_grad():
         return _rope_apply(qkv, heads, hkv, table, positions, bool(inverse), False)
+
+
+# ---------------------------------------------------------------- QK-norm (+ rotary position embedding)
+def _qk_norm_rope_ref(qkv: Tensor, heads: int, hkv: int, q_weight: Tensor, k_weight: Tensor, eps: float,
+                      table: Optional[Tensor], positions: Optional[Tensor], inplace: bool) -> Tensor:
+    """The PyTorch path of :func:`qk_norm_rope_packed`: the formulas in fp32 (fp64 for fp64 inputs), one
+    rounding, the kernel's clamp, no host sync; differentiable by autograd."""
+    B, T, E = qkv.shape
+    hr = heads + hkv
+    D = E // (hr + hkv)
+    ct = torch.float64 if qkv.dtype == torch.float64 else torch.float32
+    x = qkv[..., :hr * D].reshape(B, T, hr, D).to(ct)
+    w = torch.cat((q_weight.to(ct).expand(heads, D), k_weight.to(ct).expand(hkv, D)))
+    y = x * torch.rsqrt(x.square().mean(dim=-1, keepdim=True) + eps) * w
+    if table is not None:
+        at = torch.arange(T, device=qkv.device)[None, :]
+        if positions is not None:
+            at = positions.to(torch.int64)[:, None] + at
+        cs = table[at.clamp(0, table.shape[0] - 1)]  # [B | 1, T, 2, D / 2]
+        c, s = cs[:, :, 0, None, :].to(ct), cs[:, :, 1, None, :].to(ct)
+        y1, y2 = y[..., :D // 2], y[..., D // 2:]
+        y = torch.cat((y1 * c - y2 * s, y2 * c + y1 * s), dim=-1)
+    y = y.to(qkv.dtype).reshape(B, T, hr * D)
+    if inplace:
+        qkv[..., :hr * D].copy_(y)
+        return qkv
+    return torch.cat((y, qkv[..., hr * D:]), dim=-1)
+
+
+def _qk_norm_rope_native(qkv: Tensor, q_weight: Tensor, table: Optional[Tensor]) -> bool:
+    return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and q_weight.dtype == torch.float32
+            and (table is None or table.dtype == torch.float32) and use_native(qkv))
+
+
+class _QkNormRopeFn(torch.autograd.Function):
+    """The native path under autograd: the input is the one saved activation (csrc/qk_norm_rope.hip)."""
+
+    @staticmethod
+    def forward(ctx, qkv, q_weight, k_weight, heads, hkv, eps, table, positions):
+        x = _rows(qkv)
+        ctx.save_for_backward(x, q_weight, k_weight, table, positions)
+        ctx.cfg = (heads, hkv, eps)
+        return native().qk_norm_rope_packed(x, heads, q_weight, k_weight, eps, table, positions, hkv, None)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, q_weight, k_weight, table, positions = ctx.saved_tensors
+        heads, hkv, eps = ctx.cfg
+        dx, dq, dk = native().qk_norm_rope_packed_bwd(x, _rows(g), heads, q_weight, k_weight, eps, table, positions,
+                                                      hkv)
+        return dx, dq, dk, None, None, None, None, None
+
+
+def qk_norm_rope_packed(qkv: Tensor, heads: int, q_weight: Tensor, k_weight: Tensor, eps: float = 1e-6,
+                        table: Optional[Tensor] = None, positions: Optional[Tensor] = None, *,
+                        kv_heads: Optional[int] = None, inplace: bool = False) -> Tensor:
+    """QK-norm fused with the rotation of :func:`rope_packed`: ``qkv`` ``[B, T, (H + 2*Hkv)*D]`` -> the same
+    shape.  Each of the ``H`` query and ``Hkv`` key head vectors ``x`` of a row becomes
+    ``n = x * rsqrt(mean(x^2) + eps) * w`` with ``w = q_weight`` for a query head and ``k_weight`` for a key
+    head (float32 ``[D]`` on the device of ``qkv``, never rounded to bf16; float64 with a float64 ``qkv``),
+    then, with a ``table``, ``y = rotate(n)`` exactly as :func:`rope_packed` does it (layout, ``positions``,
+    clamp); ``table=None`` is ``y = n``, QK-norm for models without rotary positions.  All in fp32 (fp64 for
+    fp64 inputs) with ONE rounding, at the store: ``n`` is never rounded on its way into the rotation.  The
+    value part is copied bit for bit (``inplace=True``: the result is ``qkv`` itself, the value part untouched).
+
+    Native path (csrc/qk_norm_rope.hip, one launch): CUDA bf16, ``D == 64``, float32 weights, a float32 table
+    or none; a view that is not 16-B aligned with row strides in multiples of 8 goes through
+    ``.contiguous()``.  Everything else -- CPU, other dtypes, another even ``D``,
+    ``TBAMD_FORCE_REFERENCE=1`` -- is the PyTorch path with the same formulas.
+
+    Out of place it is differentiable w.r.t. ``qkv``, ``q_weight`` and ``k_weight`` (native: one backward
+    kernel from the saved ``qkv`` plus a fixed-order merge of the weight-gradient partials, no atomics,
+    bit-deterministic); the table and the positions get no gradient.  ``inplace=True`` is forward-only and
+    raises if an input requires grad in grad mode.  Nothing syncs with the host: capturable, and a replay
+    follows in-place changes of ``positions``."""
+    hkv, B, _, D, _ = _packed_dims(qkv, heads, kv_heads, even=True)
+    wt = (torch.float32, torch.float64) if qkv.dtype == torch.float64 else (torch.float32,)
+    for name, w in (("q_weight", q_weight), ("k_weight", k_weight)):
+        if w.dtype not in wt or w.shape != (D,) or w.device != qkv.device:
+            raise RuntimeError(f"{name} must be float32 [D = {D}] on the device of qkv, "
+                               f"not {w.dtype} {tuple(w.shape)} on {w.device}")
+    if table is not None:
+        if table.dim() != 3 or table.shape[1] != 2 or table.shape[2] != D // 2 or table.shape[0] < 1:
+            raise RuntimeError(f"table must be [max_len, 2, D // 2 = {D // 2}], not {tuple(table.shape)}")
+        if table.device != qkv.device:
+            raise RuntimeError("table must be on the device of qkv")
+    if positions is not None and (positions.dtype != torch.int32 or positions.shape != (B,)
+                                  or positions.device != qkv.device):
+        raise RuntimeError("positions must be an int32 tensor of shape [B] on the device of qkv")
+    eps = float(eps)
+    grad = torch.is_grad_enabled() and (qkv.requires_grad or q_weight.requires_grad or k_weight.requires_grad)
+    if inplace and grad:
+        raise RuntimeError("qk_norm_rope_packed(inplace=True) is forward-only: call it under torch.no_grad() or "
+                           "detach the inputs")
+    if not (D == 64 and _qk_norm_rope_native(qkv, q_weight, table)):
+        if grad:
+            return _qk_norm_rope_ref(qkv, heads, hkv, q_weight, k_weight, eps, table, positions, False)
+        with torch.no_grad():
+            return _qk_norm_rope_ref(qkv, heads, hkv, q_weight, k_weight, eps, table, positions, inplace)
+    table = None if table is None else table.contiguous()
+    pos = None if positions is None else positions.contiguous()
+    q_weight, k_weight = q_weight.contiguous(), k_weight.contiguous()
+    if grad:
+        return _QkNormRopeFn.apply(qkv, q_weight, k_weight, heads, hkv, eps, table, pos)
+    with torch.no_grad():
+        if _rows_ok(qkv):
+            return native().qk_norm_rope_packed(qkv, heads, q_weight, k_weight, eps, table, pos, hkv,
+                                                qkv if inplace else None)
+        y = native().qk_norm_rope_packed(qkv.contiguous(), heads, q_weight, k_weight, eps, table, pos, hkv, None)
+        if inplace:  # the normalised part alone goes back: the value part is not touched
+            w = (heads + hkv) * D
+            qkv[..., :w].copy_(y[..., :w])
+            return qkv
+        return y
