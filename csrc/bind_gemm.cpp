@@ -62,7 +62,11 @@ std::vector<Tensor> gemm(const Tensor& x, const Tensor& w, bool tw, const option
   Tensor part;
   if (s > 1) part = at::empty({(int64_t)s * P * Q}, x.options().dtype(at::kFloat));
   Tensor z;
-  if (epi == 2 && want_z) z = at::empty({P, Q}, x.options());
+  if (epi == 2 && want_z) {
+    // the kernels store z with y's row stride
+    TORCH_CHECK(y.stride(0) == Q, "gemm: the saved pre-activation needs a contiguous out");
+    z = at::empty({P, Q}, x.options());
+  }
   tbamd::gemm_bf16(x.data_ptr(), x.stride(0), tx, wc.data_ptr(), tw, y.data_ptr(), y.stride(0), bp, rp,
                    ptr_or_null(z), (int)P, (int)Q, (int)K, (int)epi, t, s, f32_or_null(part), cur_stream());
   if (z.defined()) return {y, z};
