@@ -1,5 +1,5 @@
-// Bindings of the dense GEMM kernels (gemm.hip, gemm8.hip) and of the bias-gradient / GELU kernels
-// that go with them (colsum.hip).
+// Bindings of the dense GEMM kernels (gemm.hip, gemm8.hip), of the grouped GEMM (gemm_grouped.hip) and
+// of the bias-gradient / GELU kernels that go with them (colsum.hip).
 #include "bind_common.h"
 
 namespace {
@@ -112,6 +112,64 @@ std::vector<Tensor> gemm_nn_gelu_bwd(const Tensor& dy, const Tensor& w_, const T
   return {y, db};
 }
 
+// --------------------------------------------- grouped GEMM (gemm_grouped.hip)
+void check_grouped(const Tensor& t, int64_t dim, const char* name) {
+  check_cuda(t, name);
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16 && t.dim() == dim && t.is_contiguous(), "grouped gemm: ", name,
+              " must be a contiguous ", dim, "-D bf16 tensor");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, "grouped gemm: ", name, " must be 16-B aligned");
+}
+int64_t check_offsets(const Tensor& offsets, const Tensor& like) {
+  TORCH_CHECK(offsets.is_cuda() && offsets.device() == like.device() && offsets.scalar_type() == at::kInt &&
+                  offsets.dim() == 1 && offsets.is_contiguous() && offsets.numel() >= 2,
+              "grouped gemm: offsets must be a contiguous int32 [E + 1] tensor on the operands' device");
+  return offsets.numel() - 1;
+}
+
+// y [R, Q] = x[r] @ w[e(r)]^T (tw false, w [E, Q, K]) or x[r] @ w[e(r)] (tw true, w [E, K, Q]); x [R, K];
+// the rows of expert e are offsets[e] .. offsets[e + 1] - 1, rows of no expert come back zero
+Tensor grouped_rows(const Tensor& x, const Tensor& w, const Tensor& offsets, bool tw) {
+  check_grouped(x, 2, "x");
+  check_grouped(w, 3, "w");
+  const at::DeviceGuard guard(x.device());
+  const int64_t E = check_offsets(offsets, x);
+  const int64_t R = x.size(0), K = x.size(1), Q = tw ? w.size(2) : w.size(1);
+  TORCH_CHECK(w.device() == x.device() && w.size(0) == E && (tw ? w.size(1) : w.size(2)) == K,
+              "grouped gemm: w must be [E, ", tw ? "K, Q" : "Q, K", "] with E = offsets.numel() - 1");
+  TORCH_CHECK(K % 8 == 0 && Q % 8 == 0, "grouped gemm: K and Q must be multiples of 8");
+  TORCH_CHECK(R < (1ll << 31) - 65536 && Q < (1ll << 31) - 128 && K < (1ll << 31) - 64 && E < (1 << 20),
+              "grouped gemm: dims too large");
+  Tensor y = at::empty({R, Q}, x.options());
+  tbamd::grouped_rows_bf16(x.data_ptr(), w.data_ptr(), tw, offsets.data_ptr<int>(), y.data_ptr(), (int)R, (int)E,
+                           (int)Q, (int)K, cur_stream());
+  return y;
+}
+
+// dw [E, P, Q]: dw[e] = dy[rows of e]^T @ x[rows of e]; dy [R, P], x [R, Q]
+Tensor grouped_tn(const Tensor& dy, const Tensor& x, const Tensor& offsets, const optional<Tensor>& out) {
+  check_grouped(dy, 2, "dy");
+  check_grouped(x, 2, "x");
+  const at::DeviceGuard guard(x.device());
+  const int64_t E = check_offsets(offsets, x);
+  const int64_t R = x.size(0), P = dy.size(1), Q = x.size(1);
+  TORCH_CHECK(dy.device() == x.device() && dy.size(0) == R, "grouped gemm: dy and x must have the same rows");
+  TORCH_CHECK(P % 8 == 0 && Q % 8 == 0, "grouped gemm: P and Q must be multiples of 8");
+  TORCH_CHECK(R < (1ll << 31) - 65536 && Q < (1ll << 31) - 128 && P < (1ll << 31) - 128 && E < 65536,
+              "grouped gemm: dims too large");
+  Tensor dw;
+  if (given(out)) {
+    dw = *out;
+    check_grouped(dw, 3, "out");
+    TORCH_CHECK(dw.device() == x.device() && dw.size(0) == E && dw.size(1) == P && dw.size(2) == Q,
+                "grouped gemm: out must be [E, P, Q]");
+  } else {
+    dw = at::empty({E, P, Q}, x.options());
+  }
+  tbamd::grouped_tn_bf16(dy.data_ptr(), x.data_ptr(), offsets.data_ptr<int>(), dw.data_ptr(), (int)R, (int)E, (int)P,
+                         (int)Q, cur_stream());
+  return dw;
+}
+
 // --------------------------------------------- bias gradients / GELU
 Tensor colsum_out(const Tensor& dy, const optional<Tensor>& out) {
   const int64_t C = dy.size(1);
@@ -172,7 +230,9 @@ void register_gemm(pybind11::module& m) {
         py::arg("out") = py::none(), py::arg("tx") = false, py::arg("splits") = 1);
   m.def("gemm_nn_gelu_bwd", &gemm_nn_gelu_bwd, py::arg("dy"), py::arg("w"), py::arg("z"),
         py::arg("db_out") = py::none(), py::arg("wt") = py::none());
-  m.def("colsum", &colsum, py::arg("dy"), py::arg("out") = py::none());
+  m.def("grouped_rows", &grouped_rows, py::arg("x"), py::arg("w"), py::arg("offsets"), py::arg("tw") = false);
+  m.def("grouped_tn", &grouped_tn, py::arg("dy"), py::arg("x"), py::arg("offsets"), py::arg("out") = py::none());
+  m.def("colsum", &colsum,py::arg("dy"), py::arg("out") = py::none());
   m.def("gelu_fwd", &gelu_fwd);
   m.def("gelu_bwd_colsum", &gelu_bwd_colsum, py::arg("dy"), py::arg("z"), py::arg("out") = py::none());
   m.def("gemm_pick_splits", &tbamd::gemm_pick_splits);

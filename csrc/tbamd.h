@@ -636,6 +636,18 @@ void gemm_bf16(const void* X, int64_t ldx, bool tx, const void* W, bool tw, void
                hipStream_t st);
 int gemm_pick_splits(int P, int Q, int K, int tile);
 
+// ---- grouped GEMM for mixture-of-experts MLPs (gemm_grouped.hip; bf16).  offsets: int32 [E + 1] on the
+// device, read by the kernels only: expert e owns rows [b_e, b_{e+1}) with b_0 = 0 and
+// b_i = max(b_{i-1}, clamp(offsets[i], 0, R)); rows [b_E, R) belong to no expert.
+// Y [R][Q] = X[r] . W[e(r)]^T (tw = false, W [E][Q][K]) or X[r] . W[e(r)] (tw = true, W [E][K][Q]); zeros for
+// the rows of no expert.  K % 8 == 0, Q % 8 == 0.
+void grouped_rows_bf16(const void* X, const void* W, bool tw, const int* offsets, void* Y, int R, int E, int Q, int K,
+                       hipStream_t st);
+// dW [E][P][Q]: dW[e] = dY[rows of e]^T . X[rows of e] with dY [R][P], X [R][Q]; zeros for an expert
+// without rows.  P % 8 == 0, Q % 8 == 0.  No split-K: bit-deterministic.
+void grouped_tn_bf16(const void* dY, const void* X, const int* offsets, void* dW, int R, int E, int P, int Q,
+                     hipStream_t st);
+
 // ---- fused vocabulary projection + cross entropy (gemm_k epilogues of csrc/gemm.hip; merge in csrc/loss.hip)
 int lm_loss_tile_q();
 void lm_loss_partials(const void* X, int64_t ldx, const void* W, const int64_t* labels, float* part, float* xy, int M,

@@ -51,6 +51,9 @@ class Config(BaseConfig):
     rolling: bool = False  # the sample's KV cache keeps only about `window` rows per layer (needs window > 0)
     kv_dtype: str = ""  # "fp8": the sample's KV cache holds e4m3 codes, scales calibrated on the prompt
     qk_norm: bool = False  # an RMSNorm over every query and key head ahead of the rotation (models/gpt.py)
+    experts: int = 8  # mlp: moe -- the experts of every layer's mixture (models/vit.py MoE)
+    top_k: int = 2  # mlp: moe -- the experts each token is sent to
+    aux_coef: float = 0.01  # mlp: moe -- the weight of the load-balancing loss (MoE.aux_loss, summed over the layers)
 
 
 def load_bytes(path: str) -> torch.Tensor:
@@ -66,7 +69,8 @@ def main(conf: Config) -> None:
     if data.numel() <= conf.seq_len:
         raise ValueError(f"{conf.text or 'README.md'}: {data.numel()} bytes, need more than seq_len = {conf.seq_len}")
     net = getattr(gpt, conf.arch)(vocab=256, max_len=conf.seq_len, pos=conf.pos, norm=conf.norm, mlp=conf.mlp,
-                                  window=conf.window or None, qk_norm=conf.qk_norm)
+                                  window=conf.window or None, qk_norm=conf.qk_norm,
+                                  **({"experts": conf.experts, "top_k": conf.top_k} if conf.mlp == "moe" else {}))
     model = prepare_model(net, conf, channels_last=False)
     net = getattr(model, "module", model)
     optim = conf.optim.make(model.parameters())
@@ -79,6 +83,8 @@ def main(conf: Config) -> None:
         start = torch.randint(0, data.numel() - conf.seq_len, (conf.batch_size, 1), generator=g, device=data.device)
         tokens = data[start + window]
         loss = net.loss(tokens)
+        if conf.mlp == "moe" and conf.aux_coef:  # TransformerLM.loss leaves the load-balancing loss to the caller
+            loss = loss + conf.aux_coef * sum(b.mlp.aux_loss() for b in net.blocks)
         utils.step(loss, optim, sched, clip=conf.clip)
         run.update(loss.detach())
         if (it + 1) % conf.log_every == 0 or it == 0:

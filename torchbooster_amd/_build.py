@@ -32,9 +32,10 @@ OUT = ROOT / "torchbooster_amd" / "_C.so"
 BUILD_BOUNDS = ROOT / "build_bounds"
 OUT_BOUNDS = ROOT / "torchbooster_amd" / "_C_bounds.so"
 ARCH = os.environ.get("TBAMD_ARCH", "gfx950")
-# extra hipcc flags of single kernel files, by file name: qk_norm_rope.hip is built without packed f32
-# instructions (v_pk_mul_f32 / v_pk_fma_f32), plain f32 ones instead
-HIP_EXTRA = {"qk_norm_rope.hip": "-Xclang -target-feature -Xclang -packed-fp32-ops"}
+# extra hipcc flags of single kernel files, by file name: qk_norm_rope.hip and gemm_grouped.hip are built
+# without packed f32 instructions (v_pk_mul_f32 / v_pk_fma_f32), plain f32 ones instead
+_NO_PK_F32 = "-Xclang -target-feature -Xclang -packed-fp32-ops"
+HIP_EXTRA = {"qk_norm_rope.hip": _NO_PK_F32, "gemm_grouped.hip": _NO_PK_F32}
 
 
 def _torch_paths():

@@ -93,6 +93,16 @@ the key heads: ``blocks[i].attn.q_norm.weight`` / ``k_norm.weight``) ahead of th
 rotates (``ops.attention.qk_norm_rope_packed``, csrc/qk_norm_rope.hip) -- so ``pos="rope"`` models pay no
 launch for it on any path, ``pos="learned"`` ones one per layer -- and everything above keeps its meaning: a
 cache holds normalised, rotated keys.  ``qk_norm=False`` (the default) is everything above unchanged.
+
+Mixture of experts (``TransformerLM(..., mlp="moe", experts=8, top_k=2)``; Mixtral, gpt-oss, Qwen 3 MoE): every
+MLP is a :class:`~torchbooster_amd.models.vit.MoE` -- a bias-free f32 router, the ``top_k`` largest logits per
+token, softmax gates over those, ``experts`` SwiGLU experts of hidden width ``int(dim * mlp_ratio)`` -- whose
+expert products are grouped GEMMs (``ops.gemm.grouped_linear``, csrc/gemm_grouped.hip) over the expert-sorted
+rows, without a host read or an atomic.  ``prefill`` / ``decode_step`` / ``extend`` / ``generate`` (``graph=True``,
+``cache=``, ``draft=``, ``rolling=True``, an fp8 cache) run it unchanged; ``fused=True`` raises ``ValueError``
+(no few-row expert kernel).  ``loss`` does not include the load-balancing loss: add
+``sum(b.mlp.aux_loss() for b in model.blocks)`` with a coefficient.  Any other ``mlp`` is everything above
+unchanged.
 """
 from __future__ import annotations
 
@@ -101,7 +111,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 import torch
 from torch import Tensor, nn
 
-from torchbooster_amd.models.vit import Block, Rope, make_norm, norm_args
+from torchbooster_amd.models.vit import Block, MoE, Rope, make_norm, norm_args
 from torchbooster_amd.ops.attention import _check_scale
 from torchbooster_amd.ops.linear import Linear, embed_rows, linear_rows
 from torchbooster_amd.ops.loss import linear_cross_entropy
@@ -203,7 +213,8 @@ class TransformerLM(nn.Module):
     def __init__(self, vocab: int, dim: int, depth: int, heads: int, max_len: int, mlp_ratio: float = 4.0,
                  kv_heads: Optional[int] = None, *, pos: str = "learned", rope_base: float = 10000.0,
                  norm: str = "layer", mlp: str = "gelu", bias: bool = True,
-                 window: Union[None, int, Sequence[Optional[int]]] = None, qk_norm: bool = False) -> None:
+                 window: Union[None, int, Sequence[Optional[int]]] = None, qk_norm: bool = False,
+                 experts: int = 8, top_k: int = 2) -> None:
         super().__init__()
         if not isinstance(qk_norm, bool):
             raise ValueError(f"qk_norm must be a bool, not {qk_norm!r}")
@@ -227,6 +238,8 @@ class TransformerLM(nn.Module):
             kw.update(norm=norm, mlp=mlp, bias=bias)
         if qk_norm:
             kw["qk_norm"] = True
+        if mlp == "moe":  # every MLP a mixture of `experts` SwiGLU experts, `top_k` per token (models/vit.py MoE)
+            kw.update(experts=experts, top_k=top_k)
         # (no window: the calls it always made)
         self.blocks = nn.ModuleList([Block(dim, heads, mlp_ratio, causal=True, kv_heads=kv_heads, **kw,
                                            **({} if w is None else {"window": w})) for w in windows])
@@ -240,6 +253,9 @@ class TransformerLM(nn.Module):
                 nn.init.normal_(m.weight, std=0.02)
                 if m.bias is not None:
                     nn.init.zeros_(m.bias)
+            elif isinstance(m, MoE):
+                nn.init.normal_(m.fc1, std=0.02)
+                nn.init.normal_(m.fc2, std=0.02)
 
     def features(self, tokens: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
         """[B, N] token ids -> [B, N, dim], the output of the final norm (the input of ``head``)."""
@@ -352,6 +368,8 @@ class TransformerLM(nn.Module):
         """``decode_step`` and ``extend``: ``tokens`` ``[B, T]`` at ``cache.positions[b] + t``, on the few-row
         kernels when ``fused``.  ``[B, T, vocab]``, or ``[B, vocab]`` with ``last_only``."""
         T = tokens.shape[1]
+        if fused and any(isinstance(blk.mlp, MoE) for blk in self.blocks):
+            raise ValueError("fused=True: there is no few-row kernel for an MoE block")
         with torch.no_grad():
             if fused:
                 x = embed_rows(tokens, self.tok.weight, None if self.pos is None else self.pos[0], cache.positions)
@@ -505,6 +523,8 @@ class TransformerLM(nn.Module):
             raise ValueError(f"prompt {N} + max_new_tokens {max_new_tokens} exceeds max_len {self.max_len}")
         if graph and not tokens.is_cuda:
             raise ValueError("graph=True needs CUDA tensors")
+        if fused and any(isinstance(blk.mlp, MoE) for m in (self, draft) if m is not None for blk in m.blocks):
+            raise ValueError("fused=True: there is no few-row kernel for an MoE block")
         if draft is not None:
             gamma = int(draft_tokens)
             if temperature != 0 or top_k is not None or graph or cache is not None:
@@ -613,13 +633,14 @@ def kv_scales(model: TransformerLM, tokens: Tensor, lengths: Optional[Tensor] = 
 
 def gpt_tiny(vocab: int = 256, max_len: int = 128, pos: str = "learned", *, norm: str = "layer", mlp: str = "gelu",
              bias: bool = True, kv_heads: Optional[int] = None, mlp_ratio: float = 4.0, window=None,
-             qk_norm: bool = False) -> TransformerLM:
+             qk_norm: bool = False, experts: int = 8, top_k: int = 2) -> TransformerLM:
     return TransformerLM(vocab, 128, 2, 2, max_len, mlp_ratio, kv_heads, pos=pos, norm=norm, mlp=mlp, bias=bias,
-                         window=window, qk_norm=qk_norm)
+                         window=window, qk_norm=qk_norm, experts=experts, top_k=top_k)
 
 
 def gpt2_small(vocab: int = 50257, max_len: int = 1024, pos: str = "learned", *, norm: str = "layer",
                mlp: str = "gelu", bias: bool = True, kv_heads: Optional[int] = None,
-               mlp_ratio: float = 4.0, window=None, qk_norm: bool = False) -> TransformerLM:
+               mlp_ratio: float = 4.0, window=None, qk_norm: bool = False, experts: int = 8,
+               top_k: int = 2) -> TransformerLM:
     return TransformerLM(vocab, 768, 12, 12, max_len, mlp_ratio, kv_heads, pos=pos, norm=norm, mlp=mlp, bias=bias,
-                         window=window, qk_norm=qk_norm)
+                         window=window, qk_norm=qk_norm, experts=experts, top_k=top_k)

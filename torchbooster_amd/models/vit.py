@@ -24,10 +24,11 @@ from torchbooster_amd.ops.attention import (attention_decode_packed, attention_e
 from torchbooster_amd.ops.conv import Conv2d
 
 from torchbooster_amd.ops.act import swiglu
+from torchbooster_amd.ops.gemm import grouped_linear
 from torchbooster_amd.ops.norm import LayerNorm, RMSNorm
 from torchbooster_amd.ops.linear import GeluLink, Linear, LinearGELU, linear, linear_rows
 
-__all__ = ["ViT", "vit_b_16", "vit_s_16", "vit_tiny", "Attention", "Block", "Rope", "SwiGLU"]
+__all__ = ["ViT", "vit_b_16", "vit_s_16", "vit_tiny", "Attention", "Block", "Rope", "SwiGLU", "MoE"]
 
 
 class Rope:
@@ -253,26 +254,136 @@ class SwiGLU(nn.Module):
         return self.fc2(swiglu(self.fc1(x)))
 
 
+class _Permute(torch.autograd.Function):
+    """``rows[perm]`` for a permutation ``perm`` whose inverse is ``inv``: the backward is the gather
+    ``d[inv]``, not the ``index_add`` autograd would record."""
+
+    @staticmethod
+    def forward(ctx, rows, perm, inv):
+        ctx.save_for_backward(perm, inv)
+        return rows.index_select(0, perm)
+
+    @staticmethod
+    def backward(ctx, d):
+        perm, inv = ctx.saved_tensors
+        return _Permute.apply(d, inv, perm), None, None
+
+
+class _Dispatch(torch.autograd.Function):
+    """Token rows ``h`` ``[T, dim]`` -> the ``T * top_k`` expert-sorted rows ``h[order // top_k]``.  The
+    backward gathers the sorted gradients back by the inverse permutation and sums each token's ``top_k``
+    rows in slot order: no ``index_add``, no atomics."""
+
+    @staticmethod
+    def forward(ctx, h, order, inv, top_k):
+        ctx.save_for_backward(order, inv)
+        ctx.top_k = top_k
+        return h.index_select(0, torch.div(order, top_k, rounding_mode="floor"))
+
+    @staticmethod
+    def backward(ctx, d):
+        order, inv = ctx.saved_tensors
+        k = ctx.top_k
+        dh = _Permute.apply(d, inv, order).view(-1, k, d.shape[-1])
+        return (dh[:, 0] if k == 1 else dh.sum(1)), None, None, None
+
+
+def _check_experts(experts, top_k) -> None:
+    if isinstance(experts, bool) or not isinstance(experts, int) or experts < 1:
+        raise ValueError(f"experts must be an int >= 1, not {experts!r}")
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= experts:
+        raise ValueError(f"top_k must be an int in [1, experts = {experts}], not {top_k!r}")
+
+
+class MoE(nn.Module):
+    """Sparse mixture of ``experts`` SwiGLU MLPs with Mixtral's routing rule: ``logits = router(h)`` in f32
+    (a bias-free ``Linear(dim, experts)``), the ``top_k`` largest logits of each token (ties to the lower
+    index), gates = the f32 softmax over those ``top_k`` logits, ``y = sum_j gate_j * expert_{e_j}(h)``.  The
+    experts' weights are stacked: ``fc1`` ``[experts, 2 * hidden, dim]`` (``gate | up``) and ``fc2``
+    ``[experts, dim, hidden]``; they have no bias.
+
+    Dispatch: a stable sort of the ``T * top_k`` (token, slot) pairs by expert, the group offsets from a
+    ``searchsorted`` of the sorted expert ids (``bincount`` reads its bin count on the host), a gather of
+    the rows, ``grouped_linear`` -> ``swiglu`` -> ``grouped_linear`` (ops/gemm.py; csrc/gemm_grouped.hip), and
+    the combine by the inverse permutation: gather back to ``[T, top_k, dim]``, times the gates in f32, summed
+    over ``top_k`` in slot order, one rounding.  No ``index_add``, no atomics, no host read: deterministic and
+    hipGraph-capturable.  No capacity limit: no token is dropped.
+
+    :meth:`aux_loss` is the Switch load-balancing loss of the last forward."""
+
+    def __init__(self, dim: int, hidden: int, experts: int, top_k: int = 2, bias: bool = False) -> None:
+        super().__init__()
+        _check_experts(experts, top_k)
+        if bias:
+            raise ValueError("MoE experts have no bias")
+        self.experts, self.top_k = experts, top_k
+        self.router = nn.Linear(dim, experts, bias=False)
+        self.fc1 = nn.Parameter(torch.empty(experts, 2 * hidden, dim))
+        self.fc2 = nn.Parameter(torch.empty(experts, dim, hidden))
+        for w in (self.fc1, self.fc2):  # each expert as nn.Linear initialises its weight
+            nn.init.uniform_(w, -1.0 / math.sqrt(w.shape[2]), 1.0 / math.sqrt(w.shape[2]))
+        self._aux: Optional[Tensor] = None
+
+    def route(self, h: Tensor):
+        """``h`` ``[T, dim]`` -> (f32 logits ``[T, experts]``, expert ids ``[T, top_k]``, f32 gates ``[T, top_k]``)."""
+        logits = F.linear(h.float(), self.router.weight.float())
+        top, idx = torch.sort(logits, dim=-1, descending=True, stable=True)  # stable: ties to the lower index
+        return logits, idx[:, :self.top_k], torch.softmax(top[:, :self.top_k], dim=-1)
+
+    def forward(self, x: Tensor) -> Tensor:
+        E, k = self.experts, self.top_k
+        h = x.reshape(-1, x.shape[-1])
+        T = h.shape[0]
+        logits, idx, gates = self.route(h)
+        ids, order = torch.sort(idx.reshape(-1), stable=True)  # pair t * k + j, sorted by expert
+        inv = torch.empty_like(order).scatter_(0, order, torch.arange(T * k, device=h.device))
+        offsets = torch.searchsorted(ids, torch.arange(E + 1, device=h.device)).to(torch.int32)
+        rows = _Dispatch.apply(h, order, inv, k)
+        rows = grouped_linear(swiglu(grouped_linear(rows, self.fc1, offsets)), self.fc2, offsets)
+        y = _Permute.apply(rows, inv, order).view(T, k, -1)
+        y = y[:, 0].float() * gates[:, 0, None] if k == 1 else (y.float() * gates[:, :, None]).sum(1)
+        # Switch: E * sum_e (share of the pairs routed to e) * (mean router probability of e)
+        share = (offsets[1:] - offsets[:-1]).float() / float(max(T * k, 1))
+        self._aux = E * (share * torch.softmax(logits, dim=-1).mean(0)).sum()
+        return y.to(x.dtype).view(x.shape)
+
+    def aux_loss(self) -> Tensor:
+        """The load-balancing loss ``experts * sum_e f_e * p_e`` of the last forward, an f32 scalar (1 when the
+        routing is uniform): ``f_e`` the share of the (token, slot) pairs sent to expert ``e``, ``p_e`` the
+        mean router probability of ``e`` over the tokens.  Differentiable through ``p_e``."""
+        if self._aux is None:
+            raise RuntimeError("aux_loss: no forward has run")
+        return self._aux
+
+
 class Block(nn.Module):
     """Pre-norm transformer block.  The defaults are the GPT-2 / ViT block: LayerNorm, a GELU MLP, biases.
     ``norm="rms"``: ``ln1`` / ``ln2`` are :class:`~torchbooster_amd.ops.norm.RMSNorm` (the attribute names
     stay: the ``(x, pending)`` protocol of ``forward`` is the same); ``mlp="swiglu"``: ``self.mlp`` is a
     :class:`SwiGLU` of hidden width ``int(dim * mlp_ratio)``; ``bias=False``: no bias in ``qkv``, ``proj`` and
-    the MLP's linears -- together the Llama-style block.  ``window``: the sliding window of :class:`Attention`; ``qk_norm``: its QK-norm."""
+    the MLP's linears -- together the Llama-style block.  ``window``: the sliding window of :class:`Attention`; ``qk_norm``: its QK-norm.
+    ``mlp="moe"``: ``self.mlp`` is a :class:`MoE` of ``experts`` SwiGLU experts of that hidden width, ``top_k`` per
+    token (its router and experts never have a bias; ``bias`` then governs ``qkv`` and ``proj`` alone);
+    ``forward_rows`` has no few-row expert kernel and raises ``ValueError``."""
 
     def __init__(self, dim: int, heads: int, mlp_ratio: float = 4.0, causal: bool = False,
                  kv_heads: Optional[int] = None, rope: Optional[Rope] = None, norm: str = "layer",
                  mlp: str = "gelu", bias: bool = True, window: Optional[int] = None,
-                 qk_norm: bool = False) -> None:
+                 qk_norm: bool = False, experts: int = 8, top_k: int = 2) -> None:
         super().__init__()
-        if mlp not in ("gelu", "swiglu"):
-            raise ValueError(f"mlp must be 'gelu' or 'swiglu', not {mlp!r}")
+        if mlp not in ("gelu", "swiglu", "moe"):
+            raise ValueError(f"mlp must be 'gelu', 'swiglu' or 'moe', not {mlp!r}")
+        if mlp == "moe":
+            _check_experts(experts, top_k)
         self.ln1 = make_norm(norm, dim)
         self.attn = Attention(dim, heads, causal, kv_heads, rope, bias=bias, window=window,
                               **({"qk_norm": qk_norm} if qk_norm is not False else {}))
         self.ln2 = make_norm(norm, dim)
         hidden = int(dim * mlp_ratio)
-        self.mlp = SwiGLU(dim, hidden, bias) if mlp == "swiglu" else MLP(dim, hidden, bias)
+        if mlp == "moe":
+            self.mlp = MoE(dim, hidden, experts, top_k)
+        else:
+            self.mlp = SwiGLU(dim, hidden, bias) if mlp == "swiglu" else MLP(dim, hidden, bias)
 
     def forward(self, x: Tensor, pending: Optional[Tensor] = None, key_lengths: Optional[Tensor] = None, *,
                 cache=None, positions: Optional[Tensor] = None, extend: bool = False, rolling: bool = False,
@@ -308,6 +419,8 @@ class Block(nn.Module):
         ``extend``, to rounding.  ``rolling``: ``cache`` is a rolling pair (:class:`Attention`);
         ``kv_scales``: it is an fp8 pair with these scales."""
         at = self.attn
+        if isinstance(self.mlp, MoE):
+            raise ValueError("forward_rows (fused=True): there is no few-row kernel for an MoE block")
         if x.shape[1] != 1 and not extend:
             raise ValueError("forward_rows: more than one token per sequence needs extend=True")
         qkv = linear_rows(x, at.qkv.weight, at.qkv.bias, **norm_args(self.ln1))

@@ -32,7 +32,7 @@ from torchbooster_amd.ops import _agree
 from torchbooster_amd.ops._ext import native
 
 __all__ = ["mm_nt", "mm_nn", "mm_tn", "supported_nt", "supported_nn", "supported_tn", "tile_table",
-           "save_tiles", "load_tiles"]
+           "save_tiles", "load_tiles", "grouped_linear", "group_bounds"]
 
 _AUTOTUNE = os.environ.get("TBAMD_GEMM_AUTOTUNE", "1") != "0"
 _TUNE_LOG = os.environ.get("TBAMD_TUNE_LOG", "0") == "1"
@@ -310,6 +310,87 @@ def mm_tn(dy: Tensor, x: Tensor, out: Optional[Tensor] = None) -> Tensor:
             out.copy_(y)
             y = out
     return y
+
+
+# --------------------------------------------------------------- grouped GEMM (csrc/gemm_grouped.hip)
+def group_bounds(offsets: Tensor, rows: int) -> Tensor:
+    """The boundaries every path of :func:`grouped_linear` uses, int64 ``[E + 1]``: ``b[0] = 0`` and
+    ``b[i] = max(b[i - 1], clamp(offsets[i], 0, rows))``.  Expert ``e`` owns rows ``b[e] .. b[e + 1] - 1``; a
+    decreasing pair is an empty group, a value outside ``[0, rows]`` is clamped, ``offsets[0]`` is not used."""
+    b = offsets[1:].to(torch.int64).clamp(0, rows).cummax(0).values
+    return torch.cat([b.new_zeros(1), b])
+
+
+def _grouped_ref(x: Tensor, weight: Tensor, offsets: Tensor) -> Tensor:
+    """One masked ``F.linear`` per expert; no host read of ``offsets``."""
+    R = x.shape[0]
+    b = group_bounds(offsets, R)
+    r = torch.arange(R, device=x.device)
+    y = x.new_zeros(R, weight.shape[1])
+    for e in range(weight.shape[0]):
+        mine = (r >= b[e]) & (r < b[e + 1])
+        y = torch.where(mine[:, None], F.linear(x, weight[e]), y)
+    return y
+
+
+class _GroupedLinearFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, offsets):
+        ctx.save_for_backward(x, weight, offsets)
+        ctx.param = weight  # the Parameter itself: its gradient slot (ops/_ext.py take_slot)
+        return native().grouped_rows(x, weight, offsets, False)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, offsets = ctx.saved_tensors
+        if torch.is_grad_enabled():  # double backward: differentiable recompute
+            with torch.enable_grad():
+                xx, ww = x.detach().requires_grad_(True), weight.detach().requires_grad_(True)
+                gx, gw = torch.autograd.grad(_grouped_ref(xx, ww, offsets), (xx, ww), dy.to(x.dtype),
+                                             create_graph=True)
+            return gx, gw, None
+        dy = dy.to(x.dtype).contiguous()
+        if dy.data_ptr() % 16:
+            dy = dy.clone()
+        C = native()
+        dx = C.grouped_rows(dy, weight, offsets, True) if ctx.needs_input_grad[0] else None
+        dw = None
+        if ctx.needs_input_grad[1]:
+            from torchbooster_amd.ops._ext import slot_alias, take_slot
+
+            s = take_slot(ctx.param)
+            if s is not None and not (s.dtype == dy.dtype and s.is_contiguous() and s.shape == weight.shape):
+                s = None
+            dw = C.grouped_tn(dy, x, offsets, s)  # all E weight gradients in one piece
+            if s is not None:
+                dw = slot_alias(s)
+        return dx, dw, None
+
+
+def grouped_linear(x: Tensor, weight: Tensor, offsets: Tensor) -> Tensor:
+    """``y[r] = x[r] @ weight[e(r)].T`` for expert-sorted rows: ``x`` ``[R, K]``, ``weight`` ``[E, Q, K]``,
+    ``offsets`` an integer ``[E + 1]`` tensor on ``x``'s device (:func:`group_bounds`: expert ``e`` owns rows
+    ``offsets[e] .. offsets[e + 1] - 1``) -> ``[R, Q]``.  Rows at or past ``offsets[E]`` come back zero.
+
+    Native (csrc/gemm_grouped.hip: one launch forward, one for the input gradient, one for all ``E`` weight
+    gradients; ``offsets`` is read by the kernels only, so a call is capturable and a replay follows in-place
+    changes of it; no atomics, bit-deterministic) for CUDA bf16 with ``K % 8 == 0`` and ``Q % 8 == 0``.
+    Everything else is one masked ``F.linear`` per expert under autograd, with the same meaning."""
+    if x.dim() != 2 or weight.dim() != 3 or weight.shape[2] != x.shape[1]:
+        raise ValueError(f"grouped_linear: x [R, K] and weight [E, Q, K] expected, not {tuple(x.shape)} and "
+                         f"{tuple(weight.shape)}")
+    if offsets.dim() != 1 or offsets.shape[0] != weight.shape[0] + 1 or offsets.is_floating_point():
+        raise ValueError(f"grouped_linear: offsets must be an integer [E + 1 = {weight.shape[0] + 1}] tensor")
+    from torchbooster_amd.ops._ext import use_native
+
+    R, K = x.shape
+    if (use_native(x, weight) and _ok(x, weight) and offsets.is_cuda and K % 8 == 0 and weight.shape[1] % 8 == 0
+            and R > 0 and not torch.is_autocast_enabled("cuda")):
+        xc, wc = x.contiguous(), weight.contiguous()
+        if xc.data_ptr() % 16:
+            xc = xc.clone()
+        return _GroupedLinearFn.apply(xc, wc, offsets.to(torch.int32).contiguous())
+    return _grouped_ref(x, weight, offsets)
 
 
 if _AUTOTUNE:
