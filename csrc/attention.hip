@@ -49,6 +49,14 @@
 // skips (nvk) know the upper side only.  dK/dV: key j is seen by queries j <= i < j + W and, because a
 // pad query (i >= len) sees the last W valid keys, by every i >= j when j >= len - W; so the per-key
 // qmin gains a qmax, and a wave's (and the workgroup's) query tile range an upper end.
+//
+// Attention sinks (AttnArgs::sinks, f32 [H] in device memory): head h's raw logit sinks[h] -- not multiplied by
+// scale -- takes part in every row's softmax denominator and contributes nothing to its output, whatever the masks
+// hide.  It is one more partial, (m = sinks[h] * log2e, l = 1, o = 0), folded in where a row is normalised:
+// fwd_store<true>, behind the key loop and ahead of the divide.  No tile body changes; SINK is a template flag of
+// attn_fwd_k next to MODE (six instantiations: the three that existed are the code they were), which calls with
+// sinks always take.  The stored log-sum-exp includes the sink, so the three backward kernels run as without it
+// and csrc/attention_sink.hip adds the sink's own gradient from lse and delta behind the dQ pass.
 #include <type_traits>
 
 #include "common.h"
@@ -86,21 +94,35 @@ __device__ __forceinline__ const uint16_t* head(const uint16_t* p, const int64_t
 
 // ------------------------------------------------------------------ forward
 // normalised Oᵀ -> O rows and the log-sum-exp of each query (the backward's softmax statistics)
+// SINK (AttnArgs::sinks): the head's sink is one more partial (m = sinks[h] * log2e, l = 1, o = 0) merged
+// into each query here, behind the key loop: with M' = max(m, s2) the row's sum becomes l * f + exp2(s2 - M'),
+// f = exp2(m - M'), added once per query (l is whole only after the two shuffles), and Oᵀ is scaled by f --
+// which rides in the store's factor f / l, so the accumulators are not touched.  Every query has seen a key
+// (m finite), and a sink whose term underflows leaves f = exp2(0) and l + 0: the bits of the call without it.
+template <bool SINK = false>
 __device__ __forceinline__ void fwd_store(const AttnArgs& a, int b, int h, int q0, const f32x4_t (&acc)[4][2],
                                           const float (&m)[2], const float (&l)[2], int fr, int fg) {
   const int N = a.N;
+  float s2 = 0.f;
+  if constexpr (SINK) s2 = a.sinks[h] * kLog2e;  // a raw logit: not multiplied by scale
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     float lt = l[qt];
     lt += __shfl_xor(lt, 16);
     lt += __shfl_xor(lt, 32);
+    float mt = m[qt], f = 1.f;
+    if constexpr (SINK) {
+      mt = fmaxf(m[qt], s2);
+      f = __builtin_amdgcn_exp2f(m[qt] - mt);
+      lt = __builtin_fmaf(lt, f, __builtin_amdgcn_exp2f(s2 - mt));
+    }
     const int qi = q0 + 16 * qt + fr;
     if (qi < N) {
-      const float inv = 1.f / lt;
+      const float inv = f / lt;
       uint16_t* op = a.o + b * a.so[0] + h * a.so[1] + qi * a.so[2] + 4 * fg;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) st4(op + 16 * dt, acc[dt][qt], inv);
-      if (fg == 0) a.lse[((int64_t)b * a.H + h) * N + qi] = (m[qt] + log2f(lt)) * 0.6931471805599453f;
+      if (fg == 0) a.lse[((int64_t)b * a.H + h) * N + qi] = (mt + log2f(lt)) * 0.6931471805599453f;
     }
   }
 }
@@ -221,7 +243,8 @@ __device__ __forceinline__ QLim q_limits(const AttnArgs& a, int len, int q0, int
   return r;
 }
 
-template <int MODE>
+// SINK: the instantiations calls with AttnArgs::sinks take (fwd_store<true>; the tile loop is the same)
+template <int MODE, bool SINK = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_k(AttnArgs a) {
   constexpr bool MASK = MODE != kDense, WIN = MODE == kWin;
   __shared__ __attribute__((aligned(16))) uint4 lds[2 * 2 * kTileU4];  // [buf][K | V] = 32 KiB
@@ -325,7 +348,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_k(AttnArgs a) {
   };
   if (nqt == 2) run(std::integral_constant<int, 2>{});
   else run(std::integral_constant<int, 1>{});
-  fwd_store(a, b, h, q0, acc, m, l, fr, fg);
+  fwd_store<SINK>(a, b, h, q0, acc, m, l, fr, fg);
 }
 
 // Whole-head forward (N <= 256, the ViT-B/16 197 tokens): ONE workgroup of 8 waves per (batch, head)
@@ -995,9 +1018,16 @@ int attn_set_head_mask(int mask) {
 }
 
 // the masked instantiations run only when a mask is requested (same grids, same kernel choice); a
-// windowed call always takes the 128-row kernels, whatever N and attn_set_head_mask say
+// windowed call always takes the 128-row kernels, whatever N and attn_set_head_mask say, and so does the
+// forward of a call with sinks (its backward kernels are chosen as without them)
 void attn_fwd(const AttnArgs& a, hipStream_t st) {
   const bool mask = a.causal || a.klen;
+  if (a.sinks) {  // always the 128-row kernel, like a windowed call: there is no whole-head kernel with sinks
+    const int nblk = (a.N + kBlk - 1) / kBlk;
+    auto* k = a.window > 0 ? attn_fwd_k<kWin, true> : (mask ? attn_fwd_k<kMask, true> : attn_fwd_k<kDense, true>);
+    hipLaunchKernelGGL(k, dim3(nblk * a.H * a.B), dim3(256), 0, st, a);
+    return;
+  }
   if (a.window > 0) {
     const int nblk = (a.N + kBlk - 1) / kBlk;
     hipLaunchKernelGGL(attn_fwd_k<kWin>, dim3(nblk * a.H * a.B), dim3(256), 0, st, a);
@@ -1016,14 +1046,16 @@ void attn_bwd(const AttnArgs& a, hipStream_t st) {
   const bool mask = a.causal || a.klen;
   const bool fits = a.N <= kHeadTiles * kTile;
   const int nblk = (a.N + kBlk - 1) / kBlk;
-  // dQ pass first: it also writes delta = rowsum(dO * O), which the dK/dV pass reads
+  // dQ pass first: it also writes delta = rowsum(dO * O), which the dK/dV pass and the sink's gradient read
   if (a.window > 0) {
     hipLaunchKernelGGL(attn_bwd_dq_k<kWin>, dim3(nblk * a.H * a.B), dim3(256), 0, st, a);
+    if (a.sinks) attn_bwd_dsink(a, st);
     hipLaunchKernelGGL(attn_bwd_dkdv_k<kWin>, dim3(nblk * a.H * a.B), dim3(256), 0, st, a);
     return;
   }
   hipLaunchKernelGGL(mask ? attn_bwd_dq_k<kMask> : attn_bwd_dq_k<kDense>, dim3(nblk * a.H * a.B), dim3(256), 0, st,
                      a);
+  if (a.sinks) attn_bwd_dsink(a, st);  // (the stored lse includes the sink: dq, dk, dv need nothing else)
   if ((g_attn_head & 4) && fits)
     hipLaunchKernelGGL(mask ? attn_bwd_dkdv_head_k<true> : attn_bwd_dkdv_head_k<false>, dim3(a.H * a.B),
                        dim3(kHeadWaves * 64), 0, st, a);

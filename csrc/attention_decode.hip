@@ -97,6 +97,16 @@
 // kUnroll are those of bf16 (profiles/kv_fp8/README.md has the measurements).  FP8 is a template parameter next
 // to WIN and RING: every call on a bf16 cache takes the instantiations that existed before
 // (profiles/kv_fp8/resources.txt).
+//
+// Attention sinks (AttnDecodeArgs::sinks, f32 [H] in device memory or null): query head h's raw logit sinks[h]
+// joins the softmax denominator and adds nothing to the output.  It is one more partial, (m = sinks[h] * log2e,
+// l = 1, o = 0), and enters only where a row is normalised: attn_decode_merge_k starts its running max and its
+// sum from it, and the fused single-chunk epilogue computes exactly what the merge computes from its one partial
+// plus the sink, so fused stays bit-equal to unfused.  Both sites test the pointer (wave-uniform) instead of
+// doubling the GB x WIN x RING x FP8 x FUSED instantiations for one scalar per head; with a head block, head
+// h0 + j reads sinks[h0 + j].  The streaming loop, the partials, the workspace and the grid are unchanged, the
+// sink has no position (no window or ring hides it), and under FP8 acc is scaled before the fold (o = 0 makes the
+// order irrelevant).  A sink whose term underflows -- exp2(s2 - M) = 0 -- leaves the bits of the call without it.
 #include <type_traits>
 
 #include "attn_fp8.h"
@@ -350,10 +360,18 @@ __device__ __forceinline__ void attn_decode_split_body(const AttnDecodeArgs& a, 
 #pragma unroll
       for (int i = 0; i < 8; ++i) acc[j][i] *= a.vscale;
     }
-    if (FUSED && a.nchunks == 1) {  // what attn_decode_merge_k computes from this one partial
+    if (FUSED && a.nchunks == 1) {  // what attn_decode_merge_k computes from this one partial (and the sink)
       if (g == 0) {
-        const float f = __builtin_amdgcn_exp2f(M - M);
-        const float L = fmaf(f, l[j], 0.f);
+        // sinks (a wave-uniform null check, not a template flag: one scalar per head): the running max and
+        // the sum start from the sink's partial, as in the merge; without sinks Ms = M and L starts from 0
+        float Ms = M, L0 = 0.f;
+        if (a.sinks != nullptr) {
+          const float s2 = a.sinks[h0 + j] * kLog2e;
+          Ms = fmaxf(s2, M);
+          L0 = __builtin_amdgcn_exp2f(s2 - Ms);
+        }
+        const float f = __builtin_amdgcn_exp2f(M - Ms);
+        const float L = fmaf(f, l[j], L0);
         float o[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) o[i] = fmaf(f, acc[j][i], 0.f) / L;
@@ -392,9 +410,13 @@ __global__ __launch_bounds__(64) void attn_decode_merge_k(AttnDecodeArgs a) {
   const float* wo = a.ws + (int64_t)bh * a.nchunks * 64;
   const float* wm = a.ws + (int64_t)a.nparts * 64 + (int64_t)bh * a.nchunks;
   const float* wl = wm + a.nparts;
-  float M = -INFINITY;
+  // sinks: head h's sink is one more partial, (m = sinks[h] * log2e, l = 1, o = 0), taken first: the running
+  // max starts from its m and the sum from its term (a wave-uniform null check; without sinks: -inf and 0)
+  const bool sink = a.sinks != nullptr;
+  const float s2 = sink ? a.sinks[h] * kLog2e : -INFINITY;
+  float M = s2;
   for (int ck = 0; ck < a.nchunks; ++ck) M = fmaxf(M, wm[ck]);  // the chunk of row len - 1 is never empty: finite
-  float o = 0.f, L = 0.f;
+  float o = 0.f, L = sink ? __builtin_amdgcn_exp2f(s2 - M) : 0.f;
   for (int ck = 0; ck < a.nchunks; ++ck) {
     const float mc = wm[ck];
     if (mc == -INFINITY) continue;  // empty: its o was never written and is never read

@@ -103,6 +103,11 @@
 // predicates above (RowsLoaded) and become the zero code without forming an address.  The accumulator is
 // multiplied by vscale once, before the store or the partial; the merge kernel is unchanged.  FP8 is a template
 // parameter next to WIN and RING: bf16 caches take the instantiations that existed (profiles/kv_fp8/resources.txt).
+//
+// Attention sinks (AttnExtendArgs::sinks, f32 [H] in device memory or null; csrc/attention_decode.hip states the
+// scheme): head h's sink is one more partial, (m = sinks[h] * log2e, l = 1, o = 0), merged where a row is
+// normalised -- the single-split store and attn_extend_merge_k -- behind a workgroup-uniform null check.  The
+// tile loop, the partials, the workspace and the grid are unchanged, and the sink has no position.
 #include "attn_fp8.h"
 #include "attn_ring.h"
 #include "common.h"
@@ -435,8 +440,17 @@ __global__ __launch_bounds__(64) void attn_extend_split_k(AttnExtendArgs a) {
     for (int dt = 0; dt < 4; ++dt) acc[dt] *= a.vscale;
   }
   if (a.nsplit == 1) {
-    if (qreal) {  // the one split holds row L(b, t) - 1: l > 0
-      const float inv = 1.f / l;
+    if (qreal) {  // the one split holds row L(b, t) - 1: l > 0, m finite
+      // sinks (workgroup-uniform null check): the sink's partial (m = sinks[h] * log2e, l = 1, o = 0) merged
+      // into the row -- the factor exp2(m - M') on Oᵀ rides in the store's factor, acc is not touched
+      float f = 1.f;
+      if (a.sinks != nullptr) {
+        const float s2 = a.sinks[h] * kLog2e;
+        const float ms = fmaxf(m, s2);
+        f = __builtin_amdgcn_exp2f(m - ms);
+        l = __builtin_fmaf(l, f, __builtin_amdgcn_exp2f(s2 - ms));
+      }
+      const float inv = f / l;
       uint16_t* op = a.o + b * a.so[0] + qi * a.so[1] + h * 64 + 4 * fg;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) st4(op + 16 * dt, acc[dt], inv);
@@ -465,9 +479,12 @@ __global__ __launch_bounds__(64) void attn_extend_merge_k(AttnExtendArgs a) {
   const float* wo = a.ws + (part0 * kQT + row) * 64 + d;
   const float* wm = a.ws + (int64_t)a.nparts * (kQT * 64) + part0 * kQT + row;
   const float* wl = wm + (int64_t)a.nparts * kQT;
-  float M = -INFINITY;
+  // sinks: as attn_decode_merge_k -- the sink's partial (m = sinks[h] * log2e, l = 1, o = 0) is taken first
+  const bool sink = a.sinks != nullptr;
+  const float s2 = sink ? a.sinks[h] * kLog2e : -INFINITY;
+  float M = s2;
   for (int s = 0; s < a.nsplit; ++s) M = fmaxf(M, wm[s * kQT]);  // the split of row L(b, t) - 1 is never empty: finite
-  float o = 0.f, L = 0.f;
+  float o = 0.f, L = sink ? __builtin_amdgcn_exp2f(s2 - M) : 0.f;
   for (int s = 0; s < a.nsplit; ++s) {
     const float ms = wm[s * kQT];
     if (ms == -INFINITY) continue;  // empty split or a row that saw nothing: its o is never read

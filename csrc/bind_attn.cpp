@@ -62,9 +62,10 @@ void attn_masks(tbamd::AttnArgs& a, const Tensor& q, int64_t B, bool causal, con
   a.klen = kl.data_ptr<int>();
 }
 
-// -> (o [B, N, H, 64] contiguous, lse [B, H, N] f32)
+// -> (o [B, N, H, 64] contiguous, lse [B, H, N] f32).  sinks (optional): f32 [H], one raw logit per query head
+// in every row's softmax denominator (csrc/attention.hip); lse then includes it.
 std::vector<Tensor> attn_forward(const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool causal,
-                                 const optional<Tensor>& key_lengths, int64_t window) {
+                                 const optional<Tensor>& key_lengths, int64_t window, const optional<Tensor>& sinks) {
   const at::DeviceGuard guard(q.device());
   const int64_t B = q.size(0), H = q.size(1), N = q.size(2);
   TORCH_CHECK(N >= 1 && B * H * ((N + 127) / 128) < (int64_t)INT32_MAX, "attention: bad size");
@@ -81,14 +82,16 @@ std::vector<Tensor> attn_forward(const Tensor& q, const Tensor& k, const Tensor&
   a.lse = lse.data_ptr<float>();
   a.B = (int)B, a.H = (int)H, a.N = (int)N, a.scale = (float)scale;
   attn_masks(a, q, B, causal, key_lengths, window);
+  a.sinks = sinks_of(sinks, H, q, "attention");
   tbamd::attn_fwd(a, cur_stream());
   return {o, lse};
 }
 
-// writes dq, dk, dv (views, e.g. slices of one packed dqkv buffer)
-void attn_backward(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o, const Tensor& dout,
-                   const Tensor& lse, double scale, const Tensor& dq, const Tensor& dk, const Tensor& dv, bool causal,
-                   const optional<Tensor>& key_lengths, int64_t window) {
+// writes dq, dk, dv (views, e.g. slices of one packed dqkv buffer); with sinks (the forward's) -> dsinks f32 [H]
+optional<Tensor> attn_backward(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o, const Tensor& dout,
+                               const Tensor& lse, double scale, const Tensor& dq, const Tensor& dk, const Tensor& dv,
+                               bool causal, const optional<Tensor>& key_lengths, int64_t window,
+                               const optional<Tensor>& sinks) {
   const at::DeviceGuard guard(q.device());
   const int64_t B = q.size(0), H = q.size(1), N = q.size(2);
   tbamd::AttnArgs a{};
@@ -111,7 +114,14 @@ void attn_backward(const Tensor& q, const Tensor& k, const Tensor& v, const Tens
   a.delta = delta.data_ptr<float>();
   a.B = (int)B, a.H = (int)H, a.N = (int)N, a.scale = (float)scale;
   attn_masks(a, q, B, causal, key_lengths, window);
+  a.sinks = sinks_of(sinks, H, q, "attention");
+  optional<Tensor> dsinks;
+  if (a.sinks != nullptr) {
+    dsinks = at::empty({H}, lse.options());
+    a.dsinks = dsinks->data_ptr<float>();
+  }
   tbamd::attn_bwd(a, cur_stream());
+  return dsinks;
 }
 
 // ---- KV-cache decoding (csrc/attention_decode.hip).  Cache: [B, Hkv, cap, 64] bf16 views (checked as
@@ -248,7 +258,7 @@ Tensor decode_args(tbamd::AttnDecodeArgs& a, const Tensor* qkv, int64_t H, int64
 // at least attn_decode_workspace floats; by default it comes from the caching allocator.
 Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const Tensor& v_cache, const Tensor& lengths,
                    int64_t add, double scale, const optional<Tensor>& workspace, int64_t kv_heads, int64_t window,
-                   bool rolling, double k_scale, double v_scale) {
+                   bool rolling, double k_scale, double v_scale, const optional<Tensor>& sinks) {
   const at::DeviceGuard guard(k_cache.device());
   const int64_t H = heads, Hkv = kv_heads_of(heads, kv_heads, "attention decode");
   const bool packed = q.dim() == 3 && q.size(1) == 1 && q.size(2) == packed_qkv_width(H, Hkv);
@@ -267,6 +277,7 @@ Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const 
   a.ws = ws.data_ptr<float>();
   a.ring = rolling ? 1 : 0;
   a.window = rolling ? ring_window(window, a.cap, 1, "attention decode") : cache_window(window, a.cap, "attention decode");
+  a.sinks = sinks_of(sinks, H, k_cache, "attention decode");
   tbamd::attn_decode(a, cur_stream());
   return o;
 }
@@ -276,13 +287,14 @@ Tensor attn_decode(const Tensor& q, int64_t heads, const Tensor& k_cache, const 
 // o [B, H*64].  Same bits, output and caches, as attn_kv_append followed by attn_decode(add = 1).
 Tensor attn_decode_append(const Tensor& qkv, int64_t heads, const Tensor& k_cache, const Tensor& v_cache,
                           const Tensor& positions, double scale, int64_t kv_heads, int64_t window, bool rolling,
-                          double k_scale, double v_scale) {
+                          double k_scale, double v_scale, const optional<Tensor>& sinks) {
   const at::DeviceGuard guard(k_cache.device());
   const int64_t H = heads, Hkv = kv_heads_of(heads, kv_heads, "attention decode");
   tbamd::AttnDecodeArgs a{};
   Tensor o = decode_args(a, &qkv, H, Hkv, k_cache, v_cache, positions, "positions", 1, scale, k_scale, v_scale);
   a.ring = rolling ? 1 : 0;
   a.window = rolling ? ring_window(window, a.cap, 1, "attention decode") : cache_window(window, a.cap, "attention decode");
+  a.sinks = sinks_of(sinks, H, k_cache, "attention decode");
   Tensor ws;  // a single chunk is normalised in the split kernel: no partials
   if (tbamd::attn_decode_chunks(a.cap) > 1) {
     ws = at::empty({tbamd::attn_decode_workspace(a.B, a.H, a.cap)}, k_cache.options().dtype(at::kFloat));
@@ -556,7 +568,7 @@ std::tuple<Tensor, Tensor, Tensor> qk_norm_rope_packed_bwd(const Tensor& qkv, co
 // from the caching allocator (none at all with a single key split).
 Tensor attn_extend(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& positions,
                    double scale, const optional<Tensor>& workspace, int64_t kv_heads, int64_t window, bool rolling,
-                   double k_scale, double v_scale) {
+                   double k_scale, double v_scale, const optional<Tensor>& sinks) {
   const at::DeviceGuard guard(k_cache.device());
   TORCH_CHECK(k_cache.dim() == 4, "attention extend: cache must be [B, H, cap, 64]");
   const bool fp8 = cache_fp8(k_cache, v_cache, k_scale, v_scale, "attention extend");
@@ -594,6 +606,7 @@ Tensor attn_extend(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache
   if (fp8) a.fp8 = 1, a.scale = (float)scale * (float)k_scale, a.vscale = (float)v_scale;
   a.ring = rolling ? 1 : 0;
   a.window = rolling ? ring_window(window, cap, T, "attention extend") : cache_window(window, cap, "attention extend");
+  a.sinks = sinks_of(sinks, H, k_cache, "attention extend");
   tbamd::attn_extend(a, cur_stream());
   return o;
 }
@@ -602,20 +615,21 @@ Tensor attn_extend(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache
 
 void register_attn(pybind11::module& m) {
   m.def("attn_forward", &attn_forward, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
-        py::arg("causal") = false, py::arg("key_lengths") = py::none(), py::arg("window") = 0);
+        py::arg("causal") = false, py::arg("key_lengths") = py::none(), py::arg("window") = 0,
+        py::arg("sinks") = py::none());
   m.def("attn_backward", &attn_backward, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("dout"),
         py::arg("lse"), py::arg("scale"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("causal") = false,
-        py::arg("key_lengths") = py::none(), py::arg("window") = 0);
+        py::arg("key_lengths") = py::none(), py::arg("window") = 0, py::arg("sinks") = py::none());
   m.def("attn_kv_append", &attn_kv_append, py::arg("qkv"), py::arg("heads"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("positions"), py::arg("kv_heads") = 0, py::arg("rolling") = false, py::arg("lengths") = py::none(),
         py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0);
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("heads"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("lengths"), py::arg("add"), py::arg("scale"), py::arg("workspace") = py::none(),
         py::arg("kv_heads") = 0, py::arg("window") = 0, py::arg("rolling") = false, py::arg("k_scale") = 1.0,
-        py::arg("v_scale") = 1.0);
+        py::arg("v_scale") = 1.0, py::arg("sinks") = py::none());
   m.def("attn_decode_append", &attn_decode_append, py::arg("qkv"), py::arg("heads"), py::arg("k_cache"),
         py::arg("v_cache"), py::arg("positions"), py::arg("scale"), py::arg("kv_heads") = 0, py::arg("window") = 0,
-        py::arg("rolling") = false, py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0);
+        py::arg("rolling") = false, py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0, py::arg("sinks") = py::none());
   m.def("rows_linear", &rows_linear, py::arg("x"), py::arg("weight"), py::arg("bias") = py::none(),
         py::arg("gamma") = py::none(), py::arg("beta") = py::none(), py::arg("eps") = 0.0, py::arg("epi") = 0,
         py::arg("residual") = py::none(), py::arg("out") = py::none(), py::arg("rms") = false);
@@ -637,7 +651,7 @@ void register_attn(pybind11::module& m) {
         py::arg("positions") = py::none(), py::arg("kv_heads") = 0);
   m.def("attn_extend", &attn_extend, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("positions"),
         py::arg("scale"), py::arg("workspace") = py::none(), py::arg("kv_heads") = 0, py::arg("window") = 0,
-        py::arg("rolling") = false, py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0);
+        py::arg("rolling") = false, py::arg("k_scale") = 1.0, py::arg("v_scale") = 1.0, py::arg("sinks") = py::none());
   // knobs and workspace sizes
   m.def("attn_set_head_mask", [](int64_t m) { return (int64_t)tbamd::attn_set_head_mask((int)m); });
   m.def("attn_decode_workspace", [](int64_t B, int64_t H, int64_t cap) {

@@ -100,6 +100,16 @@ inline int ring_window(int64_t window, int64_t R, int64_t T, const char* what) {
   TORCH_CHECK(T <= R - window + 1, what, ": ", T, " new rows need a ring of at least window + ", T - 1, " rows, not ", R);
   return (int)window;
 }
+// ---- attention sinks: an optional f32 [H] tensor (one raw logit per QUERY head) on the device of `like`, read
+// by the kernels.  Returns its pointer, or null when none is given.
+inline const float* sinks_of(const optional<Tensor>& sinks, int64_t heads, const Tensor& like, const char* what) {
+  if (!given(sinks)) return nullptr;
+  check_cuda(*sinks, "sinks");
+  TORCH_CHECK(sinks->scalar_type() == at::kFloat && sinks->is_contiguous() && sinks->numel() == heads, what,
+              ": sinks must be contiguous f32 with one element per query head (", heads, ")");
+  TORCH_CHECK(sinks->device() == like.device(), what, ": sinks must be on the device of the inputs");
+  return sinks->data_ptr<float>();
+}
 // elements of a packed q | k | v row, head dim 64
 inline int64_t packed_qkv_width(int64_t heads, int64_t hkv) { return (heads + 2 * hkv) * 64; }
 

@@ -283,12 +283,23 @@ struct AttnArgs {
   // sliding window (0: none; needs causal): a query whose key limit is hi = min(len, i + 1) sees keys
   // max(0, hi - window) <= j < hi.  A host value; windowed calls always run the 128-row kernels.
   int window;
+  // attention sinks (null: none): f32 [H] in device memory, one raw logit per QUERY head (not multiplied by
+  // scale) that joins every row's softmax denominator and adds nothing to its output:
+  //   M = max(max_j s_ij, sinks[h]),  p_j = exp(s_ij - M) / (sum_j exp(s_ij - M) + exp(sinks[h] - M)).
+  // The sink has no position: no mask hides it.  lse includes it, so dq / dk / dv are what the backward
+  // kernels compute from lse and delta; the backward also writes dsinks[H] (csrc/attention_sink.hip):
+  //   dsinks[h] = -sum over b, i < N of exp(sinks[h] - lse[b][h][i]) * delta[b][h][i].
+  // Calls with sinks always run the 128-row forward kernel.
+  const float* sinks;
+  float* dsinks;
 };
 int attn_supported(int D);
 // whole-head kernel mask (1 forward, 4 dK/dV); mask < 0 only reads it.  Returns the previous mask.
 int attn_set_head_mask(int mask);
 void attn_fwd(const AttnArgs& a, hipStream_t st);
 void attn_bwd(const AttnArgs& a, hipStream_t st);
+// dsinks of AttnArgs from a.sinks, a.lse and a.delta (attn_bwd launches it behind the dQ pass, which writes delta)
+void attn_bwd_dsink(const AttnArgs& a, hipStream_t st);
 
 // ---- KV-cache incremental decoding (csrc/attention_decode.hip; head dim 64, bf16) ----
 // Grouped-query attention: H query heads share Hkv key / value heads, Hkv divides H, G = H / Hkv,
@@ -346,6 +357,10 @@ struct AttnDecodeArgs {
   // written.  kinv / vinv: the quantiser's factors for the row attn_decode_append takes from qkv.
   int fp8;
   float vscale, kinv, vinv;
+  // attention sinks (null: none): f32 [H] in device memory, read by the kernels; head h's raw logit enters
+  // where its row is normalised -- the merge kernel and the fused single-chunk epilogue -- as one more
+  // partial (m = sinks[h] * log2e, l = 1, o = 0).  Partials, workspace and grids do not change.
+  const float* sinks;
 };
 // query heads per wave: 0 = the default policy (the largest of 4, 3, 2 that divides G and leaves the
 // grid enough waves, else 1: a function of B, H, Hkv, cap and the chunk size only), otherwise a
@@ -488,6 +503,8 @@ struct AttnExtendArgs {
   // the accumulator times vscale before the store or the partial
   int fp8;
   float vscale;
+  // attention sinks (null: none): as AttnDecodeArgs -- in the single-split store and in the merge kernel
+  const float* sinks;
 };
 // keys per split: 0 = the default policy (split only when B * H * ceil(T / 16) cannot occupy the
 // chip), otherwise a forced size (a multiple of 8, >= 8; at or above cap: one split); n < 0 only

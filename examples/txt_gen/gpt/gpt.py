@@ -51,6 +51,7 @@ class Config(BaseConfig):
     rolling: bool = False  # the sample's KV cache keeps only about `window` rows per layer (needs window > 0)
     kv_dtype: str = ""  # "fp8": the sample's KV cache holds e4m3 codes, scales calibrated on the prompt
     qk_norm: bool = False  # an RMSNorm over every query and key head ahead of the rotation (models/gpt.py)
+    sinks: bool = False  # attention sinks: a learned logit per head in every softmax denominator (models/gpt.py)
     experts: int = 8  # mlp: moe -- the experts of every layer's mixture (models/vit.py MoE)
     top_k: int = 2  # mlp: moe -- the experts each token is sent to
     aux_coef: float = 0.01  # mlp: moe -- the weight of the load-balancing loss (MoE.aux_loss, summed over the layers)
@@ -70,6 +71,7 @@ def main(conf: Config) -> None:
         raise ValueError(f"{conf.text or 'README.md'}: {data.numel()} bytes, need more than seq_len = {conf.seq_len}")
     net = getattr(gpt, conf.arch)(vocab=256, max_len=conf.seq_len, pos=conf.pos, norm=conf.norm, mlp=conf.mlp,
                                   window=conf.window or None, qk_norm=conf.qk_norm,
+                                  **({"sinks": True} if conf.sinks else {}),
                                   **({"experts": conf.experts, "top_k": conf.top_k} if conf.mlp == "moe" else {}))
     model = prepare_model(net, conf, channels_last=False)
     net = getattr(model, "module", model)

@@ -94,6 +94,15 @@ rotates (``ops.attention.qk_norm_rope_packed``, csrc/qk_norm_rope.hip) -- so ``p
 launch for it on any path, ``pos="learned"`` ones one per layer -- and everything above keeps its meaning: a
 cache holds normalised, rotated keys.  ``qk_norm=False`` (the default) is everything above unchanged.
 
+Attention sinks (``TransformerLM(..., sinks=True)``; gpt-oss): every layer owns ``blocks[i].attn.sinks``, an f32
+``[heads]`` parameter -- one learned logit per query head that joins every row's softmax denominator and adds nothing
+to its output (ops/attention.py states the rule), so a query can put probability mass "nowhere" instead of on the
+first token, which is what keeps windowed attention stable at long context.  It is initialised to zeros without an
+RNG draw, stays f32 under dtype casts like the norm weights, and is passed to every attention call: ``loss``,
+``prefill``, ``decode_step``, ``extend`` and ``generate`` keep their meaning with ``graph=True``, ``cache=``, ``draft=`` (the two
+models may differ in ``sinks``), ``fused=True``, ``rolling=True`` and an fp8 cache; a :class:`KVCache` is unchanged.
+``sinks=False`` (the default) is everything above unchanged: the same parameters and the same RNG stream.
+
 Mixture of experts (``TransformerLM(..., mlp="moe", experts=8, top_k=2)``; Mixtral, gpt-oss, Qwen 3 MoE): every
 MLP is a :class:`~torchbooster_amd.models.vit.MoE` -- a bias-free f32 router, the ``top_k`` largest logits per
 token, softmax gates over those, ``experts`` SwiGLU experts of hidden width ``int(dim * mlp_ratio)`` -- whose
@@ -214,10 +223,12 @@ class TransformerLM(nn.Module):
                  kv_heads: Optional[int] = None, *, pos: str = "learned", rope_base: float = 10000.0,
                  norm: str = "layer", mlp: str = "gelu", bias: bool = True,
                  window: Union[None, int, Sequence[Optional[int]]] = None, qk_norm: bool = False,
-                 experts: int = 8, top_k: int = 2) -> None:
+                 experts: int = 8, top_k: int = 2, sinks: bool = False) -> None:
         super().__init__()
         if not isinstance(qk_norm, bool):
             raise ValueError(f"qk_norm must be a bool, not {qk_norm!r}")
+        if not isinstance(sinks, bool):
+            raise ValueError(f"sinks must be a bool, not {sinks!r}")
         if pos not in ("learned", "rope"):
             raise ValueError(f"pos must be 'learned' or 'rope', not {pos!r}")
         if window is None or isinstance(window, int):
@@ -238,6 +249,8 @@ class TransformerLM(nn.Module):
             kw.update(norm=norm, mlp=mlp, bias=bias)
         if qk_norm:
             kw["qk_norm"] = True
+        if sinks:  # every layer owns blocks[i].attn.sinks, an f32 [heads] parameter (models/vit.py Attention)
+            kw["sinks"] = True
         if mlp == "moe":  # every MLP a mixture of `experts` SwiGLU experts, `top_k` per token (models/vit.py MoE)
             kw.update(experts=experts, top_k=top_k)
         # (no window: the calls it always made)
@@ -633,14 +646,14 @@ def kv_scales(model: TransformerLM, tokens: Tensor, lengths: Optional[Tensor] = 
 
 def gpt_tiny(vocab: int = 256, max_len: int = 128, pos: str = "learned", *, norm: str = "layer", mlp: str = "gelu",
              bias: bool = True, kv_heads: Optional[int] = None, mlp_ratio: float = 4.0, window=None,
-             qk_norm: bool = False, experts: int = 8, top_k: int = 2) -> TransformerLM:
+             qk_norm: bool = False, experts: int = 8, top_k: int = 2, sinks: bool = False) -> TransformerLM:
     return TransformerLM(vocab, 128, 2, 2, max_len, mlp_ratio, kv_heads, pos=pos, norm=norm, mlp=mlp, bias=bias,
-                         window=window, qk_norm=qk_norm, experts=experts, top_k=top_k)
+                         window=window, qk_norm=qk_norm, experts=experts, top_k=top_k, sinks=sinks)
 
 
 def gpt2_small(vocab: int = 50257, max_len: int = 1024, pos: str = "learned", *, norm: str = "layer",
                mlp: str = "gelu", bias: bool = True, kv_heads: Optional[int] = None,
                mlp_ratio: float = 4.0, window=None, qk_norm: bool = False, experts: int = 8,
-               top_k: int = 2) -> TransformerLM:
+               top_k: int = 2, sinks: bool = False) -> TransformerLM:
     return TransformerLM(vocab, 768, 12, 12, max_len, mlp_ratio, kv_heads, pos=pos, norm=norm, mlp=mlp, bias=bias,
-                         window=window, qk_norm=qk_norm, experts=experts, top_k=top_k)
+                         window=window, qk_norm=qk_norm, experts=experts, top_k=top_k, sinks=sinks)

@@ -132,14 +132,22 @@ class Attention(nn.Module):
     ``qk_eps``, ahead of the rotation -- ``q_norm`` / ``k_norm`` (:class:`~torchbooster_amd.ops.norm.RMSNorm`
     of the head dim) only hold the two weights, f32 under dtype casts and initialised to ones without an RNG
     draw.  It runs inside :meth:`rotate` (``ops.attention.qk_norm_rope_packed``: one launch for norm and
-    rotation, the norm alone without ``rope``), hence on every path, and a cache holds normalised keys."""
+    rotation, the norm alone without ``rope``), hence on every path, and a cache holds normalised keys.
+
+    ``sinks`` (``False``: nothing changes): attention sinks (ops/attention.py; gpt-oss) -- ``self.sinks`` is an f32
+    ``[heads]`` parameter, one logit per query head that joins every row's softmax denominator and adds nothing
+    to its output.  It is initialised to zeros without an RNG draw, stays f32 under dtype casts, and is passed
+    to every attention call below: training, prefill, decode step (``fused`` or not) and extend.  A cache is
+    unchanged."""
 
     def __init__(self, dim: int, heads: int, causal: bool = False, kv_heads: Optional[int] = None,
                  rope: Optional[Rope] = None, bias: bool = True, window: Optional[int] = None,
-                 qk_norm: bool = False, qk_eps: float = 1e-6) -> None:
+                 qk_norm: bool = False, qk_eps: float = 1e-6, sinks: bool = False) -> None:
         super().__init__()
         if not isinstance(qk_norm, bool):
             raise ValueError(f"qk_norm must be a bool, not {qk_norm!r}")
+        if not isinstance(sinks, bool):
+            raise ValueError(f"sinks must be a bool, not {sinks!r}")
         if window is not None:
             if isinstance(window, bool) or not isinstance(window, int) or window < 1:
                 raise ValueError(f"window must be None or an int >= 1, not {window!r}")
@@ -161,13 +169,23 @@ class Attention(nn.Module):
         if qk_norm:
             self.q_norm = RMSNorm(self.hd, float(qk_eps))
             self.k_norm = RMSNorm(self.hd, float(qk_eps))
+        self.sinks = nn.Parameter(torch.zeros(heads)) if sinks else None
+
+    def _apply(self, fn, recurse=True):
+        super()._apply(fn, recurse)
+        p = self.sinks  # the kernels read f32 sinks: as RMSNorm keeps its weight
+        if p is not None and p.dtype != torch.float32:
+            p.data = p.data.float()
+        return self
 
     def _kw(self) -> dict:
-        """``kv_heads`` / ``window`` where the layer has them: plain MHA without a window makes the calls it
-        always made."""
+        """``kv_heads`` / ``window`` / ``sinks`` where the layer has them: plain MHA without a window or sinks
+        makes the calls it always made."""
         kw = {} if self.kv_heads == self.heads else {"kv_heads": self.kv_heads}
         if self.window is not None:
             kw["window"] = self.window
+        if self.sinks is not None:
+            kw["sinks"] = self.sinks
         return kw
 
     def rotate(self, qkv: Tensor, positions: Optional[Tensor] = None, inplace: bool = False) -> Tensor:
@@ -361,7 +379,8 @@ class Block(nn.Module):
     ``norm="rms"``: ``ln1`` / ``ln2`` are :class:`~torchbooster_amd.ops.norm.RMSNorm` (the attribute names
     stay: the ``(x, pending)`` protocol of ``forward`` is the same); ``mlp="swiglu"``: ``self.mlp`` is a
     :class:`SwiGLU` of hidden width ``int(dim * mlp_ratio)``; ``bias=False``: no bias in ``qkv``, ``proj`` and
-    the MLP's linears -- together the Llama-style block.  ``window``: the sliding window of :class:`Attention`; ``qk_norm``: its QK-norm.
+    the MLP's linears -- together the Llama-style block.  ``window``: the sliding window of :class:`Attention`; ``qk_norm``: its QK-norm;
+    ``sinks``: its attention sinks.
     ``mlp="moe"``: ``self.mlp`` is a :class:`MoE` of ``experts`` SwiGLU experts of that hidden width, ``top_k`` per
     token (its router and experts never have a bias; ``bias`` then governs ``qkv`` and ``proj`` alone);
     ``forward_rows`` has no few-row expert kernel and raises ``ValueError``."""
@@ -369,7 +388,7 @@ class Block(nn.Module):
     def __init__(self, dim: int, heads: int, mlp_ratio: float = 4.0, causal: bool = False,
                  kv_heads: Optional[int] = None, rope: Optional[Rope] = None, norm: str = "layer",
                  mlp: str = "gelu", bias: bool = True, window: Optional[int] = None,
-                 qk_norm: bool = False, experts: int = 8, top_k: int = 2) -> None:
+                 qk_norm: bool = False, experts: int = 8, top_k: int = 2, sinks: bool = False) -> None:
         super().__init__()
         if mlp not in ("gelu", "swiglu", "moe"):
             raise ValueError(f"mlp must be 'gelu', 'swiglu' or 'moe', not {mlp!r}")
@@ -377,7 +396,8 @@ class Block(nn.Module):
             _check_experts(experts, top_k)
         self.ln1 = make_norm(norm, dim)
         self.attn = Attention(dim, heads, causal, kv_heads, rope, bias=bias, window=window,
-                              **({"qk_norm": qk_norm} if qk_norm is not False else {}))
+                              **({"qk_norm": qk_norm} if qk_norm is not False else {}),
+                              **({"sinks": sinks} if sinks is not False else {}))
         self.ln2 = make_norm(norm, dim)
         hidden = int(dim * mlp_ratio)
         if mlp == "moe":

@@ -151,6 +151,30 @@ other head dims and ``TBAMD_FORCE_REFERENCE=1`` take the PyTorch path, which deq
 (what stock PyTorch does with a pair that is not e4m3 / e4m3 is unchanged).  With bf16 caches every call is the call
 it was.
 
+Attention sinks (``sinks=`` on :func:`attention`, :func:`attention_packed`, :func:`attention_ref` and the four decode
+/ extend functions; gpt-oss).  ``sinks`` is a float32 ``[H]`` tensor on the inputs' device, one learned logit per
+QUERY head (``kv_heads`` does not change that), and one rule holds on every path: with ``s_ij = scale * q_i . k_j``
+over the keys row ``i`` sees,
+
+    ``M = max(max_j s_ij, sinks[h])``,  ``p_j = exp(s_ij - M) / (sum_j exp(s_ij - M) + exp(sinks[h] - M))``,
+    ``o_i = sum_j p_j v_j``
+
+-- the sink takes part in the denominator and contributes nothing to the output, so a row can put probability mass
+"nowhere".  It is a raw logit, NOT multiplied by ``scale`` (the Hugging Face ``sinks`` column), it has no position and
+no mask, window or ring hides it; which keys are visible is unchanged.  Natively the sink is one more partial
+``(m = sinks[h] * log2e, l = 1, o = 0)`` folded in where a row is normalised: behind the key loop of the 128-row
+forward kernel, which calls with sinks always take (a ``SINK`` instantiation; the whole-head kernel has none), in the
+decode / extend merge kernels and in their single-chunk / single-split stores, so ``fused=True`` stays bit-equal to
+``fused=False``.  The stored log-sum-exp includes the sink: dQ / dK / dV come from the backward kernels as they are, and
+``dsinks[h] = -sum_{b, i} exp(sinks[h] - lse[b, h, i]) * rowsum(dO * O)[b, h, i]`` from one more kernel
+(csrc/attention_sink.hip: one workgroup per head, a fixed reduction order, no atomics, bit-deterministic).  Rows at
+padded positions are included like any other -- the caller masks their loss, so their ``dO`` is zero.  ``sinks`` must be
+finite (NaN propagates); a sink so negative that its term underflows adds an exact 0 and leaves the bits of the call
+without sinks.  The kernels read the tensor from device memory: no host sync, capturable, and a replay follows in-place
+changes.  The PyTorch path writes the rule with the sink as an extra logit column that is dropped after the softmax
+(fp32, fp64 for fp64 inputs; ``F.scaled_dot_product_attention`` cannot express it).  A wrong shape, dtype or device
+raises ``ValueError``; ``sinks=None`` everywhere is the code as it was: the same calls, kernels and bits.
+
 Rotary position embeddings (csrc/rope.hip): :func:`rope_packed` rotates the q and k parts of a packed
 projection by the angles :func:`rope_table` holds, before any of the functions above reads it -- so the
 training path, the prefill, the append, the decode and the extend all see rotated q / k, a cache holds
@@ -216,14 +240,60 @@ def _check_window(window, causal: bool, N: int) -> Optional[int]:
     return window
 
 
+def _check_sinks(sinks, H: int, like: Tensor) -> None:
+    """``sinks`` of the module docstring: ``None`` or a float32 ``[H]`` tensor on the inputs' device."""
+    if sinks is None:
+        return
+    if not isinstance(sinks, Tensor) or sinks.dtype != torch.float32 or tuple(sinks.shape) != (H,) \
+            or sinks.device != like.device:
+        raise ValueError(f"sinks must be a float32 tensor of shape [H] = [{H}] on the device of the inputs")
+
+
+def _sink_kw(sinks: Optional[Tensor]) -> dict:
+    """``sinks`` as the trailing keyword of the native calls and of the PyTorch paths; none adds nothing: the
+    calls they always made."""
+    return {} if sinks is None else {"sinks": sinks.contiguous()}
+
+
+def _softmax_sink(s: Tensor, sinks: Optional[Tensor]) -> Tensor:
+    """The softmax over the last dim of the masked scores ``s``.  ``sinks`` (shaped to broadcast against
+    ``s[..., :1]``, its heads where ``s`` has them): the rule of the module docstring written out -- the sink is
+    one more logit column, which is dropped after the softmax."""
+    if sinks is None:
+        return torch.softmax(s, dim=-1)
+    col = sinks.to(s.dtype).expand(*s.shape[:-1], 1)
+    return torch.softmax(torch.cat((s, col), dim=-1), dim=-1)[..., :-1]
+
+
+def _attn_sinks(q: Tensor, k: Tensor, v: Tensor, scale: float, causal: bool, key_lengths: Optional[Tensor],
+                window: Optional[int], sinks: Tensor) -> Tensor:
+    """The PyTorch path of :func:`attention` with ``sinks`` ([B, H, N, D] inputs; ``_sdpa`` cannot express a
+    sink): both products in the inputs' dtype, the softmax with its extra column in fp32 (fp64 for fp64
+    inputs), under autograd."""
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    s = (torch.matmul(q, k.transpose(-1, -2)) * scale).to(ct)
+    m = _visible(q.shape[-2], q.device, causal, key_lengths, window)
+    if m is not None:
+        s = s.masked_fill(~m, float("-inf"))
+    p = _softmax_sink(s, sinks.view(1, -1, 1, 1)).to(q.dtype)
+    return torch.matmul(p, v)
+
+
 def attention_ref(q: Tensor, k: Tensor, v: Tensor, scale: Optional[float] = None, *, causal: bool = False,
-                  key_lengths: Optional[Tensor] = None, window: Optional[int] = None) -> Tensor:
+                  key_lengths: Optional[Tensor] = None, window: Optional[int] = None,
+                  sinks: Optional[Tensor] = None) -> Tensor:
     """softmax(q kᵀ · scale) v over [..., N, D] tensors (f32 softmax); with a mask, over
-    [B, H, N, D] (the fp32 oracle of the masked kernels when given fp32 inputs)."""
+    [B, H, N, D] (the fp32 oracle of the masked kernels when given fp32 inputs).  ``sinks`` (float32
+    ``[H]``, [B, H, N, D] inputs): the attention sinks of the module docstring."""
     scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else scale
     if window is not None and not causal:
         _window(window)
         raise ValueError("window needs causal=True")
+    if sinks is not None:
+        if q.dim() != 4:
+            raise ValueError("sinks need [B, H, N, D] inputs")
+        _check_sinks(sinks, q.shape[1], q)
+        return _attn_sinks(q, k, v, scale, causal, key_lengths, _window(window, q.shape[-2]), sinks)
     s = torch.matmul(q, k.transpose(-1, -2)) * scale
     m = _visible(q.shape[-2], q.device, causal, key_lengths, _window(window, q.shape[-2]))
     if m is not None:
@@ -254,56 +324,57 @@ class _AttnFn(torch.autograd.Function):
     """q, k, v: [B, H, N, 64] views -> o [B, N, H, 64] (contiguous)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale, causal=False, key_lengths=None, window=None):
+    def forward(ctx, q, k, v, scale, causal=False, key_lengths=None, window=None, sinks=None):
         kw = {} if window is None else {"window": window}  # no window: the call it always made
-        o, lse = native().attn_forward(q, k, v, scale, causal, key_lengths, **kw)
-        ctx.save_for_backward(q, k, v, o, lse, key_lengths)
+        o, lse = native().attn_forward(q, k, v, scale, causal, key_lengths, **kw, **_sink_kw(sinks))
+        ctx.save_for_backward(q, k, v, o, lse, key_lengths, sinks)
         ctx.scale, ctx.causal, ctx.kw = scale, causal, kw
         return o
 
     @staticmethod
     @once_differentiable
     def backward(ctx, do):
-        q, k, v, o, lse, key_lengths = ctx.saved_tensors
+        q, k, v, o, lse, key_lengths, sinks = ctx.saved_tensors
         do = do.contiguous()
         dq = torch.empty(q.shape, dtype=q.dtype, device=q.device)
         dk = torch.empty(k.shape, dtype=k.dtype, device=k.device)
         dv = torch.empty(v.shape, dtype=v.dtype, device=v.device)
-        native().attn_backward(q, k, v, o.permute(0, 2, 1, 3), do.permute(0, 2, 1, 3), lse, ctx.scale, dq, dk, dv,
-                               ctx.causal, key_lengths, **ctx.kw)
-        return dq, dk, dv, None, None, None, None
+        # (with sinks: their gradient, f32 [H], from the one extra kernel; None without)
+        ds = native().attn_backward(q, k, v, o.permute(0, 2, 1, 3), do.permute(0, 2, 1, 3), lse, ctx.scale, dq, dk, dv,
+                                    ctx.causal, key_lengths, **ctx.kw, **_sink_kw(sinks))
+        return dq, dk, dv, None, None, None, None, ds
 
 
 class _AttnPackedFn(torch.autograd.Function):
     """qkv: [B, N, 3*H*64] -> [B, N, H*64]; the gradient is one packed buffer."""
 
     @staticmethod
-    def forward(ctx, qkv, heads, scale, causal=False, key_lengths=None, window=None):
+    def forward(ctx, qkv, heads, scale, causal=False, key_lengths=None, window=None, sinks=None):
         B, N, E3 = qkv.shape
         D = E3 // (3 * heads)
         t = qkv.view(B, N, 3, heads, D)
         q, k, v = (t[:, :, i].transpose(1, 2) for i in range(3))
         kw = {} if window is None else {"window": window}  # no window: the call it always made
-        o, lse = native().attn_forward(q, k, v, scale, causal, key_lengths, **kw)
-        ctx.save_for_backward(qkv, o, lse, key_lengths)
+        o, lse = native().attn_forward(q, k, v, scale, causal, key_lengths, **kw, **_sink_kw(sinks))
+        ctx.save_for_backward(qkv, o, lse, key_lengths, sinks)
         ctx.cfg, ctx.kw = (heads, D, scale, causal), kw
         return o.view(B, N, heads * D)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, do):
-        qkv, o, lse, key_lengths = ctx.saved_tensors
+        qkv, o, lse, key_lengths, sinks = ctx.saved_tensors
         heads, D, scale, causal = ctx.cfg
         B, N, _ = qkv.shape
         t = qkv.view(B, N, 3, heads, D)
         dqkv = torch.empty_like(qkv)
         g = dqkv.view(B, N, 3, heads, D)
         do = do.contiguous().view(B, N, heads, D)
-        native().attn_backward(t[:, :, 0].transpose(1, 2), t[:, :, 1].transpose(1, 2), t[:, :, 2].transpose(1, 2),
-                               o.permute(0, 2, 1, 3), do.permute(0, 2, 1, 3), lse, scale,
-                               g[:, :, 0].transpose(1, 2), g[:, :, 1].transpose(1, 2), g[:, :, 2].transpose(1, 2),
-                               causal, key_lengths, **ctx.kw)
-        return dqkv, None, None, None, None, None
+        ds = native().attn_backward(t[:, :, 0].transpose(1, 2), t[:, :, 1].transpose(1, 2), t[:, :, 2].transpose(1, 2),
+                                    o.permute(0, 2, 1, 3), do.permute(0, 2, 1, 3), lse, scale,
+                                    g[:, :, 0].transpose(1, 2), g[:, :, 1].transpose(1, 2), g[:, :, 2].transpose(1, 2),
+                                    causal, key_lengths, **ctx.kw, **_sink_kw(sinks))
+        return dqkv, None, None, None, None, None, ds
 
 
 def _kv_heads(heads: int, kv_heads: Optional[int]) -> int:
@@ -333,10 +404,12 @@ def _rows(t: Tensor) -> Tensor:
 
 
 def attention(q: Tensor, k: Tensor, v: Tensor, scale: Optional[float] = None, *, causal: bool = False,
-              key_lengths: Optional[Tensor] = None, window: Optional[int] = None) -> Tensor:
+              key_lengths: Optional[Tensor] = None, window: Optional[int] = None,
+              sinks: Optional[Tensor] = None) -> Tensor:
     """[B, H, N, D] -> [B, H, N, D].  ``causal`` / ``key_lengths``: the masks of the module docstring
     (self-attention: q, k, v of one shape; lengths clamped into [1, N]).  ``window`` (needs ``causal``): the
-    sliding window of the module docstring; ``window >= N`` is ``window=None``.
+    sliding window of the module docstring; ``window >= N`` is ``window=None``.  ``sinks`` (float32 ``[H]``, one
+    logit per query head; differentiable): the attention sinks of the module docstring.
 
     Grouped-query attention: ``k`` / ``v`` may be ``[B, Hkv, N, D]`` with ``Hkv`` dividing ``H``; they are
     expanded to ``H`` heads (one copy) and dK / dV are summed over each group by autograd.  There is no
@@ -349,6 +422,14 @@ def attention(q: Tensor, k: Tensor, v: Tensor, scale: Optional[float] = None, *,
     if (causal or key_lengths is not None) and not (q.dim() == 4 and q.shape == k.shape == v.shape):
         raise ValueError("attention masks need [B, H, N, D] self-attention inputs of one shape")
     _check_lengths(key_lengths, q.shape[0], q)
+    if sinks is not None:
+        if not (q.dim() == 4 and q.shape == k.shape == v.shape):
+            raise ValueError("sinks need [B, H, N, D] self-attention inputs of one shape")
+        _check_sinks(sinks, q.shape[1], q)
+        if native_supported(q):
+            q, k, v = _rows(q), _rows(k), _rows(v)
+            return _AttnFn.apply(q, k, v, scale, bool(causal), key_lengths, window, sinks).permute(0, 2, 1, 3)
+        return _attn_sinks(q, k, v, scale, causal, key_lengths, window, sinks)
     if native_supported(q) and q.dim() == 4 and q.shape == k.shape == v.shape:
         q, k, v = _rows(q), _rows(k), _rows(v)
         if window is None:  # the call it always made
@@ -361,8 +442,8 @@ def attention(q: Tensor, k: Tensor, v: Tensor, scale: Optional[float] = None, *,
 
 def attention_packed(qkv: Tensor, heads: int, scale: Optional[float] = None, *, causal: bool = False,
                      key_lengths: Optional[Tensor] = None, kv_heads: Optional[int] = None,
-                     window: Optional[int] = None) -> Tensor:
-    """[B, N, 3*H*D] packed q|k|v (head-major inside each) -> [B, N, H*D]; masks and ``window`` as
+                     window: Optional[int] = None, sinks: Optional[Tensor] = None) -> Tensor:
+    """[B, N, 3*H*D] packed q|k|v (head-major inside each) -> [B, N, H*D]; masks, ``window`` and ``sinks`` as
     :func:`attention`.
 
     ``kv_heads`` (grouped-query attention): ``qkv`` is ``[B, N, (H + 2*Hkv)*D]``.  With ``Hkv < H`` the
@@ -372,7 +453,11 @@ def attention_packed(qkv: Tensor, heads: int, scale: Optional[float] = None, *, 
     hkv = _kv_heads(heads, kv_heads)
     window = _check_window(window, causal, qkv.shape[1])
     wkw = {} if window is None else {"window": window}  # no window: the calls it always made
-    if hkv != heads:
+    _check_sinks(sinks, heads, qkv)
+    if hkv != heads or (sinks is not None and not (qkv.dim() == 3 and qkv.shape[2] % (3 * heads) == 0
+                                                   and native_supported(qkv.view(*qkv.shape[:2], 3, heads, -1))
+                                                   and _rows_ok(qkv))):
+        # (and the PyTorch path of a call with sinks: attention() holds it)
         B, N, E = qkv.shape
         if E % (heads + 2 * hkv):
             raise RuntimeError("qkv must be [B, N, (H + 2*Hkv)*D]")
@@ -381,12 +466,14 @@ def attention_packed(qkv: Tensor, heads: int, scale: Optional[float] = None, *, 
         k, v = (_expand_kv(qkv[..., o * D:(o + hkv) * D].view(B, N, hkv, D), heads // hkv, 2).transpose(1, 2)
                 for o in (heads, heads + hkv))
         o = attention(q, k, v, 1.0 / math.sqrt(D) if scale is None else scale, causal=causal, key_lengths=key_lengths,
-                      **wkw)
+                      **wkw, **_sink_kw(sinks))
         return o.transpose(1, 2).reshape(B, N, heads * D)
     B, N, E3 = qkv.shape
     D = E3 // (3 * heads)
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     _check_lengths(key_lengths, B, qkv)
+    if sinks is not None:  # native (the other calls with sinks left above)
+        return _AttnPackedFn.apply(qkv, heads, scale, bool(causal), key_lengths, window, sinks)
     if native_supported(qkv.view(B, N, 3, heads, D)) and _rows_ok(qkv):
         return _AttnPackedFn.apply(qkv, heads, scale, bool(causal), key_lengths, *wkw.values())
     t = qkv.view(B, N, 3, heads, D).permute(2, 0, 3, 1, 4)
@@ -574,12 +661,14 @@ def _append_ref(k_cache: Tensor, v_cache: Tensor, qkv: Tensor, heads: int, posit
 
 
 def _decode_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tensor, scale: float,
-                window: Optional[int] = None, rolling: bool = False, kv_scales=None) -> Tensor:
+                window: Optional[int] = None, rolling: bool = False, kv_scales=None,
+                sinks: Optional[Tensor] = None) -> Tensor:
     """The PyTorch path of :func:`attention_decode` (softmax in fp32, or fp64 for fp64 inputs).  Hidden
     rows -- at or past the length, and below ``len - window`` -- are selected away before either product:
     a masked score is -inf whatever k held, and v is zeroed there because 0 * NaN is NaN.  A cache of
     ``Hkv < H`` heads is grouped-query attention.  ``rolling``: the same over the logical rows ``j(p)`` of the
-    ring's slots (module docstring), with the length not clamped to the row count."""
+    ring's slots (module docstring), with the length not clamped to the row count.  ``sinks``: one more logit
+    column per query head, dropped after the softmax (:func:`_softmax_sink`); it is never masked."""
     cap = k_cache.shape[2]
     if rolling:
         n = lengths.to(torch.int64).clamp_min(1)
@@ -599,10 +688,11 @@ def _decode_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tensor, sc
     if k_cache.shape[1] != H:  # query head h reads kv head h // G
         qg = q.to(ct).view(B, k_cache.shape[1], -1, D)
         s = torch.einsum("bkgd,bkjd->bkgj", qg, k_cache.to(ct)) * scale
-        p = torch.softmax(s.masked_fill(~vis[:, :, None], float("-inf")), dim=-1)
+        p = _softmax_sink(s.masked_fill(~vis[:, :, None], float("-inf")),
+                          None if sinks is None else sinks.view(1, k_cache.shape[1], -1, 1))
         return torch.einsum("bkgj,bkjd->bkgd", p, v).reshape(B, H, D).to(q.dtype)
     s = torch.einsum("bhd,bhjd->bhj", q.to(ct), k_cache.to(ct)) * scale
-    p = torch.softmax(s.masked_fill(~vis, float("-inf")), dim=-1)
+    p = _softmax_sink(s.masked_fill(~vis, float("-inf")), None if sinks is None else sinks.view(1, -1, 1))
     return torch.einsum("bhj,bhjd->bhd", p, v).to(q.dtype)
 
 
@@ -656,7 +746,7 @@ def _cache_window(window, k_cache: Tensor) -> dict:
 def attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tensor,
                      scale: Optional[float] = None, *, kv_heads: Optional[int] = None,
                      window: Optional[int] = None, rolling: bool = False,
-                     kv_scales: Optional[Tuple[float, float]] = None) -> Tensor:
+                     kv_scales: Optional[Tuple[float, float]] = None, sinks: Optional[Tensor] = None) -> Tensor:
     """One query per (batch, head): ``q`` ``[B, H, D]`` against the first ``len = clamp(lengths[b], 1, cap)``
     rows of ``k_cache`` / ``v_cache`` ``[B, Hkv, cap, D]`` -> ``[B, H, D]``.  ``kv_heads``: ``Hkv`` of
     grouped-query attention (module docstring); ``None`` is ``H``.  ``window``: only the rows
@@ -664,28 +754,32 @@ def attention_decode(q: Tensor, k_cache: Tensor, v_cache: Tensor, lengths: Tenso
     ``rolling=True`` (needs ``1 <= window <= cap``): the caches are a ring, ``len = max(lengths[b], 1)`` counts
     tokens and the query sees the slots whose logical row is in the window (module docstring).
     ``kv_scales`` (``float8_e4m3fn`` caches only; ``None``: ``(1.0, 1.0)``): the query sees the visible rows
-    dequantised, ``f32(code) * scale`` (module docstring)."""
+    dequantised, ``f32(code) * scale`` (module docstring).  ``sinks`` (float32 ``[H]``): the attention sinks of
+    the module docstring, read on the device."""
     _forward_only(q, k_cache, v_cache)
     if q.dim() != 3:
         raise RuntimeError("q must be [B, H, D]")
     B, H, D = q.shape
     hkv = _kv_heads(H, kv_heads)
+    _check_sinks(sinks, H, k_cache)
+    kkw = _sink_kw(sinks)
     wkw = _ring_kw(window, k_cache) if rolling else _cache_window(window, k_cache)
     nkw, skw = _scale_kw(_kv_scales(kv_scales, k_cache, v_cache))
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     with torch.no_grad():
         if _decode_native(q, k_cache, v_cache):
             return native().attn_decode(_rows(q), H, k_cache, v_cache, lengths, 0, scale, None, hkv,
-                                        **wkw, **nkw).view(B, H, D)
+                                        **wkw, **nkw, **kkw).view(B, H, D)
         _check_cache(k_cache, v_cache, B, hkv, D, lengths, "lengths")
-        return _decode_ref(q, k_cache, v_cache, lengths, scale, **wkw, **skw)
+        return _decode_ref(q, k_cache, v_cache, lengths, scale, **wkw, **skw, **kkw)
 
 
 def attention_decode_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
                             scale: Optional[float] = None, *, fused: bool = False,
                             kv_heads: Optional[int] = None, window: Optional[int] = None,
                             rolling: bool = False,
-                            kv_scales: Optional[Tuple[float, float]] = None) -> Tensor:
+                            kv_scales: Optional[Tuple[float, float]] = None,
+                            sinks: Optional[Tensor] = None) -> Tensor:
     """One decode step on the packed ``[B, 1, (H + 2*Hkv)*D]`` projection of the new token: append its k / v
     at row ``positions[b]``, then attend to keys ``j <= positions[b]`` -> ``[B, 1, H*D]``.  ``kv_heads``:
     ``Hkv`` of grouped-query attention (module docstring); ``None`` is ``H``.  ``window``: as
@@ -701,9 +795,12 @@ def attention_decode_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: T
     ``positions[b] mod cap`` (dropped when ``positions[b] < 0``) and ``len = max(positions[b] + 1, 1)``.
 
     ``kv_scales`` (``float8_e4m3fn`` caches only; ``None``: ``(1.0, 1.0)``): the new row is quantised as it is
-    stored and the query sees it dequantised like every other row, ``fused`` or not (module docstring)."""
+    stored and the query sees it dequantised like every other row, ``fused`` or not (module docstring).
+    ``sinks``: as :func:`attention_decode`, ``fused`` or not with the same bits."""
     _forward_only(qkv, k_cache, v_cache)
     hkv, B, _, D, scale = _packed_dims(qkv, heads, kv_heads, scale, T="1")
+    _check_sinks(sinks, heads, k_cache)
+    kkw = _sink_kw(sinks)
     wkw = _ring_kw(window, k_cache) if rolling else _cache_window(window, k_cache)
     akw = {"rolling": True} if rolling else {}  # the append's; no ring: the calls it always made
     nkw, skw = _scale_kw(_kv_scales(kv_scales, k_cache, v_cache))
@@ -712,10 +809,10 @@ def attention_decode_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: T
             qkv, C = _rows(qkv), native()
             if fused:
                 return C.attn_decode_append(qkv, heads, k_cache, v_cache, positions, scale,
-                                            hkv, **wkw, **nkw).view(B, 1, heads * D)
+                                            hkv, **wkw, **nkw, **kkw).view(B, 1, heads * D)
             C.attn_kv_append(qkv, heads, k_cache, v_cache, positions, hkv, **akw, **nkw)
             return C.attn_decode(qkv, heads, k_cache, v_cache, positions, 1, scale, None,
-                                 hkv, **wkw, **nkw).view(B, 1, heads * D)
+                                 hkv, **wkw, **nkw, **kkw).view(B, 1, heads * D)
         _check_cache(k_cache, v_cache, B, hkv, D, positions, "positions")
         if rolling:
             _append_ring_ref(k_cache, v_cache, qkv, heads, positions, hkv, None, **skw)
@@ -723,11 +820,12 @@ def attention_decode_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: T
             _append_ref(k_cache, v_cache, qkv, heads, positions, hkv, **skw)
         q = qkv[:, 0, :heads * D].reshape(B, heads, D)
         return _decode_ref(q, k_cache, v_cache, positions.to(torch.int64) + 1, scale,
-                           **wkw, **skw).reshape(B, 1, heads * D)
+                           **wkw, **skw, **kkw).reshape(B, 1, heads * D)
 
 
 def _extend_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor, scale: float,
-                window: Optional[int] = None, rolling: bool = False, kv_scales=None) -> Tensor:
+                window: Optional[int] = None, rolling: bool = False, kv_scales=None,
+                sinks: Optional[Tensor] = None) -> Tensor:
     """The PyTorch path of :func:`attention_extend` (softmax in fp32, or fp64 for fp64 inputs), sync-free.
     ``q`` ``[B, T, H, D]`` -> ``[B, T, H, D]``.  Scores are masked to -inf by ``L(b, t)``; v is zeroed at
     rows ``>= clamp(positions[b] + T, 1, cap)`` before the product because 0 * NaN is NaN.  Rows between
@@ -735,7 +833,8 @@ def _extend_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor, 
     A cache of ``Hkv < H`` heads is grouped-query attention.  ``window``: scores below ``L(b, t) - window``
     are masked as well, and v is also zeroed below the first query's lower limit ``L(b, 0) - window``.
     ``rolling``: the same over the logical rows ``j(p)`` of the ring's slots for the limit ``L(b, T - 1)``
-    (module docstring), with no limit clamped to the row count; never-written slots are zeroed too."""
+    (module docstring), with no limit clamped to the row count; never-written slots are zeroed too.
+    ``sinks``: as :func:`_decode_ref`."""
     B, T, H, D = q.shape
     cap = k_cache.shape[2]
     pos = positions.to(torch.int64)
@@ -760,17 +859,18 @@ def _extend_ref(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor, 
     if k_cache.shape[1] != H:  # query head h reads kv head h // G
         qg = q.to(ct).reshape(B, T, k_cache.shape[1], -1, D)
         s = torch.einsum("btkgd,bkjd->bkgtj", qg, k_cache.to(ct)) * scale
-        p = torch.softmax(s.masked_fill(~vis[:, :, None], float("-inf")), dim=-1)
+        p = _softmax_sink(s.masked_fill(~vis[:, :, None], float("-inf")),
+                          None if sinks is None else sinks.view(1, k_cache.shape[1], -1, 1, 1))
         return torch.einsum("bkgtj,bkjd->btkgd", p, v).reshape(B, T, H, D).to(q.dtype)
     s = torch.einsum("bthd,bhjd->bhtj", q.to(ct), k_cache.to(ct)) * scale
-    p = torch.softmax(s.masked_fill(~vis, float("-inf")), dim=-1)
+    p = _softmax_sink(s.masked_fill(~vis, float("-inf")), None if sinks is None else sinks.view(1, -1, 1, 1))
     return torch.einsum("bhtj,bhjd->bthd", p, v).to(q.dtype)
 
 
 def attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
                      scale: Optional[float] = None, *, kv_heads: Optional[int] = None,
                      window: Optional[int] = None, rolling: bool = False,
-                     kv_scales: Optional[Tuple[float, float]] = None) -> Tensor:
+                     kv_scales: Optional[Tuple[float, float]] = None, sinks: Optional[Tensor] = None) -> Tensor:
     """``T`` queries per (batch, head): ``q`` ``[B, T, H, D]`` (any view with a contiguous last dim), whose
     k / v rows are already in ``k_cache`` / ``v_cache`` ``[B, Hkv, cap, D]`` at rows ``positions[b] + t``.
     Query ``t`` sees rows ``j < clamp(positions[b] + t + 1, 1, cap)`` -> ``[B, T, H, D]``.  ``kv_heads``:
@@ -783,27 +883,31 @@ def attention_extend(q: Tensor, k_cache: Tensor, v_cache: Tensor, positions: Ten
     ``rolling=True`` (needs ``1 <= window <= cap`` and ``T <= cap - window + 1``): the caches are a ring, the
     rows sit in slots ``(positions[b] + t) mod cap`` and ``L(b, t) = max(positions[b] + t + 1, 1)`` counts
     tokens (module docstring).  ``kv_scales`` (``float8_e4m3fn`` caches only; ``None``: ``(1.0, 1.0)``): the
-    queries see the rows dequantised (module docstring)."""
+    queries see the rows dequantised (module docstring).  ``sinks`` (float32 ``[H]``): the attention sinks of the
+    module docstring, read on the device."""
     _forward_only(q, k_cache, v_cache)
     if q.dim() != 4 or q.shape[1] < 1:
         raise RuntimeError("q must be [B, T >= 1, H, D]")
     B, T, H, D = q.shape
     hkv = _kv_heads(H, kv_heads)
+    _check_sinks(sinks, H, k_cache)
+    kkw = _sink_kw(sinks)
     wkw = _ring_kw(window, k_cache, T) if rolling else _cache_window(window, k_cache)
     nkw, skw = _scale_kw(_kv_scales(kv_scales, k_cache, v_cache))
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     with torch.no_grad():
         if _decode_native(q, k_cache, v_cache):
             return native().attn_extend(_rows(q), k_cache, v_cache, positions, scale, None, hkv,
-                                        **wkw, **nkw).view(B, T, H, D)
+                                        **wkw, **nkw, **kkw).view(B, T, H, D)
         _check_cache(k_cache, v_cache, B, hkv, D, positions, "positions")
-        return _extend_ref(q, k_cache, v_cache, positions, scale, **wkw, **skw)
+        return _extend_ref(q, k_cache, v_cache, positions, scale, **wkw, **skw, **kkw)
 
 
 def attention_extend_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: Tensor, positions: Tensor,
                             scale: Optional[float] = None, *, kv_heads: Optional[int] = None,
                             window: Optional[int] = None, rolling: bool = False,
-                            kv_scales: Optional[Tuple[float, float]] = None) -> Tensor:
+                            kv_scales: Optional[Tuple[float, float]] = None,
+                            sinks: Optional[Tensor] = None) -> Tensor:
     """``T`` new tokens on their packed ``[B, T, (H + 2*Hkv)*D]`` projection: append their k / v at rows
     ``positions[b] + t`` (rows outside ``[0, cap)`` are dropped), then query ``t`` attends to rows
     ``j < clamp(positions[b] + t + 1, 1, cap)`` -> ``[B, T, H*D]``.  ``T == 1`` is
@@ -813,15 +917,17 @@ def attention_extend_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: T
     ``rolling=True``: the ring of :func:`kv_cache_append` and :func:`attention_extend` (``T <= cap - window +
     1``, or ``ValueError`` before anything is written).  ``kv_scales`` (``float8_e4m3fn`` caches only): as
     :func:`kv_cache_append` and :func:`attention_extend`; every query, a token's own included, sees quantised
-    rows."""
+    rows.  ``sinks``: as :func:`attention_extend`."""
     dims = _packed_dims(qkv, heads, kv_heads, scale, T="T >= 1")
+    _check_sinks(sinks, heads, k_cache)
+    kkw = _sink_kw(sinks)
     wkw = _ring_kw(window, k_cache, dims[2]) if rolling else _cache_window(window, k_cache)
     akw = {"rolling": True} if rolling else {}  # the append's; no ring: the calls it always made
     sc = _kv_scales(kv_scales, k_cache, v_cache)
     nkw, skw = _scale_kw(sc)
     if dims[2] == 1:
         return attention_decode_packed(qkv, heads, k_cache, v_cache, positions, scale, kv_heads=kv_heads, **wkw,
-                                       **skw)
+                                       **skw, **kkw)
     _forward_only(qkv, k_cache, v_cache)
     hkv, B, T, D, scale = dims
     with torch.no_grad():
@@ -829,14 +935,14 @@ def attention_extend_packed(qkv: Tensor, heads: int, k_cache: Tensor, v_cache: T
             qkv, C = _rows(qkv), native()
             C.attn_kv_append(qkv, heads, k_cache, v_cache, positions, hkv, **akw, **nkw)
             q = qkv[..., :heads * D].view(B, T, heads, D)
-            return C.attn_extend(q, k_cache, v_cache, positions, scale, None, hkv, **wkw, **nkw)
+            return C.attn_extend(q, k_cache, v_cache, positions, scale, None, hkv, **wkw, **nkw, **kkw)
         _check_cache(k_cache, v_cache, B, hkv, D, positions, "positions")
         if rolling:
             _append_ring_ref(k_cache, v_cache, qkv, heads, positions, hkv, None, **skw)
         else:
             _append_ref(k_cache, v_cache, qkv, heads, positions, hkv, **skw)
         q = qkv[..., :heads * D].reshape(B, T, heads, D)
-        return _extend_ref(q, k_cache, v_cache, positions, scale, **wkw, **skw).reshape(B, T, heads * D)
+        return _extend_ref(q, k_cache, v_cache, positions, scale, **wkw, **skw, **kkw).reshape(B, T, heads * D)
 
 
 # ---------------------------------------------------------------- rotary position embedding
