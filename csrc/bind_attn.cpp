@@ -387,6 +387,83 @@ Tensor rows_linear(const Tensor& x, const Tensor& weight, const optional<Tensor>
   return y;
 }
 
+// rows_linear on an MXFP4 weight (csrc/rows_gemm_mx.hip): codes uint8 [Q, K / 2] and scales uint8
+// [Q, K / 32], both contiguous ([2Q, ..] under SwiGLU), K % 32 == 0; everything else as rows_linear.
+Tensor rows_linear_mx(const Tensor& x, const Tensor& codes, const Tensor& scales, const optional<Tensor>& bias,
+                      const optional<Tensor>& gamma, const optional<Tensor>& beta, double eps, int64_t epi,
+                      const optional<Tensor>& residual, const optional<Tensor>& out, bool rms) {
+  const at::DeviceGuard guard = on_device_of(x, "x");
+  check_cuda(codes, "codes");
+  check_cuda(scales, "scales");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && codes.scalar_type() == at::kByte && scales.scalar_type() == at::kByte,
+              "rows_linear_mx: x bf16, codes and scales uint8");
+  TORCH_CHECK(x.dim() == 2 && codes.dim() == 2 && scales.dim() == 2 && codes.is_contiguous() && scales.is_contiguous() &&
+                  codes.device() == x.device() && scales.device() == x.device(),
+              "rows_linear_mx: x [M, K], codes [Q, K / 2] and scales [Q, K / 32] contiguous, on one device");
+  TORCH_CHECK(epi >= 0 && epi <= 3, "rows_linear_mx: epilogue 0 (none), 1 (gelu), 2 (residual) or 3 (swiglu)");
+  const bool glu = epi == tbamd::kRowsSwiglu;
+  TORCH_CHECK(!glu || codes.size(0) % 2 == 0, "rows_linear_mx: the swiglu epilogue needs codes [2F, K / 2]");
+  const int64_t M = x.size(0), K = x.size(1), WQ = codes.size(0), Q = glu ? WQ / 2 : WQ;
+  TORCH_CHECK(M >= 1 && M <= 16 && K % 32 == 0 && K >= 32 && K <= 4096 && Q >= 1 && Q < (int64_t)INT32_MAX / 16,
+              "rows_linear_mx: 1 <= M <= 16, K % 32 == 0, 32 <= K <= 4096");
+  TORCH_CHECK(codes.size(1) * 2 == K && scales.size(0) == WQ && scales.size(1) * 32 == K,
+              "rows_linear_mx: codes must be [Q, K / 2] and scales [Q, K / 32]");
+  TORCH_CHECK(x.stride(1) == 1 && (M == 1 || x.stride(0) % 8 == 0) && (M == 1 || x.stride(0) >= 0) &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(codes.data_ptr()) % 16 == 0,
+              "rows_linear_mx: rows and codes must be 16-B aligned, rows with a unit column stride");
+  tbamd::RowsLinearMxArgs a{};
+  a.x = reinterpret_cast<const uint16_t*>(x.data_ptr());
+  a.codes = codes.data_ptr<uint8_t>();
+  a.scales = scales.data_ptr<uint8_t>();
+  a.sx = M == 1 ? 0 : x.stride(0);
+  if (given(bias)) {
+    check_cuda(*bias, "bias");
+    TORCH_CHECK(bias->scalar_type() == at::kBFloat16 && bias->dim() == 1 && bias->size(0) == WQ &&
+                    bias->is_contiguous() && bias->device() == x.device(),
+                "rows_linear_mx: bias must be contiguous bf16 [Q] ([2F] under swiglu)");
+    a.bias = reinterpret_cast<const uint16_t*>(bias->data_ptr());
+  }
+  TORCH_CHECK(rms ? (given(gamma) && !given(beta)) : given(gamma) == given(beta),
+              "rows_linear_mx: gamma and beta come together (LayerNorm), or gamma alone with rms");
+  for (const optional<Tensor>* p : {&gamma, &beta}) {
+    if (!given(*p)) continue;
+    const Tensor& t = **p;
+    check_cuda(t, "gamma / beta");
+    TORCH_CHECK(t.scalar_type() == at::kFloat && t.dim() == 1 && t.size(0) == K && t.is_contiguous() &&
+                    t.device() == x.device() && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+                "rows_linear_mx: gamma / beta must be contiguous, 16-B aligned f32 [K]");
+  }
+  if (given(gamma)) a.gamma = gamma->data_ptr<float>();
+  if (given(beta)) a.beta = beta->data_ptr<float>();
+  a.rms = rms ? 1 : 0;
+  Tensor y;
+  if (given(out)) {
+    y = *out;
+    check_cuda(y, "out");
+    TORCH_CHECK(y.scalar_type() == at::kBFloat16 && y.dim() == 2 && y.size(0) == M && y.size(1) == Q &&
+                    y.is_contiguous() && y.device() == x.device(),
+                "rows_linear_mx: out must be contiguous bf16 [M, Q]");
+  } else {
+    y = at::empty({M, Q}, x.options());
+  }
+  TORCH_CHECK(!glu || !given(residual), "rows_linear_mx: the swiglu epilogue takes no residual");
+  if (epi == 2) {
+    TORCH_CHECK(given(residual), "rows_linear_mx: the residual epilogue needs a residual");
+    const Tensor& r = *residual;
+    check_cuda(r, "residual");
+    TORCH_CHECK(r.scalar_type() == at::kBFloat16 && r.dim() == 2 && r.size(0) == M && r.size(1) == Q &&
+                    r.stride(1) == 1 && (M == 1 || r.stride(0) >= 0) && r.device() == x.device(),
+                "rows_linear_mx: residual must be bf16 [M, Q] with a unit column stride");
+    a.res = reinterpret_cast<const uint16_t*>(r.data_ptr());
+    a.sres = M == 1 ? 0 : r.stride(0);
+  }
+  a.y = reinterpret_cast<uint16_t*>(y.data_ptr());
+  a.M = (int)M, a.K = (int)K, a.Q = (int)Q, a.epi = (int)epi, a.eps = (float)eps;
+  tbamd::rows_linear_mx(a, cur_stream());
+  return y;
+}
+
 // tokens int64 [B, T] (any strides); tok_weight [vocab, D], pos_weight [max_len, D] bf16 contiguous; positions
 // int32 [B] or none -> [B, T, D].  Token ids and positions are clamped into range by the kernel.
 // pos_weight none: the clamped token rows alone.
@@ -638,6 +715,20 @@ void register_attn(pybind11::module& m) {
     TORCH_CHECK(F >= 1 && F < (int64_t)INT32_MAX / 32, "rows_swiglu_cols_per_wave: bad F");
     return (int64_t)tbamd::rows_swiglu_cols_per_wave((int)F);
   });
+  m.def("rows_linear_mx", &rows_linear_mx, py::arg("x"), py::arg("codes"), py::arg("scales"),
+        py::arg("bias") = py::none(), py::arg("gamma") = py::none(), py::arg("beta") = py::none(),
+        py::arg("eps") = 0.0, py::arg("epi") = 0, py::arg("residual") = py::none(), py::arg("out") = py::none(),
+        py::arg("rms") = false);
+  // test helpers (tests/test_gpu_rows_mx.py checks that its shapes reach every launcher setting)
+  m.def("rows_mx_block_lanes", [](int64_t K) {
+    TORCH_CHECK(K >= 32 && K <= 4096 && K % 32 == 0, "rows_mx_block_lanes: bad K");
+    return (int64_t)tbamd::rows_mx_block_lanes((int)K);
+  });
+  m.def("rows_mx_cols_per_wave", [](int64_t Q, int64_t K, bool glu) {
+    TORCH_CHECK(K >= 32 && K <= 4096 && K % 32 == 0 && Q >= 1 && Q < (int64_t)INT32_MAX / 16,
+                "rows_mx_cols_per_wave: bad Q or K");
+    return (int64_t)tbamd::rows_mx_cols_per_wave((int)Q, (int)K, glu);
+  }, py::arg("Q"), py::arg("K"), py::arg("glu") = false);
   m.def("embed_rows", &embed_rows, py::arg("tokens"), py::arg("tok_weight"), py::arg("pos_weight") = py::none(),
         py::arg("positions") = py::none());
   m.def("rope_packed", &rope_packed, py::arg("qkv"), py::arg("heads"), py::arg("table"),

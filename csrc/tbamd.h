@@ -409,6 +409,28 @@ struct RowsLinearArgs {
 int rows_linear_cols_per_wave(int Q);
 int rows_swiglu_cols_per_wave(int F);  // output columns per wave under kRowsSwiglu (two weight rows each)
 void rows_linear(const RowsLinearArgs& a, hipStream_t st);
+// The same product on an MXFP4 weight (csrc/rows_gemm_mx.hip): codes uint8 [Q][K / 2] (element 2i in
+// the low nibble of byte i, 16-B aligned), scales uint8 [Q][K / 32] (e8m0), both contiguous ([2Q]
+// rows under kRowsSwiglu); w[q][k] = e2m1(code) * f32_from_bits(scale << 23).  K % 32 == 0,
+// 32 <= K <= 4096.  Every other field means what it means in RowsLinearArgs.
+struct RowsLinearMxArgs {
+  const uint16_t* x;
+  const uint8_t* codes;
+  const uint8_t* scales;
+  const uint16_t* bias;
+  const float* gamma;
+  const float* beta;
+  const uint16_t* res;
+  uint16_t* y;
+  int M, K, Q, epi;
+  int64_t sx, sres;
+  float eps;
+  int cpw;
+  int rms;
+};
+int rows_mx_block_lanes(int K);                      // lanes per column (LB), from K alone
+int rows_mx_cols_per_wave(int Q, int K, bool glu);  // output columns per wave, from (Q, K) alone
+void rows_linear_mx(const RowsLinearMxArgs& a, hipStream_t st);
 // y[b][t][:] = tok_w[clamp(tokens[b][t], 0, vocab - 1)] + pos_w[clamp(pos[b] + t, 0, max_len - 1)]
 // (f32 sum, one rounding); tokens int64 [B][T] with strides stok (elements), pos int32 [B] or null
 // (0), D % 8 == 0.  pos_w null (a model without learned positions): the clamped token row alone.

@@ -120,7 +120,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 import torch
 from torch import Tensor, nn
 
-from torchbooster_amd.models.vit import Block, MoE, Rope, make_norm, norm_args
+from torchbooster_amd.models.vit import Block, MoE, Rope, make_norm, mx_snapshots, norm_args, rows_weight
 from torchbooster_amd.ops.attention import _check_scale
 from torchbooster_amd.ops.linear import Linear, embed_rows, linear_rows
 from torchbooster_amd.ops.loss import linear_cross_entropy
@@ -219,6 +219,8 @@ def _sample(logits: Tensor, temperature: float, top_k: Optional[int], generator)
 
 
 class TransformerLM(nn.Module):
+    mx_rows = None  # the head's MXFP4 snapshot of quantize_rows, {"head": (codes, scales)}
+
     def __init__(self, vocab: int, dim: int, depth: int, heads: int, max_len: int, mlp_ratio: float = 4.0,
                  kv_heads: Optional[int] = None, *, pos: str = "learned", rope_base: float = 10000.0,
                  norm: str = "layer", mlp: str = "gelu", bias: bool = True,
@@ -372,9 +374,28 @@ class TransformerLM(nn.Module):
         """The final norm and the head on ``[B, T, dim]`` -> ``[B, T, vocab]``.  Default: ``x`` and its
         ``pending`` add; ``fused``: the residual stream alone, the norm as the product's prologue."""
         if fused:
-            return linear_rows(x, self.head.weight, self.head.bias, **norm_args(self.norm))
+            w, kw = rows_weight(self.head, (self.mx_rows or {}).get("head"))
+            return linear_rows(x, w, self.head.bias, **norm_args(self.norm), **kw)
         h, _ = self.norm(x, pending)
         return self.head(h)
+
+    def quantize_rows(self, fmt: Optional[str] = "mxfp4") -> None:
+        """Decode on 4-bit weights: snapshot every linear the ``fused=True`` step multiplies by -- ``qkv``,
+        ``proj``, ``fc1``, ``fc2`` of each block and the head -- in the OCP microscaling format MXFP4
+        (``ops.linear.mx_quantize``: e2m1 codes, one power-of-two scale per 32 inputs, 4.25 bits per weight).
+        ``decode_step`` / ``extend`` / ``generate`` with ``fused=True`` then pass the codes to ``linear_rows``
+        (csrc/rows_gemm_mx.hip) in place of the bf16 weight; nothing else in the step changes.  A linear whose
+        input width is no multiple of 32 stays as it is.  ``fmt=None`` drops the snapshots; any other value
+        raises ``ValueError``.
+
+        The snapshots are plain attributes (``blocks[i].mx_rows``, ``mx_rows``), like the :class:`Rope` tables:
+        no parameters, no buffers, no state-dict keys.  They are built on the device the weights are on and
+        do not follow the weights: after changing or moving them, call this again.  The bf16 parameters stay
+        -- ``fused=False``, ``prefill``, ``forward`` and ``loss`` read them."""
+        head = mx_snapshots([("head", self.head)], fmt)
+        for blk in self.blocks:
+            blk.quantize_rows(fmt)
+        self.mx_rows = head
 
     def _step(self, tokens: Tensor, cache: KVCache, lengths: Optional[Tensor], last_only: bool,
               fused: bool) -> Tensor:

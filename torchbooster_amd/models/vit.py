@@ -26,7 +26,7 @@ from torchbooster_amd.ops.conv import Conv2d
 from torchbooster_amd.ops.act import swiglu
 from torchbooster_amd.ops.gemm import grouped_linear
 from torchbooster_amd.ops.norm import LayerNorm, RMSNorm
-from torchbooster_amd.ops.linear import GeluLink, Linear, LinearGELU, linear, linear_rows
+from torchbooster_amd.ops.linear import MX_BLOCK, GeluLink, Linear, LinearGELU, linear, linear_rows, mx_quantize
 
 __all__ = ["ViT", "vit_b_16", "vit_s_16", "vit_tiny", "Attention", "Block", "Rope", "SwiGLU", "MoE"]
 
@@ -80,6 +80,22 @@ def norm_args(norm):
     if isinstance(norm, RMSNorm):
         return {"rms": (norm.weight, norm.eps)}
     return {"ln": ln_args(norm)}
+
+
+def mx_snapshots(named, fmt: Optional[str]):
+    """``{name: (codes, scales)}`` of the ``(name, linear)`` pairs whose ``in_features`` is a multiple of 32
+    (``ops.linear.mx_quantize`` of the weight, on its device), or ``None`` for ``fmt=None``."""
+    if fmt is None:
+        return None
+    if fmt != "mxfp4":
+        raise ValueError(f"quantize_rows: fmt must be 'mxfp4' or None, not {fmt!r}")
+    return {name: mx_quantize(lin.weight) for name, lin in named if lin.in_features % MX_BLOCK == 0}
+
+
+def rows_weight(lin, mx):
+    """The weight argument and the extra keywords of a ``linear_rows`` call on ``lin``: the parameter, or its
+    MXFP4 snapshot ``mx = (codes, scales)``."""
+    return (lin.weight, {}) if mx is None else (mx[0], {"mx_scales": mx[1]})
 
 
 def make_norm(kind: str, dim: int):
@@ -385,6 +401,9 @@ class Block(nn.Module):
     token (its router and experts never have a bias; ``bias`` then governs ``qkv`` and ``proj`` alone);
     ``forward_rows`` has no few-row expert kernel and raises ``ValueError``."""
 
+    # the MXFP4 snapshots of quantize_rows, {name: (codes, scales)}: a plain attribute like the Rope tables
+    mx_rows = None
+
     def __init__(self, dim: int, heads: int, mlp_ratio: float = 4.0, causal: bool = False,
                  kv_heads: Optional[int] = None, rope: Optional[Rope] = None, norm: str = "layer",
                  mlp: str = "gelu", bias: bool = True, window: Optional[int] = None,
@@ -443,13 +462,26 @@ class Block(nn.Module):
             raise ValueError("forward_rows (fused=True): there is no few-row kernel for an MoE block")
         if x.shape[1] != 1 and not extend:
             raise ValueError("forward_rows: more than one token per sequence needs extend=True")
-        qkv = linear_rows(x, at.qkv.weight, at.qkv.bias, **norm_args(self.ln1))
+        mx = self.mx_rows or {}
+        w, kw = rows_weight(at.qkv, mx.get("qkv"))
+        qkv = linear_rows(x, w, at.qkv.bias, **norm_args(self.ln1), **kw)
         a = at.cached(qkv, cache, positions, extend=extend, fused=True, **({"rolling": True} if rolling else {}),
                       **({} if kv_scales is None else {"kv_scales": kv_scales}))
-        x = linear_rows(a, at.proj.weight, at.proj.bias, residual=x)
+        w, kw = rows_weight(at.proj, mx.get("proj"))
+        x = linear_rows(a, w, at.proj.bias, residual=x, **kw)
         act = "swiglu" if isinstance(self.mlp, SwiGLU) else "gelu"
-        h = linear_rows(x, self.mlp.fc1.weight, self.mlp.fc1.bias, **norm_args(self.ln2), act=act)
-        return linear_rows(h, self.mlp.fc2.weight, self.mlp.fc2.bias, residual=x)
+        w, kw = rows_weight(self.mlp.fc1, mx.get("fc1"))
+        h = linear_rows(x, w, self.mlp.fc1.bias, **norm_args(self.ln2), act=act, **kw)
+        w, kw = rows_weight(self.mlp.fc2, mx.get("fc2"))
+        return linear_rows(h, w, self.mlp.fc2.bias, residual=x, **kw)
+
+    def quantize_rows(self, fmt: Optional[str] = "mxfp4") -> None:
+        """Snapshot ``qkv``, ``proj``, ``fc1`` and ``fc2`` as MXFP4 for ``forward_rows`` (``fmt=None``: drop the
+        snapshots); see ``TransformerLM.quantize_rows``.  An MoE MLP has no few-row path and is left alone."""
+        named = [("qkv", self.attn.qkv), ("proj", self.attn.proj)]
+        if not isinstance(self.mlp, MoE):
+            named += [("fc1", self.mlp.fc1), ("fc2", self.mlp.fc2)]
+        self.mx_rows = mx_snapshots(named, fmt)
 
 
 class ViT(nn.Module):

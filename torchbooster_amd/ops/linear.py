@@ -23,7 +23,7 @@ fp16 activations) use ATen.  State-dict compatible with ``nn.Linear``.
 from __future__ import annotations
 
 import os
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -34,7 +34,8 @@ from torchbooster_amd.ops._ext import native, slot_alias, take_slot, use_native
 from torchbooster_amd.ops.act import swiglu
 from torchbooster_amd.ops.norm import rms_norm
 
-__all__ = ["Linear", "linear", "LinearGELU", "linear_gelu", "GeluLink", "linear_rows", "embed_rows"]
+__all__ = ["Linear", "linear", "LinearGELU", "linear_gelu", "GeluLink", "linear_rows", "embed_rows",
+           "mx_quantize", "mx_dequantize"]
 
 # The fused epilogue stages the z tile through LDS with coalesced 16-B loads: 0.221 vs 0.273 ms
 # unfused, ViT-B/16 5245 / 5241 vs 5134 / 5137 img/s alternated (profiles/r03_gemm_nn/README.md;
@@ -290,8 +291,67 @@ def _rows_forward_only(*tensors: Optional[Tensor]) -> None:
                            "the inputs")
 
 
+MX_BLOCK = 32  # elements per MXFP4 block (one e8m0 scale byte each)
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def mx_quantize(weight: Tensor) -> Tuple[Tensor, Tensor]:
+    """``weight`` ``[Q, K]`` (``K % 32 == 0``) -> ``(codes, scales)`` in the OCP microscaling format MXFP4.
+
+    ``codes`` uint8 ``[Q, K / 2]``: two e2m1 codes per byte, element ``2i`` in the low nibble of byte ``i``
+    (the ``torch.float4_e2m1fn_x2`` order); a code ``c`` has sign ``c >> 3`` and magnitude
+    ``(0, 0.5, 1, 1.5, 2, 3, 4, 6)[c & 7]``.  ``scales`` uint8 ``[Q, K / 32]``: one e8m0 byte ``s`` per block of
+    32 consecutive elements, and an element is ``e2m1(c) * 2^(s - 127)``.
+
+    Per block ``s = clamp(floor(log2(max|w|)) - 2 + 127, 1, 254)`` (127 for an all-zero block; the exponent
+    comes from ``frexp``) and each element is ``w / 2^(s - 127)`` clamped to ``[-6, 6]`` and rounded to the
+    nearest code, ties to the code with the even low bit.  Computed in f32 (f64 for f64 input).  An offline
+    call: it reads one value on the host, and a non-finite ``weight`` raises ``ValueError``."""
+    if weight.dim() != 2 or weight.shape[1] % MX_BLOCK or weight.shape[1] == 0:
+        raise ValueError(f"mx_quantize: weight must be [Q, K] with K a multiple of {MX_BLOCK}, not "
+                         f"{tuple(weight.shape)}")
+    with torch.no_grad():
+        Q, K = weight.shape
+        w = weight.detach().to(torch.float64 if weight.dtype == torch.float64 else torch.float32)
+        if not bool(torch.isfinite(w).all()):
+            raise ValueError("mx_quantize: weight has a non-finite value")
+        w = w.reshape(Q, K // MX_BLOCK, MX_BLOCK)
+        amax = w.abs().amax(dim=-1)
+        _, e = torch.frexp(amax)  # amax = m * 2^e with m in [0.5, 1): floor(log2(amax)) = e - 1
+        s = (e.to(torch.int32) - 3 + 127).clamp(1, 254)
+        s = torch.where(amax == 0, torch.full_like(s, 127), s)
+        a = (w / torch.ldexp(torch.ones_like(amax), s - 127)[..., None]).clamp(-6.0, 6.0).abs()
+        # the midpoints between neighbouring magnitudes; a tie goes to the even code
+        c = ((a > 0.25).to(torch.uint8) + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5) + (a >= 3.5)
+             + (a > 5.0)).to(torch.uint8)
+        c = (c | (torch.signbit(w).to(torch.uint8) << 3)).reshape(Q, K)
+        return (c[:, 0::2] | (c[:, 1::2] << 4)).contiguous(), s.to(torch.uint8).contiguous()
+
+
+def _mx_check(codes: Tensor, scales: Tensor, who: str) -> None:
+    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8:
+        raise ValueError(f"{who}: MXFP4 codes and scales are uint8, not {codes.dtype} and {scales.dtype}")
+    if (codes.dim() != 2 or scales.dim() != 2 or scales.shape[0] != codes.shape[0]
+            or scales.shape[1] * (MX_BLOCK // 2) != codes.shape[1]):
+        raise ValueError(f"{who}: codes [Q, K / 2] and scales [Q, K / 32] do not fit: {tuple(codes.shape)} and "
+                         f"{tuple(scales.shape)}")
+
+
+def mx_dequantize(codes: Tensor, scales: Tensor, dtype=torch.bfloat16) -> Tensor:
+    """The ``[Q, K]`` tensor an MXFP4 pair of :func:`mx_quantize` stands for, in ``dtype``: element by element
+    ``e2m1(code) * f32_from_bits(scale << 23)``, which is ``2^(scale - 127)`` for a scale byte in
+    ``[1, 254]`` and exact in bf16 and f32.  A scale byte 0 reads as a zero scale and 255 as ``+inf``;
+    :func:`mx_quantize` emits neither."""
+    _mx_check(codes, scales, "mx_dequantize")
+    Q = codes.shape[0]
+    table = torch.tensor(_E2M1 + tuple(-v for v in _E2M1), dtype=torch.float32, device=codes.device)
+    nib = torch.stack((codes & 0xF, codes >> 4), dim=-1).reshape(Q, -1, MX_BLOCK)
+    scale = (scales.to(torch.int32) << 23).view(torch.float32)
+    return (table[nib.long()] * scale[..., None]).reshape(Q, -1).to(dtype)
+
+
 def linear_rows(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, ln=None, act: Optional[str] = None,
-                residual: Optional[Tensor] = None, rms=None) -> Tensor:
+                residual: Optional[Tensor] = None, rms=None, mx_scales: Optional[Tensor] = None) -> Tensor:
     """``epilogue(linear(prologue(x), weight, bias))`` for the few rows of a decode step, in ONE kernel.
 
     ``x`` ``[..., K]``, ``weight`` ``[Q, K]`` (the ``nn.Linear`` layout, read once), ``bias`` ``[Q]`` ->
@@ -310,7 +370,13 @@ def linear_rows(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, ln=
     rows.  Everything else (CPU tensors, other dtypes, more rows, another ``K``,
     ``TBAMD_FORCE_REFERENCE=1``) is the PyTorch composition ``F.layer_norm`` / ``rms_norm -> F.linear ->
     F.gelu`` / ``swiglu`` / ``+ residual``, every tensor in the dtype of ``x`` (the two norms take their statistics in
-    f32 for 16-bit inputs and round once).  Forward only."""
+    f32 for 16-bit inputs and round once).  Forward only.
+
+    ``mx_scales``: the weight is MXFP4 (:func:`mx_quantize`): ``weight`` holds the uint8 codes ``[Q, K / 2]``
+    (``[2F, K / 2]`` under ``act="swiglu"``) and ``mx_scales`` the uint8 scales ``[Q, K / 32]``; shapes or dtypes
+    that do not fit raise ``ValueError``.  The native kernel (csrc/rows_gemm_mx.hip) takes the same operands
+    with ``K % 32 == 0``, ``32 <= K <= 4096``, and streams 4.25 bits per weight; everything else is the
+    composition above on ``mx_dequantize(weight, mx_scales, x.dtype)``."""
     _rows_forward_only(x, weight, bias, residual, *((ln[0], ln[1]) if ln is not None else ()),
                        *((rms[0],) if rms is not None else ()))
     if act not in (None, "gelu", "swiglu"):
@@ -324,12 +390,20 @@ def linear_rows(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, ln=
         raise ValueError(f"linear_rows: act='swiglu' needs weight [2F, K], not {weight.shape[0]} rows")
     K, Q = x.shape[-1], weight.shape[0] // 2 if glu else weight.shape[0]
     lead = x.shape[:-1]
+    if mx_scales is not None:
+        _mx_check(weight, mx_scales, "linear_rows")
+        if weight.shape[1] * 2 != K:
+            raise ValueError(f"linear_rows: MXFP4 codes {tuple(weight.shape)} do not fit x [..., {K}]")
+        _rows_forward_only(mx_scales)
     with torch.no_grad():
         rows = x.reshape(-1, K)
         M = rows.shape[0]
         bf = torch.bfloat16
-        if (use_native(x) and x.dtype == bf and weight.dtype == bf and weight.is_cuda and 1 <= M <= ROWS_MAX
-                and K % 8 == 0 and 8 <= K <= ROWS_MAX_K and not torch.is_autocast_enabled("cuda")
+        mx = mx_scales is not None
+        step = MX_BLOCK if mx else 8  # the reduction comes in MX blocks or in 16-B chunks of bf16
+        if (use_native(x) and x.dtype == bf and (mx or weight.dtype == bf) and weight.is_cuda
+                and (not mx or mx_scales.is_cuda) and 1 <= M <= ROWS_MAX
+                and K % step == 0 and step <= K <= ROWS_MAX_K and not torch.is_autocast_enabled("cuda")
                 and (bias is None or bias.dtype == bf) and (residual is None or residual.dtype == bf)
                 and (ln is None or (ln[0] is not None and ln[1] is not None and ln[0].dtype == torch.float32
                                     and ln[1].dtype == torch.float32))
@@ -344,10 +418,17 @@ def linear_rows(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, ln=
             g, b, eps = (ln[0].contiguous(), ln[1].contiguous(), float(ln[2])) if ln is not None else (None, None, 0.0)
             if rms is not None:
                 g, eps = rms[0].contiguous(), float(rms[1])
-            y = native().rows_linear(rows, weight.contiguous(), None if bias is None else bias.contiguous(), g, b, eps,
-                                     3 if glu else 1 if act == "gelu" else 2 if res is not None else 0, res,
-                                     rms=rms is not None)
+            epi = 3 if glu else 1 if act == "gelu" else 2 if res is not None else 0
+            if mx:
+                y = native().rows_linear_mx(rows, weight.contiguous(), mx_scales.contiguous(),
+                                            None if bias is None else bias.contiguous(), g, b, eps, epi, res,
+                                            rms=rms is not None)
+            else:
+                y = native().rows_linear(rows, weight.contiguous(), None if bias is None else bias.contiguous(), g, b,
+                                         eps, epi, res, rms=rms is not None)
             return y.view(*lead, Q)
+        if mx:
+            weight = mx_dequantize(weight, mx_scales, x.dtype)
         h = x
         if rms is not None:
             h = rms_norm(h, rms[0], float(rms[1]))
