@@ -464,6 +464,118 @@ Tensor rows_linear_mx(const Tensor& x, const Tensor& codes, const Tensor& scales
   return y;
 }
 
+// gamma (and beta) of a norm prologue: contiguous, 16-B aligned f32 [K] on the device of x
+const float* rows_norm_weight(const Tensor& t, int64_t K, const Tensor& x, const char* who) {
+  check_cuda(t, "gamma / beta");
+  TORCH_CHECK(t.scalar_type() == at::kFloat && t.dim() == 1 && t.size(0) == K && t.is_contiguous() &&
+                  t.device() == x.device() && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              who, ": gamma / beta must be contiguous, 16-B aligned f32 [K]");
+  return t.data_ptr<float>();
+}
+
+// The expert-selected product (csrc/rows_experts_mx.hip): codes uint8 [E, Qw, K / 2], scales uint8
+// [E, Qw, K / 32], ids int32 [M, top_k], M * top_k <= 16.  gates none (pair mode): x [M, K] -> [M, top_k, Q]
+// (glu: Qw = 2Q); gates f32 [M, top_k] (combine mode): x [M, top_k, K] -> [M, Q], residual [M, Q] or none.
+Tensor rows_experts_mx(const Tensor& x, const Tensor& codes, const Tensor& scales, const Tensor& ids,
+                       const optional<Tensor>& gates, const optional<Tensor>& gamma, const optional<Tensor>& beta,
+                       double eps, bool glu, const optional<Tensor>& residual, bool rms) {
+  const at::DeviceGuard guard = on_device_of(x, "x");
+  check_cuda(codes, "codes");
+  check_cuda(scales, "scales");
+  check_cuda(ids, "ids");
+  const bool comb = given(gates);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && codes.scalar_type() == at::kByte && scales.scalar_type() == at::kByte &&
+                  ids.scalar_type() == at::kInt,
+              "rows_experts_mx: x bf16, codes and scales uint8, ids int32");
+  TORCH_CHECK(x.dim() == (comb ? 3 : 2) && codes.dim() == 3 && scales.dim() == 3 && ids.dim() == 2 &&
+                  codes.is_contiguous() && scales.is_contiguous() && ids.is_contiguous() && x.is_contiguous() &&
+                  codes.device() == x.device() && scales.device() == x.device() && ids.device() == x.device(),
+              "rows_experts_mx: x [M, K] ([M, top_k, K] with gates), codes [E, Qw, K / 2], scales [E, Qw, K / 32] and "
+              "ids [M, top_k] contiguous, on one device");
+  const int64_t M = x.size(0), K = x.size(-1), top_k = ids.size(1), E = codes.size(0), WQ = codes.size(1);
+  TORCH_CHECK(!glu || (!comb && WQ % 2 == 0), "rows_experts_mx: glu needs codes [E, 2F, K / 2] and no gates");
+  const int64_t Q = glu ? WQ / 2 : WQ;
+  TORCH_CHECK(M >= 1 && top_k >= 1 && M * top_k <= 16 && K % 32 == 0 && K >= 32 && K <= 4096 && E >= 1 &&
+                  E < (int64_t)INT32_MAX && Q >= 1 && Q < (int64_t)INT32_MAX / 16,
+              "rows_experts_mx: 1 <= M * top_k <= 16, K % 32 == 0, 32 <= K <= 4096");
+  TORCH_CHECK(ids.size(0) == M && (!comb || x.size(1) == top_k) && codes.size(2) * 2 == K && scales.size(0) == E &&
+                  scales.size(1) == WQ && scales.size(2) * 32 == K,
+              "rows_experts_mx: ids must be [M, top_k], codes [E, Qw, K / 2] and scales [E, Qw, K / 32]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(codes.data_ptr()) % 16 == 0,
+              "rows_experts_mx: rows and codes must be 16-B aligned");
+  tbamd::RowsExpertsMxArgs a{};
+  a.x = reinterpret_cast<const uint16_t*>(x.data_ptr());
+  a.codes = codes.data_ptr<uint8_t>();
+  a.scales = scales.data_ptr<uint8_t>();
+  a.ids = ids.data_ptr<int>();
+  a.sx = K;
+  TORCH_CHECK(rms ? (given(gamma) && !given(beta)) : given(gamma) == given(beta),
+              "rows_experts_mx: gamma and beta come together (LayerNorm), or gamma alone with rms");
+  TORCH_CHECK(!comb || (!given(gamma) && !rms), "rows_experts_mx: the combine mode takes no prologue");
+  if (given(gamma)) a.gamma = rows_norm_weight(*gamma, K, x, "rows_experts_mx");
+  if (given(beta)) a.beta = rows_norm_weight(*beta, K, x, "rows_experts_mx");
+  a.rms = rms ? 1 : 0;
+  if (comb) {
+    const Tensor& g = *gates;
+    check_cuda(g, "gates");
+    TORCH_CHECK(g.scalar_type() == at::kFloat && g.dim() == 2 && g.size(0) == M && g.size(1) == top_k &&
+                    g.is_contiguous() && g.device() == x.device(),
+                "rows_experts_mx: gates must be contiguous f32 [M, top_k]");
+    a.gates = g.data_ptr<float>();
+  }
+  TORCH_CHECK(comb || !given(residual), "rows_experts_mx: the residual belongs to the combine mode");
+  if (given(residual)) {
+    const Tensor& r = *residual;
+    check_cuda(r, "residual");
+    TORCH_CHECK(r.scalar_type() == at::kBFloat16 && r.dim() == 2 && r.size(0) == M && r.size(1) == Q &&
+                    r.stride(1) == 1 && (M == 1 || r.stride(0) >= 0) && r.device() == x.device(),
+                "rows_experts_mx: residual must be bf16 [M, Q] with a unit column stride");
+    a.res = reinterpret_cast<const uint16_t*>(r.data_ptr());
+    a.sres = M == 1 ? 0 : r.stride(0);
+  }
+  Tensor y = comb ? at::empty({M, Q}, x.options()) : at::empty({M, top_k, Q}, x.options());
+  a.y = reinterpret_cast<uint16_t*>(y.data_ptr());
+  a.M = (int)M, a.top_k = (int)top_k, a.E = (int)E, a.K = (int)K, a.Q = (int)Q, a.glu = glu ? 1 : 0;
+  a.eps = (float)eps;
+  tbamd::rows_experts_mx(a, cur_stream());
+  return y;
+}
+
+// The fused router (csrc/rows_experts_mx.hip): x bf16 [M, K] (M <= 16), weight bf16 [E, K] (E <= 256) ->
+// (ids int32 [M, top_k], gates f32 [M, top_k]); gamma / beta / eps / rms: the prologue of rows_linear.
+std::tuple<Tensor, Tensor> moe_route(const Tensor& x, const Tensor& weight, int64_t top_k, const optional<Tensor>& gamma,
+                                     const optional<Tensor>& beta, double eps, bool rms) {
+  const at::DeviceGuard guard = on_device_of(x, "x");
+  check_cuda(weight, "weight");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && weight.scalar_type() == at::kBFloat16, "moe_route: bf16 only");
+  TORCH_CHECK(x.dim() == 2 && weight.dim() == 2 && weight.is_contiguous() && weight.device() == x.device(),
+              "moe_route: x [M, K], weight [E, K] contiguous, on one device");
+  const int64_t M = x.size(0), K = x.size(1), E = weight.size(0);
+  TORCH_CHECK(M >= 1 && M <= 16 && K % 8 == 0 && K >= 8 && K <= 4096 && weight.size(1) == K && E >= 1 && E <= 256 &&
+                  top_k >= 1 && top_k <= 16 && top_k <= E,
+              "moe_route: 1 <= M <= 16, K % 8 == 0, K <= 4096, E <= 256, 1 <= top_k <= min(E, 16)");
+  TORCH_CHECK(x.stride(1) == 1 && (M == 1 || x.stride(0) % 8 == 0) && (M == 1 || x.stride(0) >= 0) &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(weight.data_ptr()) % 16 == 0,
+              "moe_route: rows must be 16-B aligned with a unit column stride");
+  TORCH_CHECK(rms ? (given(gamma) && !given(beta)) : given(gamma) == given(beta),
+              "moe_route: gamma and beta come together (LayerNorm), or gamma alone with rms");
+  tbamd::MoeRouteArgs a{};
+  a.x = reinterpret_cast<const uint16_t*>(x.data_ptr());
+  a.w = reinterpret_cast<const uint16_t*>(weight.data_ptr());
+  a.sx = M == 1 ? 0 : x.stride(0);
+  if (given(gamma)) a.gamma = rows_norm_weight(*gamma, K, x, "moe_route");
+  if (given(beta)) a.beta = rows_norm_weight(*beta, K, x, "moe_route");
+  a.rms = rms ? 1 : 0;
+  Tensor ids = at::empty({M, top_k}, x.options().dtype(at::kInt));
+  Tensor gates = at::empty({M, top_k}, x.options().dtype(at::kFloat));
+  a.ids = ids.data_ptr<int>();
+  a.gates = gates.data_ptr<float>();
+  a.M = (int)M, a.K = (int)K, a.E = (int)E, a.top_k = (int)top_k, a.eps = (float)eps;
+  tbamd::moe_route(a, cur_stream());
+  return {ids, gates};
+}
+
 // tokens int64 [B, T] (any strides); tok_weight [vocab, D], pos_weight [max_len, D] bf16 contiguous; positions
 // int32 [B] or none -> [B, T, D].  Token ids and positions are clamped into range by the kernel.
 // pos_weight none: the clamped token rows alone.
@@ -719,6 +831,11 @@ void register_attn(pybind11::module& m) {
         py::arg("bias") = py::none(), py::arg("gamma") = py::none(), py::arg("beta") = py::none(),
         py::arg("eps") = 0.0, py::arg("epi") = 0, py::arg("residual") = py::none(), py::arg("out") = py::none(),
         py::arg("rms") = false);
+  m.def("rows_experts_mx", &rows_experts_mx, py::arg("x"), py::arg("codes"), py::arg("scales"), py::arg("ids"),
+        py::arg("gates") = py::none(), py::arg("gamma") = py::none(), py::arg("beta") = py::none(),
+        py::arg("eps") = 0.0, py::arg("glu") = false, py::arg("residual") = py::none(), py::arg("rms") = false);
+  m.def("moe_route", &moe_route, py::arg("x"), py::arg("weight"), py::arg("top_k"), py::arg("gamma") = py::none(),
+        py::arg("beta") = py::none(), py::arg("eps") = 0.0, py::arg("rms") = false);
   // test helpers (tests/test_gpu_rows_mx.py checks that its shapes reach every launcher setting)
   m.def("rows_mx_block_lanes", [](int64_t K) {
     TORCH_CHECK(K >= 32 && K <= 4096 && K % 32 == 0, "rows_mx_block_lanes: bad K");

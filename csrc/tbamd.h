@@ -431,6 +431,48 @@ struct RowsLinearMxArgs {
 int rows_mx_block_lanes(int K);                      // lanes per column (LB), from K alone
 int rows_mx_cols_per_wave(int Q, int K, bool glu);  // output columns per wave, from (Q, K) alone
 void rows_linear_mx(const RowsLinearMxArgs& a, hipStream_t st);
+// The product with the weight chosen per (token, slot) pair from a stack of MXFP4 experts
+// (csrc/rows_experts_mx.hip): codes [E][Qw][K / 2], scales [E][Qw][K / 32] contiguous, ids int32
+// [M][top_k] read by the kernel and clamped into [0, E), P = M * top_k <= 16 pairs.
+// gates null (pair mode): x [M][K] (row stride sx), y [M][top_k][Q] with Qw = Q, or Qw = 2Q (gate rows,
+// then up rows) and y = silu(gate) * up when glu != 0; gamma / beta / rms / eps as in RowsLinearArgs.
+// gates f32 [M][top_k] (combine mode): x [P][K] (row stride sx), Qw = Q, y [M][Q] with y[m] = res[m] (row
+// stride sres; null: 0) + sum_j gates[m][j] * (x[m][j] . w[e_mj]^T), f32 sums added in slot order, one
+// rounding; no prologue, no glu.  cpw is filled in by rows_experts_mx.
+struct RowsExpertsMxArgs {
+  const uint16_t* x;
+  const uint8_t* codes;
+  const uint8_t* scales;
+  const int* ids;
+  const float* gates;
+  const float* gamma;
+  const float* beta;
+  const uint16_t* res;
+  uint16_t* y;
+  int M, top_k, E, K, Q, glu;
+  int64_t sx, sres;
+  float eps;
+  int cpw;
+  int rms;
+};
+void rows_experts_mx(const RowsExpertsMxArgs& a, hipStream_t st);
+// The router of an MoE decode step on M <= 16 rows (csrc/rows_experts_mx.hip): h = prologue(x[m]) rounded
+// to bf16 as rows_linear rounds it, f32 logits h . w[E][K]^T (w bf16, E <= 256, K % 8 == 0, K <= 4096), ids
+// [M][top_k] the top_k largest logits in descending order (ties to the lower index, always in [0, E)),
+// gates [M][top_k] the f32 softmax over them.  1 <= top_k <= min(E, 16).
+struct MoeRouteArgs {
+  const uint16_t* x;
+  const uint16_t* w;
+  const float* gamma;
+  const float* beta;
+  int* ids;
+  float* gates;
+  int M, K, E, top_k;
+  int64_t sx;
+  float eps;
+  int rms;
+};
+void moe_route(const MoeRouteArgs& a, hipStream_t st);
 // y[b][t][:] = tok_w[clamp(tokens[b][t], 0, vocab - 1)] + pos_w[clamp(pos[b] + t, 0, max_len - 1)]
 // (f32 sum, one rounding); tokens int64 [B][T] with strides stok (elements), pos int32 [B] or null
 // (0), D % 8 == 0.  pos_w null (a model without learned positions): the clamped token row alone.

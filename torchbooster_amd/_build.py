@@ -36,7 +36,7 @@ ARCH = os.environ.get("TBAMD_ARCH", "gfx950")
 # without packed f32 instructions (v_pk_mul_f32 / v_pk_fma_f32), plain f32 ones instead
 _NO_PK_F32 = "-Xclang -target-feature -Xclang -packed-fp32-ops"
 HIP_EXTRA = {"qk_norm_rope.hip": _NO_PK_F32, "gemm_grouped.hip": _NO_PK_F32, "attention_sink.hip": _NO_PK_F32,
-             "rows_gemm_mx.hip": _NO_PK_F32}
+             "rows_gemm_mx.hip": _NO_PK_F32, "rows_experts_mx.hip": _NO_PK_F32}
 
 
 def _torch_paths():

@@ -108,8 +108,13 @@ MLP is a :class:`~torchbooster_amd.models.vit.MoE` -- a bias-free f32 router, th
 token, softmax gates over those, ``experts`` SwiGLU experts of hidden width ``int(dim * mlp_ratio)`` -- whose
 expert products are grouped GEMMs (``ops.gemm.grouped_linear``, csrc/gemm_grouped.hip) over the expert-sorted
 rows, without a host read or an atomic.  ``prefill`` / ``decode_step`` / ``extend`` / ``generate`` (``graph=True``,
-``cache=``, ``draft=``, ``rolling=True``, an fp8 cache) run it unchanged; ``fused=True`` raises ``ValueError``
-(no few-row expert kernel).  ``loss`` does not include the load-balancing loss: add
+``cache=``, ``draft=``, ``rolling=True``, an fp8 cache) run it unchanged.  ``fused=True`` needs
+``quantize_rows()`` first (``ValueError`` without: there is no few-row kernel for bf16 experts): it snapshots the
+stacked experts as MXFP4 too, and the MoE half of a fused step is then three launches -- ``moe_route_rows`` (norm,
+router, top-k, softmax), ``linear_rows_experts`` with the norm prologue and the SwiGLU epilogue, and
+``linear_rows_experts`` with the gated combine and the residual (csrc/rows_experts_mx.hip) -- which stream each
+distinct chosen expert's 4.25-bit weight once; with more than 16 (token, slot) pairs the same calls take their
+PyTorch fallbacks.  The fused path does not update ``aux_loss``.  ``loss`` does not include the load-balancing loss: add
 ``sum(b.mlp.aux_loss() for b in model.blocks)`` with a coefficient.  Any other ``mlp`` is everything above
 unchanged.
 """
@@ -216,6 +221,13 @@ def _sample(logits: Tensor, temperature: float, top_k: Optional[int], generator)
         kth = z.topk(min(int(top_k), z.shape[-1]), dim=-1).values[:, -1:]
         z = z.masked_fill(z < kth, float("-inf"))
     return torch.multinomial(torch.softmax(z, dim=-1), 1, generator=generator)[:, 0]
+
+
+def _check_rows_path(*models) -> None:
+    """``fused=True`` needs ``Block.forward_rows`` in every layer: an MoE block has it after ``quantize_rows()``."""
+    if any(not blk.has_rows_path() for m in models if m is not None for blk in m.blocks):
+        raise ValueError("fused=True: an MoE block decodes on the few-row kernels only with MXFP4 expert "
+                         "snapshots: call quantize_rows() first")
 
 
 class TransformerLM(nn.Module):
@@ -386,7 +398,8 @@ class TransformerLM(nn.Module):
         ``decode_step`` / ``extend`` / ``generate`` with ``fused=True`` then pass the codes to ``linear_rows``
         (csrc/rows_gemm_mx.hip) in place of the bf16 weight; nothing else in the step changes.  A linear whose
         input width is no multiple of 32 stays as it is.  ``fmt=None`` drops the snapshots; any other value
-        raises ``ValueError``.
+        raises ``ValueError``.  An MoE block's stacked experts are snapshotted too (``Block.quantize_rows``; the
+        router stays bf16), which is what opens ``fused=True`` to an MoE model (``ops.linear.linear_rows_experts``).
 
         The snapshots are plain attributes (``blocks[i].mx_rows``, ``mx_rows``), like the :class:`Rope` tables:
         no parameters, no buffers, no state-dict keys.  They are built on the device the weights are on and
@@ -402,8 +415,8 @@ class TransformerLM(nn.Module):
         """``decode_step`` and ``extend``: ``tokens`` ``[B, T]`` at ``cache.positions[b] + t``, on the few-row
         kernels when ``fused``.  ``[B, T, vocab]``, or ``[B, vocab]`` with ``last_only``."""
         T = tokens.shape[1]
-        if fused and any(isinstance(blk.mlp, MoE) for blk in self.blocks):
-            raise ValueError("fused=True: there is no few-row kernel for an MoE block")
+        if fused:
+            _check_rows_path(self)
         with torch.no_grad():
             if fused:
                 x = embed_rows(tokens, self.tok.weight, None if self.pos is None else self.pos[0], cache.positions)
@@ -557,8 +570,8 @@ class TransformerLM(nn.Module):
             raise ValueError(f"prompt {N} + max_new_tokens {max_new_tokens} exceeds max_len {self.max_len}")
         if graph and not tokens.is_cuda:
             raise ValueError("graph=True needs CUDA tensors")
-        if fused and any(isinstance(blk.mlp, MoE) for m in (self, draft) if m is not None for blk in m.blocks):
-            raise ValueError("fused=True: there is no few-row kernel for an MoE block")
+        if fused:
+            _check_rows_path(self, draft)
         if draft is not None:
             gamma = int(draft_tokens)
             if temperature != 0 or top_k is not None or graph or cache is not None:

@@ -26,7 +26,8 @@ from torchbooster_amd.ops.conv import Conv2d
 from torchbooster_amd.ops.act import swiglu
 from torchbooster_amd.ops.gemm import grouped_linear
 from torchbooster_amd.ops.norm import LayerNorm, RMSNorm
-from torchbooster_amd.ops.linear import MX_BLOCK, GeluLink, Linear, LinearGELU, linear, linear_rows, mx_quantize
+from torchbooster_amd.ops.linear import (MX_BLOCK, GeluLink, Linear, LinearGELU, linear, linear_rows,
+                                         linear_rows_experts, moe_route_rows, mx_quantize)
 
 __all__ = ["ViT", "vit_b_16", "vit_s_16", "vit_tiny", "Attention", "Block", "Rope", "SwiGLU", "MoE"]
 
@@ -399,7 +400,9 @@ class Block(nn.Module):
     ``sinks``: its attention sinks.
     ``mlp="moe"``: ``self.mlp`` is a :class:`MoE` of ``experts`` SwiGLU experts of that hidden width, ``top_k`` per
     token (its router and experts never have a bias; ``bias`` then governs ``qkv`` and ``proj`` alone);
-    ``forward_rows`` has no few-row expert kernel and raises ``ValueError``."""
+    ``forward_rows`` runs it on the few-row expert kernels (``ops.linear.moe_route_rows``, then
+    ``linear_rows_experts`` twice: 3 launches) once ``quantize_rows()`` has snapshotted the experts as MXFP4,
+    and raises ``ValueError`` before that; it does not update ``MoE.aux_loss``."""
 
     # the MXFP4 snapshots of quantize_rows, {name: (codes, scales)}: a plain attribute like the Rope tables
     mx_rows = None
@@ -458,8 +461,9 @@ class Block(nn.Module):
         ``extend``, to rounding.  ``rolling``: ``cache`` is a rolling pair (:class:`Attention`);
         ``kv_scales``: it is an fp8 pair with these scales."""
         at = self.attn
-        if isinstance(self.mlp, MoE):
-            raise ValueError("forward_rows (fused=True): there is no few-row kernel for an MoE block")
+        if not self.has_rows_path():
+            raise ValueError("forward_rows (fused=True): an MoE block decodes on the few-row kernels only with "
+                             "MXFP4 expert snapshots: call quantize_rows() first")
         if x.shape[1] != 1 and not extend:
             raise ValueError("forward_rows: more than one token per sequence needs extend=True")
         mx = self.mx_rows or {}
@@ -469,19 +473,46 @@ class Block(nn.Module):
                       **({} if kv_scales is None else {"kv_scales": kv_scales}))
         w, kw = rows_weight(at.proj, mx.get("proj"))
         x = linear_rows(a, w, at.proj.bias, residual=x, **kw)
+        if isinstance(self.mlp, MoE):
+            return self.moe_rows(x)
         act = "swiglu" if isinstance(self.mlp, SwiGLU) else "gelu"
         w, kw = rows_weight(self.mlp.fc1, mx.get("fc1"))
         h = linear_rows(x, w, self.mlp.fc1.bias, **norm_args(self.ln2), act=act, **kw)
         w, kw = rows_weight(self.mlp.fc2, mx.get("fc2"))
         return linear_rows(h, w, self.mlp.fc2.bias, residual=x, **kw)
 
+    def moe_rows(self, x: Tensor) -> Tensor:
+        """The MoE half of ``forward_rows``, ``x + mlp(ln2(x))`` on the residual stream ``x`` ``[..., dim]``, in three
+        launches (csrc/rows_experts_mx.hip): the router on the normed rows, the chosen experts' ``fc1`` with the norm
+        prologue and the SwiGLU epilogue, their ``fc2`` with the gated combine and the residual.  Needs the MXFP4
+        expert snapshots of ``quantize_rows``; forward only, and ``MoE.aux_loss`` is not updated."""
+        mx = self.mx_rows
+        rows = x.reshape(-1, x.shape[-1])
+        ids, gates = moe_route_rows(rows, self.mlp.router.weight, self.mlp.top_k, **norm_args(self.ln2))
+        h = linear_rows_experts(rows, *mx["fc1"], ids, **norm_args(self.ln2), act="swiglu")
+        return linear_rows_experts(h, *mx["fc2"], ids, gates=gates, residual=rows).view(x.shape)
+
+    def has_rows_path(self) -> bool:
+        """Whether ``forward_rows`` can run: always, except for an MoE block without the MXFP4 expert snapshots
+        of ``quantize_rows`` (there is no few-row kernel for bf16 experts)."""
+        return not isinstance(self.mlp, MoE) or {"fc1", "fc2"} <= set(self.mx_rows or {})
+
     def quantize_rows(self, fmt: Optional[str] = "mxfp4") -> None:
         """Snapshot ``qkv``, ``proj``, ``fc1`` and ``fc2`` as MXFP4 for ``forward_rows`` (``fmt=None``: drop the
-        snapshots); see ``TransformerLM.quantize_rows``.  An MoE MLP has no few-row path and is left alone."""
+        snapshots); see ``TransformerLM.quantize_rows``.  An MoE MLP's stacked experts become ``fc1`` = (codes
+        ``[E, 2 * hidden, dim / 2]``, scales ``[E, 2 * hidden, dim / 32]``) and ``fc2`` = (``[E, dim, hidden / 2]``,
+        ``[E, dim, hidden / 32]``), ``mx_quantize`` of the ``[E * rows, K]`` view, when ``dim`` and ``hidden`` are
+        both multiples of 32; its router stays bf16."""
         named = [("qkv", self.attn.qkv), ("proj", self.attn.proj)]
-        if not isinstance(self.mlp, MoE):
+        moe = isinstance(self.mlp, MoE)
+        if not moe:
             named += [("fc1", self.mlp.fc1), ("fc2", self.mlp.fc2)]
         self.mx_rows = mx_snapshots(named, fmt)
+        if moe and fmt is not None and self.mlp.fc1.shape[2] % MX_BLOCK == 0 and self.mlp.fc2.shape[2] % MX_BLOCK == 0:
+            for name, w in (("fc1", self.mlp.fc1), ("fc2", self.mlp.fc2)):
+                E, rows, K = w.shape
+                codes, scales = mx_quantize(w.reshape(E * rows, K))
+                self.mx_rows[name] = (codes.view(E, rows, K // 2), scales.view(E, rows, K // MX_BLOCK))
 
 
 class ViT(nn.Module):

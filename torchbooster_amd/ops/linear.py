@@ -22,6 +22,7 @@ fp16 activations) use ATen.  State-dict compatible with ``nn.Linear``.
 """
 from __future__ import annotations
 
+import functools
 import os
 from typing import Optional, Tuple
 
@@ -35,7 +36,7 @@ from torchbooster_amd.ops.act import swiglu
 from torchbooster_amd.ops.norm import rms_norm
 
 __all__ = ["Linear", "linear", "LinearGELU", "linear_gelu", "GeluLink", "linear_rows", "embed_rows",
-           "mx_quantize", "mx_dequantize"]
+           "mx_quantize", "mx_dequantize", "linear_rows_experts", "moe_route_rows"]
 
 # The fused epilogue stages the z tile through LDS with coalesced 16-B loads: 0.221 vs 0.273 ms
 # unfused, ViT-B/16 5245 / 5241 vs 5134 / 5137 img/s alternated (profiles/r03_gemm_nn/README.md;
@@ -337,6 +338,13 @@ def _mx_check(codes: Tensor, scales: Tensor, who: str) -> None:
                          f"{tuple(scales.shape)}")
 
 
+@functools.lru_cache(maxsize=None)
+def _e2m1_table(device) -> Tensor:
+    """The 16 e2m1 values by code, f32 on ``device``: made once, so that a later call copies nothing from the host
+    (a captured step may take a few-row fallback)."""
+    return torch.tensor(_E2M1 + tuple(-v for v in _E2M1), dtype=torch.float32, device=device)
+
+
 def mx_dequantize(codes: Tensor, scales: Tensor, dtype=torch.bfloat16) -> Tensor:
     """The ``[Q, K]`` tensor an MXFP4 pair of :func:`mx_quantize` stands for, in ``dtype``: element by element
     ``e2m1(code) * f32_from_bits(scale << 23)``, which is ``2^(scale - 127)`` for a scale byte in
@@ -344,7 +352,7 @@ def mx_dequantize(codes: Tensor, scales: Tensor, dtype=torch.bfloat16) -> Tensor
     :func:`mx_quantize` emits neither."""
     _mx_check(codes, scales, "mx_dequantize")
     Q = codes.shape[0]
-    table = torch.tensor(_E2M1 + tuple(-v for v in _E2M1), dtype=torch.float32, device=codes.device)
+    table = _e2m1_table(codes.device)
     nib = torch.stack((codes & 0xF, codes >> 4), dim=-1).reshape(Q, -1, MX_BLOCK)
     scale = (scales.to(torch.int32) << 23).view(torch.float32)
     return (table[nib.long()] * scale[..., None]).reshape(Q, -1).to(dtype)
@@ -444,6 +452,158 @@ def linear_rows(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, ln=
         if residual is not None:
             y = y + residual.to(y.dtype)
         return y
+
+
+def _rows_prologue(x: Tensor, ln, rms) -> Tensor:
+    """The norm prologue of the few-row fallbacks, in the dtype of ``x``."""
+    if rms is not None:
+        x = rms_norm(x, rms[0], float(rms[1]))
+    if ln is not None:
+        g, b, eps = ln
+        x = F.layer_norm(x, x.shape[-1:], None if g is None else g.to(x.dtype), None if b is None else b.to(x.dtype),
+                         float(eps))
+    return x
+
+
+def _norm_native_ok(ln, rms) -> bool:
+    return ((ln is None or (ln[0] is not None and ln[1] is not None and ln[0].dtype == torch.float32
+                            and ln[1].dtype == torch.float32 and ln[0].is_cuda and ln[1].is_cuda))
+            and (rms is None or (rms[0] is not None and rms[0].dtype == torch.float32 and rms[0].is_cuda)))
+
+
+def _norm_native_args(ln, rms):
+    if rms is not None:
+        return rms[0].contiguous(), None, float(rms[1])
+    if ln is not None:
+        return ln[0].contiguous(), ln[1].contiguous(), float(ln[2])
+    return None, None, 0.0
+
+
+ROUTE_MAX_EXPERTS = 256  # experts the fused router takes
+ROUTE_MAX_TOP_K = 16
+
+
+def linear_rows_experts(x: Tensor, codes: Tensor, mx_scales: Tensor, ids: Tensor, *, ln=None, rms=None,
+                        act: Optional[str] = None, gates: Optional[Tensor] = None,
+                        residual: Optional[Tensor] = None) -> Tensor:
+    """The few-row product of an MoE decode step: every (token, slot) pair against the MXFP4 weight of the
+    expert ``ids`` names for it, in ONE kernel.  ``codes`` uint8 ``[E, Qw, K / 2]`` and ``mx_scales`` uint8
+    ``[E, Qw, K / 32]`` are the stacked experts (:func:`mx_quantize` on the ``[E * Qw, K]`` view), ``ids`` int32
+    ``[M, top_k]`` a device tensor the kernel reads: nothing syncs and the call is capturable.  An id outside
+    ``[0, E)`` is CLAMPED into range on every path (the rule of :func:`embed_rows`).  Experts have no bias.
+
+    Pair mode (``gates=None``): ``x`` ``[M, K]`` -> ``[M, top_k, Q]``, pair ``(m, j)`` being
+    ``epilogue(prologue(x[m]) . dq(expert ids[m, j])^T)`` with the ``ln=`` / ``rms=`` prologues of
+    :func:`linear_rows`; ``Qw = Q``, or ``Qw = 2F`` (``gate | up``) and ``Q = F`` under ``act="swiglu"``.  The pair
+    has the bits of ``linear_rows(x[m:m+1], codes[e], mx_scales=mx_scales[e], ...)``.
+
+    Combine mode (``gates`` f32 ``[M, top_k]``): ``x`` ``[M, top_k, K]`` -> ``[M, Q]`` with ``y[m] = residual[m] +
+    sum_j gates[m, j] * (x[m, j] . dq(expert ids[m, j])^T)``: the products stay f32, are multiplied by the gates
+    and added in slot order onto the f32 residual (0 without one), and rounded once.  No prologue, no ``act``.
+
+    The native kernel (csrc/rows_experts_mx.hip) takes CUDA bf16 ``x`` / ``residual`` with ``K % 32 == 0``,
+    ``32 <= K <= 4096`` and at most 16 pairs ``M * top_k``; it streams each DISTINCT expert's weight once,
+    and token ``m`` has the same bits alone or among other tokens.  Everything else (CPU, other dtypes, more
+    pairs, ``TBAMD_FORCE_REFERENCE=1``) is the PyTorch composition on :func:`mx_dequantize` of the experts in
+    the dtype of ``x`` (each expert on every row, the named one kept: no host read either).  Shapes or dtypes
+    that do not fit raise ``ValueError``.  Forward only."""
+    _rows_forward_only(x, residual, gates, *((ln[0], ln[1]) if ln is not None else ()),
+                       *((rms[0],) if rms is not None else ()))
+    who = "linear_rows_experts"
+    comb = gates is not None
+    if act not in (None, "swiglu"):
+        raise ValueError(f"{who}: unsupported activation {act!r}")
+    if ln is not None and rms is not None:
+        raise ValueError(f"{who}: one prologue, ln or rms")
+    if comb and (act is not None or ln is not None or rms is not None):
+        raise ValueError(f"{who}: the combine mode (gates=) takes no prologue and no act")
+    if residual is not None and not comb:
+        raise ValueError(f"{who}: residual belongs to the combine mode (gates=)")
+    if codes.dim() != 3 or mx_scales.dim() != 3:
+        raise ValueError(f"{who}: codes [E, Qw, K / 2] and scales [E, Qw, K / 32] are stacks, not "
+                         f"{tuple(codes.shape)} and {tuple(mx_scales.shape)}")
+    E, Qw = codes.shape[:2]
+    if mx_scales.shape[0] != E or E < 1:
+        raise ValueError(f"{who}: {E} experts of codes, {mx_scales.shape[0]} of scales")
+    _mx_check(codes.reshape(E * Qw, codes.shape[2]), mx_scales.reshape(E * mx_scales.shape[1], mx_scales.shape[2]), who)
+    K = codes.shape[2] * 2
+    glu = act == "swiglu"
+    if glu and Qw % 2:
+        raise ValueError(f"{who}: act='swiglu' needs codes [E, 2F, K / 2], not {Qw} rows")
+    Q = Qw // 2 if glu else Qw
+    if ids.dim() != 2 or ids.dtype != torch.int32 or ids.shape[1] < 1:
+        raise ValueError(f"{who}: ids must be int32 [M, top_k], not {ids.dtype} {tuple(ids.shape)}")
+    M, top_k = ids.shape
+    if tuple(x.shape) != ((M, top_k, K) if comb else (M, K)):
+        raise ValueError(f"{who}: x {tuple(x.shape)} does not fit ids {tuple(ids.shape)} and K = {K}"
+                         + (" (combine mode: [M, top_k, K])" if comb else " (pair mode: [M, K])"))
+    if comb and (gates.dtype != torch.float32 or gates.shape != ids.shape):
+        raise ValueError(f"{who}: gates must be f32 {tuple(ids.shape)}, not {gates.dtype} {tuple(gates.shape)}")
+    if residual is not None and tuple(residual.shape) != (M, Q):
+        raise ValueError(f"{who}: residual must be [{M}, {Q}], not {tuple(residual.shape)}")
+    with torch.no_grad():
+        bf = torch.bfloat16
+        if (use_native(x) and x.dtype == bf and codes.is_cuda and mx_scales.is_cuda and ids.is_cuda
+                and 1 <= M * top_k <= ROWS_MAX and MX_BLOCK <= K <= ROWS_MAX_K
+                and not torch.is_autocast_enabled("cuda") and _norm_native_ok(ln, rms)
+                and (not comb or gates.is_cuda) and (residual is None or (residual.dtype == bf and residual.is_cuda))):
+            g, b, eps = _norm_native_args(ln, rms)
+            res = residual if residual is None or residual.stride(1) == 1 else residual.contiguous()
+            return native().rows_experts_mx(x.contiguous(), codes.contiguous(), mx_scales.contiguous(),
+                                            ids.contiguous(), None if not comb else gates.contiguous(), g, b, eps,
+                                            glu, res, rms=rms is not None)
+        idc = ids.to(torch.int64).clamp(0, E - 1)
+        h = _rows_prologue(x, ln, rms)
+        out = torch.zeros(M, top_k, Q, dtype=x.dtype, device=x.device)
+        for e in range(E):  # every expert on every row, the named one kept: shapes alone decide the work
+            ye = F.linear(h, mx_dequantize(codes[e], mx_scales[e], x.dtype))
+            if glu:
+                ye = swiglu(ye)
+            out = torch.where((idc == e)[:, :, None], ye if comb else ye[:, None, :], out)
+        if not comb:
+            return out
+        acc = torch.promote_types(x.dtype, torch.float32)
+        y = torch.zeros(M, Q, dtype=acc, device=x.device) if residual is None else residual.to(acc)
+        for j in range(top_k):
+            y = y + gates[:, j, None].to(acc) * out[:, j].to(acc)
+        return y.to(x.dtype)
+
+
+def moe_route_rows(x: Tensor, router_weight: Tensor, top_k: int, *, ln=None, rms=None) -> Tuple[Tensor, Tensor]:
+    """The router of an MoE decode step in ONE kernel: ``x`` ``[M, K]``, ``router_weight`` ``[E, K]`` -> ``(ids``
+    int32 ``[M, top_k]``, ``gates`` f32 ``[M, top_k])`` by the rule of ``models.vit.MoE.route`` on the normed row:
+    ``h = prologue(x)`` in the dtype of ``x`` (``ln=`` / ``rms=`` of :func:`linear_rows`), f32 logits ``h . w^T``, the
+    ``top_k`` largest in descending order with ties to the lower index, gates = the f32 softmax over those.
+    Ids are always in ``[0, E)``.
+
+    The native kernel (csrc/rows_experts_mx.hip) takes CUDA bf16 operands with ``1 <= M <= 16``, ``K % 8 == 0``,
+    ``K <= 4096``, ``E <= 256`` and ``top_k <= 16``; identical router rows give bit-identical logits.  Everything
+    else is the PyTorch rule: the norm, ``F.linear`` in f32, a stable descending sort, softmax.  Forward only."""
+    _rows_forward_only(x, router_weight, *((ln[0], ln[1]) if ln is not None else ()),
+                       *((rms[0],) if rms is not None else ()))
+    if ln is not None and rms is not None:
+        raise ValueError("moe_route_rows: one prologue, ln or rms")
+    if x.dim() != 2 or router_weight.dim() != 2 or router_weight.shape[1] != x.shape[1]:
+        raise ValueError(f"moe_route_rows: x [M, K] and router_weight [E, K] do not fit: {tuple(x.shape)} and "
+                         f"{tuple(router_weight.shape)}")
+    M, K = x.shape
+    E = router_weight.shape[0]
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= E:
+        raise ValueError(f"moe_route_rows: top_k must be an int in [1, E = {E}], not {top_k!r}")
+    with torch.no_grad():
+        bf = torch.bfloat16
+        if (use_native(x) and x.dtype == bf and router_weight.dtype == bf and router_weight.is_cuda
+                and 1 <= M <= ROWS_MAX and K % 8 == 0 and 8 <= K <= ROWS_MAX_K and E <= ROUTE_MAX_EXPERTS
+                and top_k <= ROUTE_MAX_TOP_K and not torch.is_autocast_enabled("cuda") and _norm_native_ok(ln, rms)):
+            rows = x
+            if rows.stride(1) != 1 or (M > 1 and rows.stride(0) % 8) or rows.data_ptr() % 16:
+                rows = rows.contiguous()
+            g, b, eps = _norm_native_args(ln, rms)
+            return native().moe_route(rows, router_weight.contiguous(), top_k, g, b, eps, rms=rms is not None)
+        h = _rows_prologue(x, ln, rms)
+        logits = F.linear(h.float(), router_weight.float())
+        top, idx = torch.sort(logits, dim=-1, descending=True, stable=True)  # stable: ties to the lower index
+        return idx[:, :top_k].to(torch.int32), torch.softmax(top[:, :top_k], dim=-1)
 
 
 def embed_rows(tokens: Tensor, tok_weight: Tensor, pos_weight: Optional[Tensor] = None,
