@@ -1,4 +1,4 @@
-// Bindings of the dense GEMM kernels (gemm.hip, gemm8.hip), of the grouped GEMM (gemm_grouped.hip) and
+// Bindings of the dense GEMM kernels (gemm.hip, gemm8.hip, gemm_mx.hip), of the grouped GEMM (gemm_grouped.hip) and
 // of the bias-gradient / GELU kernels that go with them (colsum.hip).
 #include "bind_common.h"
 
@@ -110,6 +110,57 @@ std::vector<Tensor> gemm_nn_gelu_bwd(const Tensor& dy, const Tensor& w_, const T
   }
   tbamd::colsum_finalize(dt_code(db), part.data_ptr<float>(), ntp, (int)Q, db.data_ptr(), cur_stream());
   return {y, db};
+}
+
+// y [P, Q] = epi(x @ dq(codes, scales)^T + bias) on an MXFP4 weight (gemm_mx.hip): x bf16 [P, K], codes uint8
+// [Q, K / 2], scales uint8 [Q, K / 32], any P and Q, K % 32 == 0.  epi 0 (none), 1 (exact GELU) or
+// 2 (+ residual [P, Q]).
+Tensor gemm_mx(const Tensor& x, const Tensor& codes, const Tensor& scales, const optional<Tensor>& bias, int64_t epi,
+               const optional<Tensor>& residual) {
+  check_rows_bf16(x, "x");
+  const at::DeviceGuard guard(x.device());
+  check_cuda(codes, "codes");
+  check_cuda(scales, "scales");
+  TORCH_CHECK(codes.scalar_type() == at::kByte && scales.scalar_type() == at::kByte && codes.dim() == 2 &&
+                  scales.dim() == 2 && codes.is_contiguous() && scales.is_contiguous() &&
+                  codes.device() == x.device() && scales.device() == x.device(),
+              "gemm_mx: codes [Q, K / 2] and scales [Q, K / 32] must be contiguous uint8 on the device of x");
+  const int64_t P = x.size(0), K = x.size(1), Q = codes.size(0);
+  TORCH_CHECK(K % 32 == 0 && K >= 32 && codes.size(1) * 2 == K && scales.size(0) == Q && scales.size(1) * 32 == K,
+              "gemm_mx: K % 32 == 0, K >= 32, codes [Q, K / 2] and scales [Q, K / 32]");
+  TORCH_CHECK(P >= 1 && Q >= 1 && P < (1ll << 31) - 256 && Q < (1ll << 31) - 256 && K < (1ll << 31) - 256 &&
+                  ((P + 63) / 64) * ((Q + 31) / 32) < (1ll << 31),
+              "gemm_mx: dims out of range");
+  TORCH_CHECK(x.stride(0) >= K || P == 1, "gemm_mx: overlapping rows of x");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(codes.data_ptr()) % 16 == 0, "gemm_mx: codes must be 16-B aligned");
+  TORCH_CHECK(epi >= 0 && epi <= 2, "gemm_mx: epilogue 0 (none), 1 (gelu) or 2 (residual)");
+  tbamd::GemmMxArgs a{};
+  a.X = reinterpret_cast<const uint16_t*>(x.data_ptr());
+  a.codes = codes.data_ptr<uint8_t>();
+  a.scales = scales.data_ptr<uint8_t>();
+  a.ldx = x.stride(0);
+  if (given(bias)) {
+    check_cuda(*bias, "bias");
+    TORCH_CHECK(bias->scalar_type() == at::kBFloat16 && bias->dim() == 1 && bias->size(0) == Q &&
+                    bias->is_contiguous() && bias->device() == x.device(),
+                "gemm_mx: bias must be contiguous bf16 [Q]");
+    a.bias = reinterpret_cast<const uint16_t*>(bias->data_ptr());
+  }
+  TORCH_CHECK((epi == 2) == given(residual), "gemm_mx: a residual comes with epilogue 2 and only with it");
+  if (given(residual)) {
+    const Tensor& r = *residual;
+    check_cuda(r, "residual");
+    TORCH_CHECK(r.scalar_type() == at::kBFloat16 && r.dim() == 2 && r.size(0) == P && r.size(1) == Q &&
+                    r.stride(1) == 1 && (P == 1 || r.stride(0) >= Q) && r.device() == x.device(),
+                "gemm_mx: residual must be bf16 [P, Q] with a unit column stride");
+    a.res = reinterpret_cast<const uint16_t*>(r.data_ptr());
+    a.ldres = r.stride(0);
+  }
+  Tensor y = at::empty({P, Q}, x.options());
+  a.Y = reinterpret_cast<uint16_t*>(y.data_ptr());
+  a.P = (int)P, a.Q = (int)Q, a.K = (int)K, a.epi = (int)epi;
+  tbamd::gemm_mx(a, cur_stream());
+  return y;
 }
 
 // --------------------------------------------- grouped GEMM (gemm_grouped.hip)
@@ -228,6 +279,12 @@ void register_gemm(pybind11::module& m) {
   m.def("gemm", &gemm, py::arg("x"), py::arg("w"), py::arg("tw") = false, py::arg("bias") = py::none(),
         py::arg("residual") = py::none(), py::arg("epi") = 0, py::arg("want_z") = false, py::arg("tile") = -1,
         py::arg("out") = py::none(), py::arg("tx") = false, py::arg("splits") = 1);
+  m.def("gemm_mx", &gemm_mx, py::arg("x"), py::arg("codes"), py::arg("scales"), py::arg("bias") = py::none(),
+        py::arg("epi") = 0, py::arg("residual") = py::none());
+  m.def("gemm_mx_tile_rows", [](int64_t P) {
+    TORCH_CHECK(P >= 1 && P < (1ll << 31), "gemm_mx_tile_rows: bad P");
+    return (int64_t)tbamd::gemm_mx_tile_rows((int)P);
+  });
   m.def("gemm_nn_gelu_bwd", &gemm_nn_gelu_bwd, py::arg("dy"), py::arg("w"), py::arg("z"),
         py::arg("db_out") = py::none(), py::arg("wt") = py::none());
   m.def("grouped_rows", &grouped_rows, py::arg("x"), py::arg("w"), py::arg("offsets"), py::arg("tw") = false);

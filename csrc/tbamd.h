@@ -431,6 +431,24 @@ struct RowsLinearMxArgs {
 int rows_mx_block_lanes(int K);                      // lanes per column (LB), from K alone
 int rows_mx_cols_per_wave(int Q, int K, bool glu);  // output columns per wave, from (Q, K) alone
 void rows_linear_mx(const RowsLinearMxArgs& a, hipStream_t st);
+// Dense GEMM on an MXFP4 weight for any number of rows (csrc/gemm_mx.hip): y[P][Q] = epilogue(x[P][K] .
+// dq(codes, scales)[Q][K]^T + bias) on the MFMA, codes / scales as in RowsLinearMxArgs.  Any P, Q >= 1,
+// K % 32 == 0, K >= 32.  x: row stride ldx (a multiple of 8), 16-B aligned; y contiguous.  bias (bf16 [Q])
+// may be null; epi kRowsNone, kRowsGelu (exact GELU) or kRowsResidual (+ res[P][Q], row stride ldres).
+// vec is filled in by gemm_mx.  Row p has the same bits for every P with the same gemm_mx_tile_rows(P).
+struct GemmMxArgs {
+  const uint16_t* X;
+  const uint8_t* codes;
+  const uint8_t* scales;
+  uint16_t* Y;
+  const uint16_t* bias;
+  const uint16_t* res;
+  int P, Q, K, epi;
+  int64_t ldx, ldres;
+  int vec;
+};
+int gemm_mx_tile_rows(int P);  // rows per workgroup of the tile that serves P rows: 64 or 128
+void gemm_mx(const GemmMxArgs& a, hipStream_t st);
 // The product with the weight chosen per (token, slot) pair from a stack of MXFP4 experts
 // (csrc/rows_experts_mx.hip): codes [E][Qw][K / 2], scales [E][Qw][K / 32] contiguous, ids int32
 // [M][top_k] read by the kernel and clamped into [0, E), P = M * top_k <= 16 pairs.

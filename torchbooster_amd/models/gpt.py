@@ -322,14 +322,26 @@ class TransformerLM(nn.Module):
 
     # ---------------------------------------------------------------- generation (forward only)
     def prefill(self, tokens: Tensor, lengths: Optional[Tensor] = None,
-                cache: Optional[KVCache] = None) -> Tuple[Tensor, KVCache]:
+                cache: Optional[KVCache] = None, *, mx: bool = False) -> Tuple[Tensor, KVCache]:
         """Run the prompt ``[B, N]`` once (causal, ``key_lengths=lengths``) and fill ``cache`` (a fresh
         full-size one by default) from row 0.  Returns the logits ``[B, vocab]`` of each sequence's last
         valid token -- position ``lengths[b] - 1``, or ``N - 1`` -- and the cache, whose ``positions`` are
-        now the (clamped) lengths: the pad rows of a ragged batch are overwritten as each sequence grows."""
+        now the (clamped) lengths: the pad rows of a ragged batch are overwritten as each sequence grows.
+
+        ``mx=True``: ``qkv``, ``proj``, ``fc1`` and ``fc2`` of every block multiply by their MXFP4 snapshots
+        (``quantize_rows``) through ``ops.linear.linear_mx`` (csrc/gemm_mx.hip), bias and GELU in its epilogue, so
+        the cache rows come from the weights the ``fused=True`` steps decode against; norms, rotation, attention,
+        the append and the last-row head are unchanged, and a linear ``quantize_rows`` skipped stays bf16.
+        Without snapshots, or on a model with MoE blocks, it raises ``ValueError``."""
         B, N = tokens.shape
         if N > self.max_len:
             raise ValueError(f"sequence length {N} exceeds max_len {self.max_len}")
+        mkw = {}  # mx=False: the calls it always made
+        if mx:
+            if self.mx_rows is None or any(blk.mx_rows is None or isinstance(blk.mlp, MoE) for blk in self.blocks):
+                raise ValueError("prefill(mx=True) needs the MXFP4 snapshots of quantize_rows() and dense MLPs "
+                                 "in every block")
+            mkw["mx"] = True
         with torch.no_grad():
             if cache is None:
                 cache = KVCache(self, B)
@@ -341,11 +353,11 @@ class TransformerLM(nn.Module):
             for blk, kv, ring, sc in zip(self.blocks, cache.layers, cache.rolling, cache.scales):
                 if sc is not None:  # an fp8 layer: the append quantises
                     x, pending = blk(x, pending, lengths, cache=kv, positions=cache.positions,
-                                     **({"rolling": True} if ring else {}), kv_scales=sc)
+                                     **({"rolling": True} if ring else {}), kv_scales=sc, **mkw)
                 elif ring:  # the ring append: the last R valid rows of each sequence
-                    x, pending = blk(x, pending, lengths, cache=kv, positions=cache.positions, rolling=True)
+                    x, pending = blk(x, pending, lengths, cache=kv, positions=cache.positions, rolling=True, **mkw)
                 else:
-                    x, pending = blk(x, pending, lengths, cache=kv, positions=cache.positions)
+                    x, pending = blk(x, pending, lengths, cache=kv, positions=cache.positions, **mkw)
             if lengths is None:
                 cache.positions.fill_(N)
             else:
@@ -404,7 +416,7 @@ class TransformerLM(nn.Module):
         The snapshots are plain attributes (``blocks[i].mx_rows``, ``mx_rows``), like the :class:`Rope` tables:
         no parameters, no buffers, no state-dict keys.  They are built on the device the weights are on and
         do not follow the weights: after changing or moving them, call this again.  The bf16 parameters stay
-        -- ``fused=False``, ``prefill``, ``forward`` and ``loss`` read them."""
+        -- ``fused=False``, ``prefill`` (unless ``mx=True``), ``forward`` and ``loss`` read them."""
         head = mx_snapshots([("head", self.head)], fmt)
         for blk in self.blocks:
             blk.quantize_rows(fmt)
@@ -519,7 +531,7 @@ class TransformerLM(nn.Module):
                  generator=None, graph: bool = False, cache: Optional[KVCache] = None,
                  draft: Optional["TransformerLM"] = None, draft_tokens: int = 4,
                  fused: bool = False, rolling: bool = False, kv_dtype=None,
-                 kv_scales=None) -> Tuple[Tensor, Tensor]:
+                 kv_scales=None, mx_prefill: bool = False) -> Tuple[Tensor, Tensor]:
         """Continue the prompts ``tokens`` ``[B, N]`` (``lengths``: valid tokens of each, right-padded) by
         ``max_new_tokens`` tokens -> ``(out [B, max_new_tokens], out_lengths [B])``.
 
@@ -561,8 +573,13 @@ class TransformerLM(nn.Module):
         ``kv_dtype`` / ``kv_scales``: the ``dtype`` and ``scales`` of the caches made here (:class:`KVCache`;
         ``torch.float8_e4m3fn`` is the fp8 cache, ``kv_scales`` as its ``scales``).  With ``draft`` the draft's
         cache gets ``kv_dtype`` and scales of 1.  A caller's ``cache`` brings its own and takes neither
-        (``ValueError``).  Works with ``graph=True``, ``fused=True`` and ``rolling=True``."""
+        (``ValueError``).  Works with ``graph=True``, ``fused=True`` and ``rolling=True``.
+
+        ``mx_prefill=True``: the prefill made here is ``prefill(mx=True)``, on the MXFP4 snapshots the ``fused=True``
+        steps decode against.  It belongs to that prefill: with ``cache`` or ``draft`` it raises ``ValueError``."""
         B, N = tokens.shape
+        if mx_prefill and (cache is not None or draft is not None):
+            raise ValueError("mx_prefill is for the prefill generate makes itself: no cache and no draft")
         max_new_tokens = int(max_new_tokens)
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be at least 1")
@@ -611,7 +628,7 @@ class TransformerLM(nn.Module):
                 if kv_scales is not None:
                     ckw["scales"] = kv_scales
                 cache = KVCache(self, B, capacity=N + max_new_tokens, **ckw)
-                logits, _ = self.prefill(tokens, lengths, cache)
+                logits, _ = self.prefill(tokens, lengths, cache, **({"mx": True} if mx_prefill else {}))
             else:
                 logits = self.extend(tokens, cache, lengths, last_only=True, **kw)
                 start = cache.positions.clone()  # start[b] + prompt_len[b]

@@ -26,7 +26,7 @@ from torchbooster_amd.ops.conv import Conv2d
 from torchbooster_amd.ops.act import swiglu
 from torchbooster_amd.ops.gemm import grouped_linear
 from torchbooster_amd.ops.norm import LayerNorm, RMSNorm
-from torchbooster_amd.ops.linear import (MX_BLOCK, GeluLink, Linear, LinearGELU, linear, linear_rows,
+from torchbooster_amd.ops.linear import (MX_BLOCK, GeluLink, Linear, LinearGELU, linear, linear_mx, linear_rows,
                                          linear_rows_experts, moe_route_rows, mx_quantize)
 
 __all__ = ["ViT", "vit_b_16", "vit_s_16", "vit_tiny", "Attention", "Block", "Rope", "SwiGLU", "MoE"]
@@ -97,6 +97,16 @@ def rows_weight(lin, mx):
     """The weight argument and the extra keywords of a ``linear_rows`` call on ``lin``: the parameter, or its
     MXFP4 snapshot ``mx = (codes, scales)``."""
     return (lin.weight, {}) if mx is None else (mx[0], {"mx_scales": mx[1]})
+
+
+def snap_linear(lin, mx, name: str):
+    """What multiplies by ``lin`` in a forward with the MXFP4 snapshots ``mx`` (``{name: (codes, scales)}`` or
+    None): ``lin`` itself without a snapshot called ``name``, else ``ops.linear.linear_mx`` on the snapshot with
+    ``lin``'s bias (keywords: its ``act=`` / ``residual=``)."""
+    snap = (mx or {}).get(name)
+    if snap is None:
+        return lin
+    return lambda x, **kw: linear_mx(x, snap[0], snap[1], lin.bias, **kw)
 
 
 def make_norm(kind: str, dim: int):
@@ -218,15 +228,17 @@ class Attention(nn.Module):
 
     def forward(self, x: Tensor, key_lengths: Optional[Tensor] = None, *, cache=None,
                 positions: Optional[Tensor] = None, extend: bool = False, rolling: bool = False,
-                kv_scales=None) -> Tensor:
+                kv_scales=None, mx=None) -> Tensor:
+        # mx: the block's MXFP4 snapshots (a quantised prefill); None: the parameters, the calls it always made
+        qkv, proj = snap_linear(self.qkv, mx, "qkv"), snap_linear(self.proj, mx, "proj")
         if cache is not None:
             rkw = {"rolling": True} if rolling else {}  # a linear cache: the call it always made
             if kv_scales is not None:  # likewise a cache that is not fp8
                 rkw["kv_scales"] = kv_scales
-            return self.proj(self.cached(self.qkv(x), cache, positions, key_lengths, extend=extend, **rkw))
+            return proj(self.cached(qkv(x), cache, positions, key_lengths, extend=extend, **rkw))
         kw = self._kw()
-        return self.proj(attention_packed(self.rotate(self.qkv(x)), self.heads, 1.0 / math.sqrt(self.hd),
-                                          causal=self.causal, key_lengths=key_lengths, **kw))
+        return proj(attention_packed(self.rotate(qkv(x)), self.heads, 1.0 / math.sqrt(self.hd),
+                                     causal=self.causal, key_lengths=key_lengths, **kw))
 
     def cached(self, qkv: Tensor, cache, positions: Optional[Tensor], key_lengths: Optional[Tensor] = None, *,
                extend: bool = False, fused: bool = False, rolling: bool = False, kv_scales=None) -> Tensor:
@@ -269,7 +281,10 @@ class MLP(nn.Module):
         self.fc1 = LinearGELU(dim, hidden, bias=bias)  # GELU fused into its backward / bias-grad pass
         self.fc2 = Linear(hidden, dim, bias=bias)
 
-    def forward(self, x: Tensor) -> Tensor:
+    def forward(self, x: Tensor, *, mx=None) -> Tensor:
+        if mx:  # MXFP4 snapshots (forward only): GELU in fc1's epilogue
+            fc1 = snap_linear(self.fc1, mx, "fc1")
+            return snap_linear(self.fc2, mx, "fc2")(fc1(x) if fc1 is self.fc1 else fc1(x, act="gelu"))
         # fc2 is the hidden activation's only consumer: its input gradient takes fc1's GELU
         # backward and bias gradient into the same GEMM epilogue (ops/linear.py GeluLink)
         link = GeluLink()
@@ -285,8 +300,8 @@ class SwiGLU(nn.Module):
         self.fc1 = Linear(dim, 2 * hidden, bias=bias)
         self.fc2 = Linear(hidden, dim, bias=bias)
 
-    def forward(self, x: Tensor) -> Tensor:
-        return self.fc2(swiglu(self.fc1(x)))
+    def forward(self, x: Tensor, *, mx=None) -> Tensor:
+        return snap_linear(self.fc2, mx, "fc2")(swiglu(snap_linear(self.fc1, mx, "fc1")(x)))
 
 
 class _Permute(torch.autograd.Function):
@@ -429,25 +444,31 @@ class Block(nn.Module):
 
     def forward(self, x: Tensor, pending: Optional[Tensor] = None, key_lengths: Optional[Tensor] = None, *,
                 cache=None, positions: Optional[Tensor] = None, extend: bool = False, rolling: bool = False,
-                kv_scales=None):
+                kv_scales=None, mx: bool = False):
         """``x``: residual stream; ``pending``: a sub-block output not yet added
         to it.  Returns (stream, pending) so adds fuse into the next LayerNorm.
         ``key_lengths``: per-batch key lengths for the attention (None: every key).
         ``cache`` / ``positions`` / ``extend`` / ``rolling`` / ``kv_scales``: this layer's KV cache, passed to
-        :class:`Attention`."""
+        :class:`Attention`.  ``mx``: ``qkv``, ``proj``, ``fc1`` and ``fc2`` multiply by their MXFP4 snapshots
+        (``quantize_rows``) through ``ops.linear.linear_mx``; forward only, dense MLPs only (``ValueError``)."""
+        mkw = {}  # mx=False: the calls it always made
+        if mx:
+            if isinstance(self.mlp, MoE) or self.mx_rows is None:
+                raise ValueError("mx=True needs a dense MLP and the MXFP4 snapshots of quantize_rows()")
+            mkw["mx"] = self.mx_rows
         if pending is None:
             h = self.ln1(x)
         else:
             h, x = self.ln1(x, pending)
         if kv_scales is not None:  # an fp8 cache
             a = self.attn(h, key_lengths, cache=cache, positions=positions, extend=extend,
-                          **({"rolling": True} if rolling else {}), kv_scales=kv_scales)
+                          **({"rolling": True} if rolling else {}), kv_scales=kv_scales, **mkw)
         elif rolling:
-            a = self.attn(h, key_lengths, cache=cache, positions=positions, extend=extend, rolling=True)
+            a = self.attn(h, key_lengths, cache=cache, positions=positions, extend=extend, rolling=True, **mkw)
         else:
-            a = self.attn(h, key_lengths, cache=cache, positions=positions, extend=extend)
+            a = self.attn(h, key_lengths, cache=cache, positions=positions, extend=extend, **mkw)
         h, x = self.ln2(x, a)
-        return x, self.mlp(h)
+        return x, self.mlp(h, **mkw)
 
     def forward_rows(self, x: Tensor, *, cache, positions: Tensor, extend: bool = False,
                      rolling: bool = False, kv_scales=None) -> Tensor:

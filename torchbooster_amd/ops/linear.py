@@ -13,7 +13,8 @@ img_cls/lenet/lenet.py:33-35, resnet.py:112) -> cuBLAS.  Here, per step:
 Decoding has 1 - 16 rows per product, nothing for that engine's 128 - 256 row tiles:
 ``linear_rows`` is the weight-streaming few-row kernel of csrc/rows_gemm.hip with a LayerNorm
 prologue and bias / GELU / residual epilogues, ``embed_rows`` the fused token + position embedding
-(both forward only).
+(both forward only).  ``linear_mx`` is the dense product on an MXFP4 weight for any number of rows
+(csrc/gemm_mx.hip): what ``linear_rows(mx_scales=)`` runs past 16 rows and a quantised prefill multiplies by.
 
 Weight/bias gradients land straight in the parameter's persistent gradient
 slot (ops/_ext.py ``take_slot``) — no accumulate-add or bucket copy per step.
@@ -33,10 +34,10 @@ from torch import Tensor, nn
 from torchbooster_amd.ops import gemm as G
 from torchbooster_amd.ops._ext import native, slot_alias, take_slot, use_native
 from torchbooster_amd.ops.act import swiglu
-from torchbooster_amd.ops.norm import rms_norm
+from torchbooster_amd.ops.norm import layer_norm, rms_norm
 
 __all__ = ["Linear", "linear", "LinearGELU", "linear_gelu", "GeluLink", "linear_rows", "embed_rows",
-           "mx_quantize", "mx_dequantize", "linear_rows_experts", "moe_route_rows"]
+           "mx_quantize", "mx_dequantize", "linear_mx", "linear_rows_experts", "moe_route_rows"]
 
 # The fused epilogue stages the z tile through LDS with coalesced 16-B loads: 0.221 vs 0.273 ms
 # unfused, ViT-B/16 5245 / 5241 vs 5134 / 5137 img/s alternated (profiles/r03_gemm_nn/README.md;
@@ -358,6 +359,61 @@ def mx_dequantize(codes: Tensor, scales: Tensor, dtype=torch.bfloat16) -> Tensor
     return (table[nib.long()] * scale[..., None]).reshape(Q, -1).to(dtype)
 
 
+def linear_mx(x: Tensor, codes: Tensor, mx_scales: Tensor, bias: Optional[Tensor] = None, *,
+              act: Optional[str] = None, residual: Optional[Tensor] = None) -> Tensor:
+    """``epilogue(linear(x, dq(codes, mx_scales), bias))`` on an MXFP4 weight (:func:`mx_quantize`), for any number
+    of rows: ``x`` ``[..., K]``, ``codes`` uint8 ``[Q, K / 2]``, ``mx_scales`` uint8 ``[Q, K / 32]``, ``bias`` ``[Q]`` ->
+    ``[..., Q]``.  ``act="gelu"``: exact GELU; ``residual`` ``[..., Q]``: added.  Both work on the f32 accumulator,
+    which is rounded once at the store; they exclude each other.  Shapes or dtypes that do not fit raise
+    ``ValueError``.  Forward only.
+
+    The native kernel (csrc/gemm_mx.hip) takes CUDA bf16 ``x`` / ``bias`` / ``residual`` with ``K % 32 == 0``, any
+    number of rows and any ``Q``: the codes are decoded to bf16 in registers (``v_cvt_scalef32_pk_bf16_fp4``,
+    exact) on their way into LDS and multiplied on the bf16 MFMA with f32 accumulation; the bf16 weight is never
+    written to memory.  Up to 128 rows run a 64-row tile, more a 128-row tile, and a row has the same bits for
+    every row count served by the same tile.  Everything else (CPU tensors, other dtypes, autocast,
+    ``TBAMD_FORCE_REFERENCE=1``) is ``F.linear`` on ``mx_dequantize(codes, mx_scales, x.dtype)``, then ``F.gelu`` or
+    ``+ residual``."""
+    _rows_forward_only(x, bias, residual)
+    if act not in (None, "gelu"):
+        raise ValueError(f"linear_mx: unsupported activation {act!r}")
+    if act is not None and residual is not None:
+        raise ValueError("linear_mx: one epilogue, act or residual")
+    _mx_check(codes, mx_scales, "linear_mx")
+    K, Q = x.shape[-1], codes.shape[0]
+    if codes.shape[1] * 2 != K:
+        raise ValueError(f"linear_mx: MXFP4 codes {tuple(codes.shape)} do not fit x [..., {K}]")
+    if bias is not None and tuple(bias.shape) != (Q,):
+        raise ValueError(f"linear_mx: bias must be [{Q}], not {tuple(bias.shape)}")
+    lead = x.shape[:-1]
+    if residual is not None and tuple(residual.shape) != (*lead, Q):
+        raise ValueError(f"linear_mx: residual must be {(*lead, Q)}, not {tuple(residual.shape)}")
+    with torch.no_grad():
+        bf = torch.bfloat16
+        if (use_native(x) and x.dtype == bf and codes.is_cuda and mx_scales.is_cuda and K >= MX_BLOCK and Q >= 1
+                and x.numel() > 0 and not torch.is_autocast_enabled("cuda")
+                and (bias is None or (bias.dtype == bf and bias.is_cuda))
+                and (residual is None or (residual.dtype == bf and residual.is_cuda))):
+            rows = x.reshape(-1, K)
+            if rows.stride(1) != 1 or rows.stride(0) % 8 or rows.stride(0) < K or rows.data_ptr() % 16:
+                rows = rows.contiguous()
+            res = None
+            if residual is not None:
+                res = residual.reshape(-1, Q)
+                if res.stride(1) != 1 or res.stride(0) < Q:
+                    res = res.contiguous()
+            y = native().gemm_mx(rows, codes.contiguous(), mx_scales.contiguous(),
+                                 None if bias is None else bias.contiguous(),
+                                 1 if act == "gelu" else 2 if res is not None else 0, res)
+            return y.view(*lead, Q)
+        y = F.linear(x, mx_dequantize(codes, mx_scales, x.dtype), None if bias is None else bias.to(x.dtype))
+        if act == "gelu":
+            y = F.gelu(y)
+        if residual is not None:
+            y = y + residual.to(y.dtype)
+        return y
+
+
 def linear_rows(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, ln=None, act: Optional[str] = None,
                 residual: Optional[Tensor] = None, rms=None, mx_scales: Optional[Tensor] = None) -> Tensor:
     """``epilogue(linear(prologue(x), weight, bias))`` for the few rows of a decode step, in ONE kernel.
@@ -383,8 +439,11 @@ def linear_rows(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, ln=
     ``mx_scales``: the weight is MXFP4 (:func:`mx_quantize`): ``weight`` holds the uint8 codes ``[Q, K / 2]``
     (``[2F, K / 2]`` under ``act="swiglu"``) and ``mx_scales`` the uint8 scales ``[Q, K / 32]``; shapes or dtypes
     that do not fit raise ``ValueError``.  The native kernel (csrc/rows_gemm_mx.hip) takes the same operands
-    with ``K % 32 == 0``, ``32 <= K <= 4096``, and streams 4.25 bits per weight; everything else is the
-    composition above on ``mx_dequantize(weight, mx_scales, x.dtype)``."""
+    with ``K % 32 == 0``, ``32 <= K <= 4096``, and streams 4.25 bits per weight.  More than 16 rows of CUDA bf16
+    operands never dequantise the weight either: they run the norm (``ops.norm.layer_norm`` / ``rms_norm``), then
+    :func:`linear_mx` (csrc/gemm_mx.hip, any ``K % 32 == 0``) with the bias / GELU / residual epilogue, then
+    ``ops.act.swiglu`` under ``act="swiglu"``.  Everything else is the composition above on
+    ``mx_dequantize(weight, mx_scales, x.dtype)``."""
     _rows_forward_only(x, weight, bias, residual, *((ln[0], ln[1]) if ln is not None else ()),
                        *((rms[0],) if rms is not None else ()))
     if act not in (None, "gelu", "swiglu"):
@@ -435,6 +494,18 @@ def linear_rows(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, ln=
                 y = native().rows_linear(rows, weight.contiguous(), None if bias is None else bias.contiguous(), g, b,
                                          eps, epi, res, rms=rms is not None)
             return y.view(*lead, Q)
+        if (mx and M > ROWS_MAX and use_native(x) and x.dtype == bf and weight.is_cuda and mx_scales.is_cuda
+                and K >= MX_BLOCK and not torch.is_autocast_enabled("cuda") and _norm_native_ok(ln, rms)
+                and (bias is None or (bias.dtype == bf and bias.is_cuda))
+                and (residual is None or (residual.dtype == bf and residual.is_cuda))):
+            # more rows than the few-row kernel takes: the norm, the MFMA product on the codes, the gate
+            h = x
+            if rms is not None:
+                h = rms_norm(h, rms[0], float(rms[1]))
+            if ln is not None:
+                h = layer_norm(h, ln[0], ln[1], float(ln[2]))
+            y = linear_mx(h, weight, mx_scales, bias, act="gelu" if act == "gelu" else None, residual=residual)
+            return swiglu(y) if glu else y
         if mx:
             weight = mx_dequantize(weight, mx_scales, x.dtype)
         h = x
